@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: density-eval samples/sec of a Boosted-Glow mixture on MI355X.
 
-    python bench.py [--gpus N --steps K --warmup W]
+    python bench.py [--gpus N --steps K --warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -22,16 +22,23 @@ of float32[C/N, S*batch] per rank per group rebuilds (C, S*batch) before the rec
 Timing: 2000 x `--prewarm` untimed steps let the clocks of a cold GPU settle, then W untimed warm-up steps, then exactly
 K timed steps between barriers + device synchronisations, MAX over ranks.
 
+A plain run does only that and prints the line: set-up, warm-up, the K timed steps, the outputs of the last timed step if
+`--dump-outputs DIR` is given (DIR/G.npy: G (batch,) of that step, float32; inputs and weights come from fixed seeds, so two
+runs with the same arguments compute from identical inputs), and the result line.  `--full` adds everything else the
+benchmark measures: the CPU baseline, the other legs and BASELINE configurations, the repetitions of a short timed region
+(a run of fewer than 4 groups is repeated 21 x and `value` comes from the median repetition) and the full record.
+
 Prints ONE JSON line on rank 0, the LAST line on stdout, at most LINE_LIMIT (6000) bytes (compact_line: the driver contract's
 keys only), including
+  "ms_per_step":  milliseconds one timed step took
   "dtype":        the arithmetic the timed kernel computes in ("f16x3" = f32 operands split into two fp16 pieces, three
                   f16 MFMAs per product, f32 accumulate; "bf16x6"; "f32" = exact f32-input MFMA)
   "roofline":     dominant kernel (the fused flow kernel) against the dense MFMA peak of the pipe it runs on
-  "cpu_baseline": the torch-CPU oracle ("port" of the reference path) timed on this box's cores
-  "configs" / "legs_summary": (N = 1) one [value, frac, executed_frac] triple per other BASELINE configuration / leg.
-Everything else measured in the run -- the legs in full (the exact-f32 kernel, one batch per launch, the reference's batch
+  "cpu_baseline": (--full) the torch-CPU oracle ("port" of the reference path) timed on this box's cores
+  "configs" / "legs_summary": (--full, N = 1) one [value, frac, executed_frac] triple per other BASELINE configuration / leg.
+Everything else a --full run measures -- the legs in full (the exact-f32 kernel, one batch per launch, the reference's batch
 sizes, the module's evaluate loop, every other configuration's own line), the notes, the thread probes -- goes to stderr
-and to the side file the line names ("full_record": gpurun_out/bench_full.json).
+and to the side file the line names ("full_record", set by --full-record).
 """
 import argparse
 import ctypes
@@ -374,9 +381,9 @@ def config_legs(args):
     tools = os.path.join(REPO, "tools")
     cpu = str(min(3.0, args.cpu_seconds))
     jobs = [
-        ("miniboone_glow_c4_n4096", [py, bench, "--config", "miniboone_glow", "--components", "4", "--steps", "2048", "--prewarm", "0.1",
+        ("miniboone_glow_c4_n4096", [py, bench, "--full", "--config", "miniboone_glow", "--components", "4", "--steps", "2048", "--prewarm", "0.1",
                                      "--cpu-seconds", cpu, "--no-extra-legs", "--no-config-legs"]),
-        ("hepmass_realnvp_c8_n65536", [py, bench, "--config", "hepmass_realnvp", "--steps", "256", "--warmup", "32", "--prewarm", "0.02",
+        ("hepmass_realnvp_c8_n65536", [py, bench, "--full", "--config", "hepmass_realnvp", "--steps", "256", "--warmup", "32", "--prewarm", "0.02",
                                        "--cpu-seconds", cpu, "--no-extra-legs", "--no-config-legs"]),
         ("cifar10_glow_c4_n256", [py, os.path.join(tools, "bench_image.py"), "--batch", "256", "--steps", "40", "--warmup", "5",
                                   "--cpu-seconds", cpu]),
@@ -396,9 +403,9 @@ def config_legs(args):
         # configs[4] (MINIBOONE C = 8 sharded one component per GPU) as far as one GPU can show it: ONE rank's share of the 8-GPU
         # run -- one component on every batch, the gather of the full (8, S N) table through the library's RCCL communicator
         # (world size 1: the copy, not the xGMI hop), the recursion -- at the driver's own --steps 20 and in steady state
-        ("miniboone_glow_c8_one_rank_of_8_emulated_steps20", [py, bench, "--force-gather", "--components", "1", "--steps", "20", "--warmup", "5",
+        ("miniboone_glow_c8_one_rank_of_8_emulated_steps20", [py, bench, "--full", "--force-gather", "--components", "1", "--steps", "20", "--warmup", "5",
                                                               "--cpu-seconds", "0", "--no-extra-legs", "--no-config-legs"]),
-        ("miniboone_glow_c8_one_rank_of_8_emulated", [py, bench, "--force-gather", "--components", "1", "--cpu-seconds", "0",
+        ("miniboone_glow_c8_one_rank_of_8_emulated", [py, bench, "--full", "--force-gather", "--components", "1", "--cpu-seconds", "0",
                                                       "--no-extra-legs", "--no-config-legs"]),
     ]
     keep = ("metric", "value", "unit", "dtype", "ms_per_step", "steps", "config", "roofline", "cpu_baseline", "speedup_vs_cpu",
@@ -455,16 +462,21 @@ def main():
     ap.add_argument("--config", default="miniboone_glow", choices=sorted(CONFIGS))
     ap.add_argument("--batch", type=int, default=None)
     ap.add_argument("--components", type=int, default=None)
-    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg (0 = skip)")
+    ap.add_argument("--full", action="store_true",
+                    help="measure more than the headline: the CPU baseline, the extra legs, the other BASELINE configurations, "
+                         "21 repetitions of a short timed region, and the full record")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (G of its batch) as DIR/G.npy, float32")
+    ap.add_argument("--cpu-seconds", type=float, default=12.0, help="budget of the CPU baseline leg of a --full run (0 = skip)")
     ap.add_argument("--math", default="default", choices=["default", "f32", "f16x3", "bf16x6"],
                     help="matrix path: default = chosen by the library per model (probe at create time)")
     ap.add_argument("--force-gather", action="store_true",
                     help="EMULATION aid: run the RCCL all-gather leg with one rank (with --components k: the per-rank load "
                          "of an 8/k-GPU run on one GPU; the cross-GPU hop itself is not exercised)")
     ap.add_argument("--group", type=int, default=GROUP, help=f"batches per launch / all-gather (default {GROUP}, max 32)")
-    ap.add_argument("--full-record", default=FULL_RECORD, help="side file (relative to the repo) for the full record: legs, notes, probes")
-    ap.add_argument("--no-extra-legs", action="store_true", help="skip the f32-exact and group-1 legs of the N=1 line")
-    ap.add_argument("--no-config-legs", action="store_true", help="skip legs.configs (the other BASELINE configurations, run as child processes)")
+    ap.add_argument("--full-record", default=FULL_RECORD, help="side file (relative to the repo) for the full record of a --full run: legs, notes, probes")
+    ap.add_argument("--no-extra-legs", action="store_true", help="--full: skip the f32-exact and group-1 legs of the N=1 line")
+    ap.add_argument("--no-config-legs", action="store_true", help="--full: skip legs.configs (the other BASELINE configurations, run as child processes)")
     ap.add_argument("--graph-exchange", action="store_true", help="sharded runs over real ranks: capture the group (RCCL all-gather included) into a HIP graph")
     ap.add_argument("--pipeline", default="auto", choices=["auto", "library", "torch"],
                     help="sharded runs: 'library' = RCCL called from libgbnf_hip.so, one HIP graph per group; 'torch' = the "
@@ -476,7 +488,7 @@ def main():
         sys.exit(self_launch(args))
 
     cfg_legs = None
-    if (args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_extra_legs and not args.no_config_legs
+    if (args.full and args.gpus == 1 and "WORLD_SIZE" not in os.environ and not args.no_extra_legs and not args.no_config_legs
             and args.config == "miniboone_glow" and args.components is None and args.batch is None and not args.force_gather):
         cfg_legs = config_legs(args)          # children first: this process has not touched the GPU yet
 
@@ -614,7 +626,7 @@ def main():
 
         def run(n_steps, events=None):
             done = gi = 0
-            last = None
+            last = tail = None
             while done < n_steps:
                 k = min(group, n_steps - done)
                 if k not in bound and not fresh:
@@ -628,9 +640,10 @@ def main():
                 res = pipe.submit(list(xs[:k]) if fresh else bound[k], ev)
                 if k == group:
                     last = res               # (G tensor of the slot, slot) of the last FULL group
+                tail = (res[0], k)           # the last group submitted, full or not: its last batch is the run's last step
                 done += k
                 gi += 1
-            return last
+            return last, tail
 
         # clock settle phase (untimed, on top of the W warm-up steps, reported as "prewarm_s"): a cold MI355X runs the
         # first few hundred steps ~10 % slower while its clocks ramp up (a FIXED number of steps: every rank must issue
@@ -639,19 +652,19 @@ def main():
         run(warmup)
         if steps % group:           # the timed loop ends on a partial group: bind and run that launch shape now (untimed), every rank alike
             run(steps % group)
-        # A run shorter than 4 groups is repeated (same K steps, each repetition between barriers + device synchronisations,
-        # MAX over ranks per repetition): `value` comes from the MEDIAN repetition, so the driver's --steps 20 is not a
-        # sample of one ~1 ms launch (>= 20 timed iterations, median and min)
-        reps = repetitions if repetitions else (1 if steps >= 4 * group else 21)
+        # --full: a run shorter than 4 groups is repeated (same K steps, each repetition between barriers + device
+        # synchronisations, MAX over ranks per repetition): `value` comes from the MEDIAN repetition, so the driver's --steps 20
+        # is not a sample of one ~1 ms launch (>= 20 timed iterations, median and min).  A plain run times K steps.
+        reps = repetitions if repetitions else (21 if args.full and steps < 4 * group else 1)
         events = []
         if want_gather_times and gather:
             pipe.gather_events = []
         all_elapsed = []
-        last_full = None
+        last_full = tail = None
         for rep in range(reps):
             barrier()
             t0 = time.perf_counter()
-            last = run(steps, events)
+            last, tail = run(steps, events)
             barrier()
             all_elapsed.append(time.perf_counter() - t0)
             last_full = last if steps >= group else last_full
@@ -667,6 +680,8 @@ def main():
             gather_us = 1e3 * sum(a.elapsed_time(b) for a, b in pipe.gather_events) / len(pipe.gather_events)
         # batch 0 of the last full group of the timed region (the tensor its submit returned)
         G0 = last_full[0][:B].cpu().numpy() if last_full is not None else None
+        # G of the last timed step: the last batch of the last group (batch b of a group is rows [b*B, (b+1)*B) of its G)
+        G_last = tail[0][(tail[1] - 1) * B: tail[1] * B].cpu().numpy() if tail is not None else None
         st = mix.numerics()              # the mode the mixture runs in NOW (a failed on-device check demotes f16x3 -> bf16x6)
         modes = [int(st.math_mode)]
         if world > 1:
@@ -674,7 +689,7 @@ def main():
             ml = [torch.zeros_like(mt) for _ in range(world)]
             dist.all_gather(ml, mt)
             modes = [int(v.item()) for v in ml]
-        return {"elapsed": elapsed, "elapsed_all": all_elapsed, "kern_ms": kern_ms, "info": info, "G0": G0, "gather_us": gather_us,
+        return {"elapsed": elapsed, "elapsed_all": all_elapsed, "kern_ms": kern_ms, "info": info, "G0": G0, "G_last": G_last, "gather_us": gather_us,
                 "modes": modes, "guard": {"checks": int(st.checks), "worst_rel_err": float(st.worst_rel_err),
                                           "demoted": bool(st.demoted), "tolerance": float(st.tolerance)},
                 "kern_ms_min": per_launch[0] if per_launch else None,
@@ -711,6 +726,13 @@ def main():
         seen[rank] = 1 + torch.cuda.current_device()
         dist.all_reduce(seen)
         ranks_seen = [int(v) - 1 for v in seen.cpu()]       # local device index of every rank, -1 = a rank that did not answer
+
+    if rank == 0 and args.dump_outputs and main_run["G_last"] is not None:
+        G_last = main_run["G_last"].astype(np.float32)
+        if G_last.nbytes > 64 << 20:        # the dump stays within 64 MB: a fixed, seeded sample of the rows
+            G_last = G_last[np.sort(np.random.default_rng(0).choice(G_last.size, (64 << 20) // 4, replace=False))]
+        os.makedirs(args.dump_outputs, exist_ok=True)
+        np.save(os.path.join(args.dump_outputs, "G.npy"), G_last)
 
     if rank == 0:
         value = B * args.steps / main_run["elapsed"]
@@ -753,7 +775,7 @@ def main():
                                     "and the two slots' groups overlap: launch_ms / achieved / flows_only_samples_per_s of this run are "
                                     "whole-group, overlapped times -- not the flow kernel alone (that is the N=1 line's roofline)")
                                    if pipeline_used.get("kind") == "library" else None}
-        if world == 1 and not args.no_extra_legs:
+        if args.full and world == 1 and not args.no_extra_legs:
             legs = {}
             n_leg = max(2 * S, min(args.steps, 320))
             try:
@@ -839,7 +861,7 @@ def main():
             if cfg_legs is not None:
                 legs["configs"] = cfg_legs
             out["legs"] = legs
-        if args.cpu_seconds > 0 and world == 1:
+        if args.full and args.cpu_seconds > 0 and world == 1:
             cb, G_cpu, n_cpu = cpu_baseline(specs, rho_np, x_np, args.cpu_seconds)
             out["cpu_baseline"] = cb
             out["speedup_vs_cpu"] = value / cb["value"]
@@ -847,9 +869,10 @@ def main():
                 err = float(np.max(np.abs(main_run["G0"][:n_cpu].astype(np.float64) - G_cpu) / np.maximum(np.abs(G_cpu), 1.0)))
                 out["max_rel_err_vs_cpu"] = err
         elif args.cpu_seconds > 0:
-            out["cpu_baseline"] = None     # reported on the N=1 run only
-        emit_full_record(out, args.full_record)
-        line = compact_line(out, args.full_record)
+            out["cpu_baseline"] = None     # reported on the N=1 --full run only
+        if args.full:
+            emit_full_record(out, args.full_record)
+        line = compact_line(out, args.full_record if args.full else None)
     else:
         line = None
 

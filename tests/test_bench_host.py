@@ -35,7 +35,7 @@ def test_traffic_lookup_matches_only_the_measured_workloads():
 
 def test_driver_invocation_parses_and_defaults_finish_quickly():
     out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--help"], stdout=subprocess.PIPE, text=True, check=True).stdout
-    for flag in ("--gpus", "--steps", "--warmup"):
+    for flag in ("--gpus", "--steps", "--warmup", "--full", "--dump-outputs"):
         assert flag in out
     b = _bench()
     assert b.GROUP <= 32 and set(b.CONFIGS) >= {"miniboone_glow", "hepmass_realnvp"}

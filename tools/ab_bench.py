@@ -40,7 +40,7 @@ def main():
     for r in range(args.rounds):
         for n in names:
             env = dict(os.environ, GBNF_LIB_PATH=lib(n))
-            out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--cpu-seconds", "0", "--steps", str(args.steps),
+            out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--cpu-seconds", "0", "--steps", str(args.steps),
                                   "--warmup", "64", "--prewarm", "0.15", "--group", str(args.group), "--no-extra-legs"] + args.extra.split(),
                                  env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)
             line = [l for l in out.stdout.splitlines() if l.startswith("{")]

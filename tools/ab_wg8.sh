@@ -5,7 +5,7 @@ for rep in 1 2 3; do
   for form in pairs wg8; do
     e=""; [ $form = wg8 ] && e="GBNF_NO_WG_PAIRS=1"
     a=$(env $e python bench.py --cpu-seconds 0 --no-extra-legs --no-config-legs 2>/dev/null | tail -1)
-    b=$(env $e python bench.py --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-extra-legs --no-config-legs 2>/dev/null | tail -1)
+    b=$(env $e python bench.py --full --gpus 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-extra-legs --no-config-legs 2>/dev/null | tail -1)
     c=$(env $e python bench.py --components 4 --steps 2048 --cpu-seconds 0 --no-extra-legs --no-config-legs 2>/dev/null | tail -1)
     python - "$form" "$a" "$b" "$c" <<'PY'
 import json, sys

@@ -3,7 +3,7 @@ for rep in 1 2; do
   for form in pairs wg8; do
     e=""; [ $form = wg8 ] && e="GBNF_NO_WG_PAIRS=1"
     a=$(env $e python bench.py --config hepmass_realnvp --steps 256 --warmup 32 --prewarm 0.02 --cpu-seconds 0 --no-extra-legs --no-config-legs 2>/dev/null | tail -1)
-    b=$(env $e python bench.py --force-gather --components 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-extra-legs --no-config-legs 2>/dev/null | tail -1)
+    b=$(env $e python bench.py --full --force-gather --components 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-extra-legs --no-config-legs 2>/dev/null | tail -1)
     c=$(env $e python tools/bench_train.py --batch 65536 --steps 20 --warmup 5 --cpu-steps 0 --no-torch-legs 2>/dev/null | tail -1)
     python - "$form" "$a" "$b" "$c" <<'PY'
 import json, sys

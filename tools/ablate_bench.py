@@ -28,7 +28,7 @@ def main():
         for lib in libs:
             name = os.path.basename(lib)[len("libgbnf_hip_"):-3]
             env = dict(os.environ, GBNF_LIB_PATH=lib)
-            out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--cpu-seconds", "0", "--steps",
+            out = subprocess.run([sys.executable, os.path.join(REPO, "bench.py"), "--full", "--cpu-seconds", "0", "--steps",
                                   str(args.steps), "--warmup", "40", "--prewarm", "0.1", "--group", str(args.group),
                                   "--math", "f16x3", "--no-extra-legs"],
                                  env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True)

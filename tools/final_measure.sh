@@ -5,14 +5,14 @@ set -x
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 O=gpurun_out/final; mkdir -p $O; : > $O/rc.txt
 run() { name=$1; shift; timeout 420 "$@" > $O/$name.json 2> $O/$name.err; echo "rc $? $name" >> $O/rc.txt; }
-run bench_default python bench.py
-run bench_steps20 python bench.py --gpus 1 --steps 20 --warmup 5 --no-config-legs
-run bench_hepmass python bench.py --config hepmass_realnvp --batch 65536 --steps 256 --warmup 32 --no-extra-legs --cpu-seconds 0
-run bench_c4 python bench.py --components 4 --steps 2048 --no-extra-legs --cpu-seconds 0
-run bench_bf16x6 python bench.py --math bf16x6 --no-extra-legs --cpu-seconds 0
-run bench_emul8_steps20 python bench.py --force-gather --components 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-extra-legs
-run bench_emul8_default python bench.py --force-gather --components 1 --cpu-seconds 0 --no-extra-legs
-run bench_emul8_default_torch python bench.py --force-gather --components 1 --cpu-seconds 0 --no-extra-legs --pipeline torch
+run bench_default python bench.py --full
+run bench_steps20 python bench.py --full --gpus 1 --steps 20 --warmup 5 --no-config-legs
+run bench_hepmass python bench.py --full --config hepmass_realnvp --batch 65536 --steps 256 --warmup 32 --no-extra-legs --cpu-seconds 0
+run bench_c4 python bench.py --full --components 4 --steps 2048 --no-extra-legs --cpu-seconds 0
+run bench_bf16x6 python bench.py --full --math bf16x6 --no-extra-legs --cpu-seconds 0
+run bench_emul8_steps20 python bench.py --full --force-gather --components 1 --steps 20 --warmup 5 --cpu-seconds 0 --no-extra-legs
+run bench_emul8_default python bench.py --full --force-gather --components 1 --cpu-seconds 0 --no-extra-legs
+run bench_emul8_default_torch python bench.py --full --force-gather --components 1 --cpu-seconds 0 --no-extra-legs --pipeline torch
 run image_n256 python tools/bench_image.py --batch 256 --cpu-seconds 5
 run image_n64 python tools/bench_image.py --batch 64 --cpu-seconds 0
 run image_1x28x28_n256 python tools/bench_image.py --batch 256 --input 1 28 28 --cpu-seconds 3
