@@ -27,6 +27,7 @@ misspelt kwarg); image inputs dispatch to ``image_glow.BoostedImageFlow`` (``Boo
 from __future__ import annotations
 
 import math
+import os
 
 import numpy as np
 import torch
@@ -356,6 +357,13 @@ class BoostedFlow(nn.Module):
     def __init__(self, args):
         super().__init__()
         self.args = args
+        # arithmetic of the training path (native.NativeTrainer): args.train_math, else env GBNF_TRAIN_MATH, else the fast
+        # saturating "f16x3"; "bf16x6" is the range-safe trainer, "repair" f16x3 with a same-call bf16x6 re-run of a step that met the
+        # range.  Checked here, before any device work.
+        train_math = getattr(args, "train_math", None) or os.environ.get("GBNF_TRAIN_MATH") or "f16x3"
+        if train_math not in native.NativeTrainer.TRAIN_MATH:
+            raise ValueError(f"train_math must be one of {sorted(native.NativeTrainer.TRAIN_MATH)}, got {train_math!r}")
+        self.train_math = train_math
         self.num_flows = args.num_flows
         self.z_size = args.z_size
         self.density_evaluation = args.density_evaluation
@@ -648,7 +656,8 @@ class BoostedFlow(nn.Module):
         key = tuple(key)
         cached = self._trainers.get(c)
         if cached is None or cached[0] != key:
-            self._trainers[c] = (key, native.NativeTrainer(gspec.device_spec_from_component(flow)))
+            # (a geometry without the kernels of self.train_math raises GbnfError here: the module never downgrades the mode)
+            self._trainers[c] = (key, native.NativeTrainer(gspec.device_spec_from_component(flow), math=self.train_math))
         return self._trainers[c][1]
 
     def _ensure_actnorm(self, x, c):

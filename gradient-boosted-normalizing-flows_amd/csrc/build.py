@@ -22,6 +22,7 @@ FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wno-unused-val
 
 def read_variants():
     out = []
+    safe_lines = []
     with open(os.path.join(HERE, "variants.list")) as f:
         for line in f:
             line = line.split("#")[0].strip()
@@ -32,6 +33,15 @@ def read_variants():
                 kind, ht, ot, acta, actb = (int(v) for v in toks[1:6])
                 for form in (int(ch) for ch in (toks[6] if len(toks) > 6 else "123")):       # 1 = 16-sample tiles / 4 waves, 2 = 32 / 4, 3 = 32 / 8
                     out.append(("coop", kind, ht, ot, form, acta, actb))
+                continue
+            if line.startswith("safe"):    # the bf16x6 forms of an hx3 line's training sweeps (range-safe trainers): safe KIND HT OT ACTA ACTB [DEPTH]
+                vals = [int(v) for v in line.split()[1:]]
+                kind, ht, ot, acta, actb = vals[:5]
+                depth = vals[5] if len(vals) > 5 else 1
+                for nt in (1, 2):
+                    out.append(("hx3t", kind, ht, ot, nt, acta, actb, 1, depth))
+                out.append(("hx3b", kind, ht, ot, acta, actb, depth, 1))             # (a trailing 1: the bf16x6 form)
+                safe_lines.append((line, (kind, ht, ot, acta, actb, depth)))
                 continue
             if line.startswith("hx3"):     # both split precisions: 0 = f16x3, 1 = bf16x6 (its repair pass / safe mode)
                 toks = line.split()[1:]
@@ -54,6 +64,9 @@ def read_variants():
             kind, ht, ksl, ks1, ot, lmid, acta, actb = (int(v) for v in toks)
             for nt in nts:
                 out.append((kind, ht, ksl, ks1, ot, nt, lmid, acta, actb))
+    for line, key in safe_lines:   # the hx3 line it names must exist and build training sweeps (no `eval` line): its blob layout is what is re-packed
+        if ("hx3b",) + key not in out:
+            raise ValueError(f"variants.list: `{line}` names no `hx3` line of that geometry with training sweeps")
     return sorted(set(out), key=str)
 
 
@@ -165,8 +178,8 @@ def main(argv=None):
         objs.append(o)
         extra = []
         if v[0] == "hx3b":
-            vsrc, vargs = os.path.join(HERE, "variant_bwd.hip"), v[1:]
-            extra = list(VGPR_FORM)
+            vsrc, vargs = os.path.join(HERE, "variant_bwd.hip"), v[1:7]
+            extra = list(VGPR_FORM) + (["-DGBNF_V_SAFE=1"] if len(v) > 7 else [])
         elif v[0] == "coop":
             vsrc, vargs = os.path.join(HERE, "variant_coop.hip"), v[1:]
             extra = list(VGPR_FORM)
@@ -176,7 +189,7 @@ def main(argv=None):
             extra = list(VGPR_FORM) + (["-DGBNF_V_TRAIN=1"] if v[0] == "hx3t" else [])
         else:
             vsrc, vargs = os.path.join(HERE, "variant.hip"), v
-        if args.force or not newer(o, [vsrc] + hdr + ([os.path.join(HERE, "gbnf_train_bwd.hip.h")] if v[0] == "hx3b" else [])
+        if args.force or not newer(o, [vsrc] + hdr + ([os.path.join(HERE, "gbnf_train_bwd.hip.h"), os.path.join(HERE, "gbnf_train_bwd_kernel.inc")] if v[0] == "hx3b" else [])
                                    + ([os.path.join(HERE, "gbnf_flow_kernel_coop.hip.h")] if v[0] == "coop" else [])):
             jobs.append([HIPCC] + FLAGS + extra + ["-DGBNF_V_ARGS=" + ",".join(str(a) for a in vargs), "-c", vsrc, "-o", o])
     img_o, img_src = os.path.join(OBJ, "gbnf_image.o"), os.path.join(HERE, "gbnf_image.hip")

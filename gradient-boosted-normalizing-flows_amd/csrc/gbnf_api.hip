@@ -1673,6 +1673,8 @@ int gbnf_boosting_weights(const float* G, int64_t n, float beta, float* w_out, v
 // =====================================================================================================================
 namespace gbnf {
 
+static_assert(CHAIN_TABLE_STEPS == LDS_TABLE_STEPS, "gbnf_internal.h: the trainer refuses at create time what the sweeps refuse at launch");
+
 struct LiveLayer { const float* W; const float* b; int rows, cols; };
 // one weight tile of the blob: NP fragments at word `dst`; kind 0: layer 0 (a = tile t), 1: hidden (a = out tile u, b = chunk c),
 // 2: output layer (a = chunk c, b = out tile o); rows / cols: the layer's live extent (beyond it the tile is zero).
@@ -1707,6 +1709,9 @@ struct LiveBlob {
   const char* name_bwd = nullptr;
   int bwd_waves = 4;                    // waves per workgroup of the backward launch (bwd_hx3_waves)
   int ht = 0;                           // hidden tiles of the kernel variant
+  int np = 2;                           // pieces per weight tile: 2 = f16x3, 3 = bf16x6 (a range-safe trainer's blob)
+  unsigned* sat = nullptr;              // (repairing trainer) where this blob's launches count range events; null: the device's training counter
+  const unsigned* gate = nullptr;       // (repairing trainer) device word: this blob's launches return at once while it is 0
   int depth = 1;                        // coupling_network_depth: hidden -> hidden layers per net
   bool tilesB_packed = false;           // the last re-pack included the transposed tiles
 };
@@ -1715,6 +1720,9 @@ struct LiveBlob {
 // (sat: the device's range counter -- a weight beyond the fp16 range, +-65504 after the tanh pre-scale, cannot be split: hi rounds to inf, the
 //  residual to -inf, a ReLU of the NaN they produce is 0.  No trained model has such weights; a diverged one is COUNTED here like every other
 //  operand that leaves the range (gbnf_saturation_count), not passed over in silence)
+// NP = 3: the bf16x6 twin -- p_k = bf16_rne(x - p_0 - .. - p_{k-1}), as put_tile() packs bf16x6 evaluation blobs.  bf16 has the range of
+// f32: a weight beyond +-65504 is legal there and nothing is counted.
+template <int NP>
 __device__ __forceinline__ void live_tile(const LiveTile T, const LiveLayer* __restrict__ layers, uint32_t* __restrict__ blob, int lane,
                                           unsigned* __restrict__ sat) {
   const LiveLayer L = layers[T.lid];
@@ -1722,7 +1730,9 @@ __device__ __forceinline__ void live_tile(const LiveTile T, const LiveLayer* __r
   bool big = false;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    uint32_t w[2] = {0u, 0u};
+    uint32_t w[NP];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) w[k] = 0u;
 #pragma unroll
     for (int e = 0; e < 2; ++e) {
       const int j = 2 * q + e;
@@ -1734,22 +1744,32 @@ __device__ __forceinline__ void live_tile(const LiveTile T, const LiveLayer* __r
       else if (T.kind == 3 || T.kind == 4) { row = kslot_b; col = 16 * T.a + i; }      // contraction over W's rows
       else { row = kslot_a; col = 16 * T.b + i; }
       float r = (row < T.rows && col < T.cols) ? T.scale * L.W[(size_t)row * L.cols + col] : 0.0f;
-      big = big || !(__builtin_fabsf(r) <= 65504.0f);
+      if constexpr (NP == 2) {
+        big = big || !(__builtin_fabsf(r) <= 65504.0f);
 #pragma unroll
-      for (int k = 0; k < 2; ++k) {       // hi = f16(r), mid = f16(r - hi): both round to nearest, like the host packer
-        const _Float16 h = static_cast<_Float16>(r);
-        w[k] |= (uint32_t)__builtin_bit_cast(unsigned short, h) << (16 * e);
-        r -= static_cast<float>(h);
+        for (int k = 0; k < 2; ++k) {       // hi = f16(r), mid = f16(r - hi): both round to nearest, like the host packer
+          const _Float16 h = static_cast<_Float16>(r);
+          w[k] |= (uint32_t)__builtin_bit_cast(unsigned short, h) << (16 * e);
+          r -= static_cast<float>(h);
+        }
+      } else {
+#pragma unroll
+        for (int k = 0; k < NP; ++k) {      // three bf16 pieces, each rounded to nearest even
+          const __bf16 h = static_cast<__bf16>(r);
+          w[k] |= (uint32_t)__builtin_bit_cast(unsigned short, h) << (16 * e);
+          r -= static_cast<float>(h);
+        }
       }
     }
-    blob[T.dst + (size_t)lane * 4 + q] = w[0];
-    blob[T.dst + 256 + (size_t)lane * 4 + q] = w[1];
+#pragma unroll
+    for (int k = 0; k < NP; ++k) blob[T.dst + (size_t)k * 256 + (size_t)lane * 4 + q] = w[k];
   }
-  if (sat != nullptr && __any(big) && lane == 0) atomicAdd(sat, 1u);
+  if (NP == 2 && sat != nullptr && __any(big) && lane == 0) atomicAdd(sat, 1u);
 }
+template <int NP>
 __global__ void __launch_bounds__(64) live_tiles_kernel(const LiveTile* __restrict__ tiles, const LiveLayer* __restrict__ layers,
                                                         uint32_t* __restrict__ blob, unsigned* __restrict__ sat) {
-  live_tile(tiles[blockIdx.x], layers, blob, (int)threadIdx.x, sat);
+  live_tile<NP>(tiles[blockIdx.x], layers, blob, (int)threadIdx.x, sat);
 }
 
 // biases (folded row sums in double, like the host packer), live table entries, per-step log-det constants
@@ -1801,17 +1821,19 @@ __device__ __forceinline__ void live_small(int block, const LiveBias* __restrict
 // ONE launch re-derives everything a training step's kernels read from the live parameters: the forward blob's tiles, the
 // transposed tiles of the backward sweep (when one will follow: the trace contract), the biases / tables / log-det constants.
 // (Three launches of ~6 us each were 8 % of the N = 4096 training step.)  256 threads: four tiles per block, then the small work.
+template <int NP>
 __global__ void __launch_bounds__(256) live_pack_kernel(const LiveTile* __restrict__ tiles, int n_tiles, const LiveTile* __restrict__ tilesB,
                                                         int n_tilesB, uint32_t* __restrict__ blobB, const LiveBias* __restrict__ bias,
                                                         int n_bias, const LiveEntry* __restrict__ ent, int n_ent,
                                                         const LiveNorm* __restrict__ norms, int K, int d, int glow,
                                                         const LiveLayer* __restrict__ layers, uint32_t* __restrict__ blob,
-                                                        unsigned* __restrict__ sat) {
+                                                        unsigned* __restrict__ sat, const unsigned* __restrict__ gate) {
+  if (gate != nullptr && *gate == 0u) return;        // (the re-run of a call that did not meet the range)
   const int tile_blocks = (n_tiles + n_tilesB + 3) / 4;
   if ((int)blockIdx.x < tile_blocks) {
     const int t = (int)blockIdx.x * 4 + (int)(threadIdx.x >> 6), lane = (int)(threadIdx.x & 63);
-    if (t < n_tiles) live_tile(tiles[t], layers, blob, lane, sat);
-    else if (t < n_tiles + n_tilesB) live_tile(tilesB[t - n_tiles], layers, blobB, lane, nullptr);      // (the same weights, transposed)
+    if (t < n_tiles) live_tile<NP>(tiles[t], layers, blob, lane, sat);
+    else if (t < n_tiles + n_tilesB) live_tile<NP>(tilesB[t - n_tiles], layers, blobB, lane, nullptr);      // (the same weights, transposed)
     return;
   }
   live_small((int)blockIdx.x - tile_blocks, bias, n_bias, ent, n_ent, norms, K, d, glow, layers, blob);
@@ -1822,7 +1844,8 @@ __global__ void __launch_bounds__(256) live_pack_kernel(const LiveTile* __restri
 // of the step range that starts with it.
 __global__ void __launch_bounds__(256) live_norm_step_kernel(const LiveEntry* __restrict__ ent, int n_ent, const LiveNorm* __restrict__ norms,
                                                              int step, int d, const float* __restrict__ bmean, const float* __restrict__ bvar,
-                                                             uint32_t* __restrict__ blob) {
+                                                             uint32_t* __restrict__ blob, const unsigned* __restrict__ gate) {
+  if (gate != nullptr && *gate == 0u) return;
   const LiveNorm N = norms[step];
   if (!N.has_norm) return;
   auto put = [&](uint32_t off, float v) { blob[off] = __builtin_bit_cast(uint32_t, v); };
@@ -1839,6 +1862,13 @@ __global__ void __launch_bounds__(256) live_norm_step_kernel(const LiveEntry* __
     put(N.ld_dst, acc);
   }
 }
+
+void live_blob_set_repair(LiveBlob* lb, unsigned* sat, const unsigned* gate) {
+  if (!lb) return;
+  lb->sat = sat;
+  lb->gate = gate;
+}
+static unsigned* live_sat(const LiveBlob* lb) { return lb->sat != nullptr ? lb->sat : training_saturation_counter(); }
 
 void live_blob_destroy(LiveBlob* lb) {
   if (!lb) return;
@@ -1868,7 +1898,8 @@ static hipError_t upload_vec(const std::vector<T>& v, T** dev) {
 
 // The TRAIN kernel variant of a flow: the exact padded width if one is compiled, else the cheapest zero-padded superset (the
 // per-step-activation variants are generic supersets).  GBNF_OK and *vc, or UNSUPPORTED.
-static int live_choose(const gbnf_flow_desc* desc, DescInfo& info, VariantChoice* vc) {
+// ksl_key: -3 = the f16x3 sweeps, -6 = the bf16x6 sweeps of a range-safe trainer (a `safe` line of variants.list)
+static int live_choose(const gbnf_flow_desc* desc, DescInfo& info, VariantChoice* vc, int ksl_key = -3) {
   const int h = info.ref.hidden, depth = info.ref.depth;
   if (info.ref.residual ? (depth != 2 && depth != 4) : depth > 2)
     return fail(GBNF_ERR_UNSUPPORTED, "live blob: TanhNet / ReLUNet of coupling_network_depth 0, 1 or 2 and ResidualNets of one or two blocks only");
@@ -1876,7 +1907,7 @@ static int live_choose(const gbnf_flow_desc* desc, DescInfo& info, VariantChoice
   {   // an activation pair nobody compiled a kernel for runs on the per-step variants (as gbnf_flow_create_ex does)
     bool compiled = false;
     for (const Variant& v : variants())
-      compiled = compiled || (v.key.ks1 == 1 && v.key.kind == desc->kind && v.key.act_a == info.act_a && v.key.act_b == info.act_b);
+      compiled = compiled || (v.key.ks1 == 1 && v.key.ksl == ksl_key && v.key.kind == desc->kind && v.key.act_a == info.act_a && v.key.act_b == info.act_b);
     // (a ResidualNet never takes the per-step-activation variants: they have no skip connection -- RES is a compile-time
     //  property of the act-2 kernels.  Glow + ResidualNet has no TRAIN variant, so such a descriptor keeps the per-step trainer:
     //  ADVICE r5)
@@ -1884,13 +1915,14 @@ static int live_choose(const gbnf_flow_desc* desc, DescInfo& info, VariantChoice
       return fail(GBNF_ERR_UNSUPPORTED, "live blob: no TRAIN kernel variant with a skip connection for kind=%d (ResidualNets train on the chained kernels for RealNVP only)", desc->kind);
     if (!compiled) info.act_a = info.act_b = GBNF_ACT_PER_STEP;
   }
-  if (!choose_hx3(desc->kind, h, info.ot, depth, info.act_a, info.act_b, -3, vc, /*train=*/1)) {
+  const char* what = ksl_key == -3 ? "TRAIN" : "bf16x6 TRAIN";
+  if (!choose_hx3(desc->kind, h, info.ot, depth, info.act_a, info.act_b, ksl_key, vc, /*train=*/1)) {
     if (info.act_a != GBNF_ACT_PER_STEP && !info.ref.residual) {
       info.act_a = info.act_b = GBNF_ACT_PER_STEP;
-      if (!choose_hx3(desc->kind, h, info.ot, depth, info.act_a, info.act_b, -3, vc, 1))
-        return fail(GBNF_ERR_UNSUPPORTED, "live blob: no TRAIN kernel variant for kind=%d hidden=%d out_tiles=%d", desc->kind, h, info.ot);
+      if (!choose_hx3(desc->kind, h, info.ot, depth, info.act_a, info.act_b, ksl_key, vc, 1))
+        return fail(GBNF_ERR_UNSUPPORTED, "live blob: no %s kernel variant for kind=%d hidden=%d out_tiles=%d depth=%d", what, desc->kind, h, info.ot, depth);
     } else {
-      return fail(GBNF_ERR_UNSUPPORTED, "live blob: no TRAIN kernel variant for kind=%d hidden=%d out_tiles=%d", desc->kind, h, info.ot);
+      return fail(GBNF_ERR_UNSUPPORTED, "live blob: no %s kernel variant for kind=%d hidden=%d out_tiles=%d depth=%d", what, desc->kind, h, info.ot, depth);
     }
   }
   return GBNF_OK;
@@ -1898,15 +1930,15 @@ static int live_choose(const gbnf_flow_desc* desc, DescInfo& info, VariantChoice
 
 // Hidden rows (16 x hidden tiles) of the TRAIN variant a trainer of this flow would run, 0 if none: the trainer sizes its
 // operand workspace by it (round 5: a width without a variant of its own trains on the next wider one, its extra rows are zeros)
-int live_blob_train_rows(const gbnf_flow_desc* desc) {
+int live_blob_train_rows(const gbnf_flow_desc* desc, int prec) {
   DescInfo info;
   if (validate_desc(desc, &info)) return 0;
   VariantChoice vc;
-  if (live_choose(desc, info, &vc)) return 0;
+  if (live_choose(desc, info, &vc, prec == 0 ? -3 : -6)) return 0;
   return 16 * vc.ht;
 }
 
-int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offsets, LiveBlob** out) {
+int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offsets, LiveBlob** out, int prec) {
   *out = nullptr;
   DescInfo info;
   int rc = validate_desc(desc, &info);
@@ -1916,7 +1948,7 @@ int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offset
   const bool additive = glow && desc->coupling == GBNF_COUPLING_ADDITIVE;
   const int h = info.ref.hidden, depth = info.ref.depth;
   VariantChoice vc;
-  rc = live_choose(desc, info, &vc);
+  rc = live_choose(desc, info, &vc, prec == 0 ? -3 : -6);
   if (rc) return rc;
   // ---- the value-independent words: pack a copy of the descriptor whose parameter arrays are host zeros
   static const std::vector<float> zeros((size_t)512 * 512 + 64, 0.0f);
@@ -1949,7 +1981,7 @@ int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offset
   pack_component(&dummy, info, vc, &pb);
 
   // ---- where every value-dependent word comes from (the loops of pack_component / pack_net_hx3, recording instead of computing)
-  const int HT = vc.ht, OT = vc.ot, NP = 2, nnets = glow ? 1 : 2;
+  const int HT = vc.ht, OT = vc.ot, NP = vc.np, nnets = glow ? 1 : 2;
   const Hx3Layout L(HT, OT, NP, depth);
   const size_t NW = (size_t)L.NET_WORDS, step_words = SMALL_WORDS + nnets * NW, TW = (size_t)NP * 256;
   const int d1 = d / 2, d2 = d - d1;
@@ -1958,7 +1990,7 @@ int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offset
   std::vector<LiveBias> biases;
   std::vector<LiveEntry> entries;
   std::vector<LiveNorm> norms(K);
-  const BwdLayout LB(HT, OT, depth);
+  const BwdLayout LB(HT, OT, depth, NP);
   const size_t NWB = (size_t)LB.NET_WORDS, step_words_b = nnets * NWB;
   std::vector<LiveTile> tilesB;
   std::vector<int32_t> bwd_tab((size_t)K * 2 * 4 * NENT, -1);
@@ -2091,6 +2123,7 @@ int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offset
   lb->kind = desc->kind; lb->d = d; lb->K = K; lb->additive = additive ? 1 : 0; lb->nnets = nnets;
   lb->blob_words = pb.words.size();
   lb->ht = vc.ht;
+  lb->np = NP;
   lb->depth = depth;
   lb->n_tiles = (int)tiles.size(); lb->n_bias = (int)biases.size(); lb->n_entries = (int)entries.size();
   for (int nt = 1; nt <= 2; ++nt) { lb->launch_nt[nt] = vc.launch_nt[nt]; lb->name_nt[nt] = vc.name_nt[nt]; }
@@ -2102,7 +2135,7 @@ int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offset
   if (e == hipSuccess) e = upload_vec(norms, &lb->norms_dev);
   // ---- the backward sweep, where a variant of bwd_kernel_hx3 exists for this geometry (else the caller keeps its own)
   if (e == hipSuccess && norm_grad_offsets != nullptr) {
-    const Variant* vb = find_variant(VariantKey{desc->kind, vc.ht, -3, 2, vc.ot, 1, depth, info.act_a, info.act_b});
+    const Variant* vb = find_variant(VariantKey{desc->kind, vc.ht, prec == 0 ? -3 : -6, 2, vc.ot, 1, depth, info.act_a, info.act_b});
     // (the backward kernel keeps every step's tables in LDS: flows of more than LDS_TABLE_STEPS steps, or whose tables + stage
     //  slots + per-wave state do not fit a CU, keep the round-1 backward kernels -- the forward sweep has a global-table form)
     if (vb != nullptr && (K > LDS_TABLE_STEPS || bwd_hx3_lds_bytes(K, bwd_hx3_waves(K, LB.STAGE_FRAGS, d), LB.STAGE_FRAGS, d) > 160 * 1024))
@@ -2165,13 +2198,19 @@ int live_blob_backward(LiveBlob* lb, int64_t n, const float* trace, float* acts,
   hipStream_t s = (hipStream_t)stream;
   // the transposed tiles were packed by the forward call that wrote the trace (the parameters are unchanged since: the trace
   // contract of include/gbnf.h); a trainer that has not run one yet packs them here
-  if (!lb->tilesB_packed)
-    hipLaunchKernelGGL(live_tiles_kernel, dim3((unsigned)lb->n_tilesB), dim3(64), 0, s, (const LiveTile*)lb->tilesB_dev,
-                       (const LiveLayer*)lb->layers_dev, lb->blobB_dev, (unsigned*)nullptr);
+  if (!lb->tilesB_packed) {
+    if (lb->np == 2)
+      hipLaunchKernelGGL(live_tiles_kernel<2>, dim3((unsigned)lb->n_tilesB), dim3(64), 0, s, (const LiveTile*)lb->tilesB_dev,
+                         (const LiveLayer*)lb->layers_dev, lb->blobB_dev, (unsigned*)nullptr);
+    else
+      hipLaunchKernelGGL(live_tiles_kernel<3>, dim3((unsigned)lb->n_tilesB), dim3(64), 0, s, (const LiveTile*)lb->tilesB_dev,
+                         (const LiveLayer*)lb->layers_dev, lb->blobB_dev, (unsigned*)nullptr);
+  }
   FlowLaunch p{};
   p.blobs = lb->table_dev; p.blobs_bwd = lb->tableB_dev;
   p.n = n; p.d = lb->d; p.n_steps = lb->K; p.n_comp = 1; p.n_batches = 1; p.additive = lb->additive;
-  p.sat = reinterpret_cast<unsigned long long*>(training_saturation_counter());
+  p.sat = reinterpret_cast<unsigned long long*>(live_sat(lb));
+  if (lb->gate != nullptr) { p.repair = 2; p.guard = lb->gate; }      // (bwd_kernel_hx3_safe returns at once while *gate == 0)
   p.acts_out = acts; p.np = np; p.tr_ip = ip; p.tr_hp = hp; p.tr_op = op; p.net_rows = ip + 2 * (lb->depth + 1) * hp + 2 * op;
   p.bwd_tab = lb->bwd_tab_dev; p.bwd_goff = lb->bwd_goff_dev; p.trace_in = trace;
   p.g_z = g_z; p.g_ldj = g_ldj; p.g_x = g_x; p.grads = grads; p.gmax = gmax;
@@ -2202,10 +2241,16 @@ static void live_blob_repack(LiveBlob* lb, hipStream_t s, bool with_backward = f
   const int n_tilesB = (with_backward && lb->launch_bwd != nullptr) ? lb->n_tilesB : 0;
   const int small_blocks = (lb->n_bias + 15) / 16 + (lb->n_entries + lb->K + 255) / 256;
   const int tile_blocks = (lb->n_tiles + n_tilesB + 3) / 4;
-  hipLaunchKernelGGL(live_pack_kernel, dim3((unsigned)(tile_blocks + small_blocks)), dim3(256), 0, s, (const LiveTile*)lb->tiles_dev,
-                     lb->n_tiles, (const LiveTile*)lb->tilesB_dev, n_tilesB, lb->blobB_dev, (const LiveBias*)lb->bias_dev, lb->n_bias,
-                     (const LiveEntry*)lb->entries_dev, lb->n_entries, (const LiveNorm*)lb->norms_dev, lb->K, lb->d,
-                     lb->kind == GBNF_KIND_GLOW ? 1 : 0, (const LiveLayer*)lb->layers_dev, lb->blob_dev, training_saturation_counter());
+  if (lb->np == 2)
+    hipLaunchKernelGGL(live_pack_kernel<2>, dim3((unsigned)(tile_blocks + small_blocks)), dim3(256), 0, s, (const LiveTile*)lb->tiles_dev,
+                       lb->n_tiles, (const LiveTile*)lb->tilesB_dev, n_tilesB, lb->blobB_dev, (const LiveBias*)lb->bias_dev, lb->n_bias,
+                       (const LiveEntry*)lb->entries_dev, lb->n_entries, (const LiveNorm*)lb->norms_dev, lb->K, lb->d,
+                       lb->kind == GBNF_KIND_GLOW ? 1 : 0, (const LiveLayer*)lb->layers_dev, lb->blob_dev, live_sat(lb), (const unsigned*)nullptr);
+  else
+    hipLaunchKernelGGL(live_pack_kernel<3>, dim3((unsigned)(tile_blocks + small_blocks)), dim3(256), 0, s, (const LiveTile*)lb->tiles_dev,
+                       lb->n_tiles, (const LiveTile*)lb->tilesB_dev, n_tilesB, lb->blobB_dev, (const LiveBias*)lb->bias_dev, lb->n_bias,
+                       (const LiveEntry*)lb->entries_dev, lb->n_entries, (const LiveNorm*)lb->norms_dev, lb->K, lb->d,
+                       lb->kind == GBNF_KIND_GLOW ? 1 : 0, (const LiveLayer*)lb->layers_dev, lb->blob_dev, (unsigned*)nullptr, lb->gate);
   lb->tilesB_packed = n_tilesB > 0;
 }
 
@@ -2227,7 +2272,7 @@ int live_blob_forward(LiveBlob* lb, const float* x, int64_t n, float* z, float* 
   if (range != nullptr && range->bmean != nullptr)
     hipLaunchKernelGGL(live_norm_step_kernel, dim3((unsigned)((lb->n_entries + 1 + 255) / 256)), dim3(256), 0, s,
                        (const LiveEntry*)lb->entries_dev, lb->n_entries, (const LiveNorm*)lb->norms_dev, range->k_begin, lb->d,
-                       range->bmean, range->bvar, lb->blob_dev);
+                       range->bmean, range->bvar, lb->blob_dev, lb->gate);
   // 32-sample waves once that still gives every SIMD of the chip a wave, else 16-sample ones (as pick_nt does)
   int nt = pick_nt(n, 1);
   if (lb->launch_nt[nt] == nullptr) nt = 1;
@@ -2236,7 +2281,10 @@ int live_blob_forward(LiveBlob* lb, const float* x, int64_t n, float* z, float* 
   p.n_batches = 1; p.xs[0] = x;
   p.n = n; p.out_stride = n; p.d = lb->d; p.n_steps = lb->K; p.c_begin = 0; p.n_comp = 1;
   p.n_tiles = (int32_t)((n + 16 * nt - 1) / (16 * nt)); p.additive = lb->additive;
-  p.sat = reinterpret_cast<unsigned long long*>(training_saturation_counter());      // (TRAIN instantiations touch the counter word only, never the marks)
+  p.sat = reinterpret_cast<unsigned long long*>(live_sat(lb));      // (TRAIN instantiations touch the counter word only, never the marks)
+  // the re-run of a repairing trainer: a conditional full launch on the trainer's decision word (FlowLaunch::repair = 2: returns at
+  // once while it is 0, else walks the whole work list with the capped grid of a repair launch)
+  if (lb->gate != nullptr) { p.repair = 2; p.guard = lb->gate; }
   p.seq = next_serial();
   p.trace_out = trace; p.acts_out = acts; p.np = np; p.tr_ip = ip; p.tr_hp = hp; p.tr_op = op; p.net_rows = ip + 2 * (lb->depth + 1) * hp + 2 * op;
   if (range != nullptr) {

@@ -348,7 +348,7 @@ flow_kernel_hx3(const FlowLaunch p) {
   // between the two register sets of B operands; behind layer 2 (the first block's second Linear) the skip sum t = a2 + t0 replaces
   // the raw layer-0 tiles AND is what the second block starts from (relu(t)); the last layer's output + t goes to the final layer.
   // (TRAIN at DEPTH = 4: relu(a0), relu(a1), relu(t1), relu(a3) and t2 go to the operand rows of "hidden layers" 0 .. 4)
-  static_assert(!TRAIN || PREC == 0, "the training forward runs on f16x3");
+  // (TRAIN at PREC = 1: the range-safe trainer's forward sweep -- the same trace and operand rows, nothing clamped, nothing counted)
   constexpr int WAVES = WV;
   constexpr int NP = hx3_pieces(PREC);
   constexpr int NPROD = Products<NP>::N;

@@ -21,6 +21,9 @@ unsigned* training_saturation_counter();
 // Kernel-variant key only (not a descriptor value): the activation differs between the steps / nets of a component
 // (`--coupling_network random` in the reference); the kernel reads it per step and net from the step header.
 constexpr int GBNF_ACT_PER_STEP = 3;
+// Steps whose tables the chained training sweeps keep in LDS: LDS_TABLE_STEPS of gbnf_flow_kernel.hip.h (gbnf_api.hip asserts the two
+// are equal), for the translation units that do not see the kernels
+constexpr int CHAIN_TABLE_STEPS = 24;
 
 // ---- the training path's forward sweep on the evaluation kernels (gbnf_api.hip; used by gbnf_train.hip) -------------
 // A "live blob": the packed hx3 (f16x3) parameter blob of ONE component whose parameters live in device tensors that an
@@ -33,9 +36,11 @@ struct LiveBlob;
 // (and *out = nullptr) when no TRAIN kernel variant covers the geometry: the caller keeps its own forward kernel.
 // norm_grad_offsets: [K][2] float offsets of every step's two normalisation-parameter gradients in the caller's flat gradient
 // buffer (null: no backward sweep wanted)
-int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offsets, LiveBlob** out);
+// prec: 0 = f16x3 (the sweeps saturate at the fp16 range and count it), 1 = bf16x6 (f32 range: the blob of a range-safe trainer;
+// only geometries with a `safe` line in variants.list have these sweeps)
+int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offsets, LiveBlob** out, int prec = 0);
 // Hidden rows (16 x hidden tiles) of the TRAIN variant a trainer of this flow would run, 0 if none
-int live_blob_train_rows(const gbnf_flow_desc* desc);
+int live_blob_train_rows(const gbnf_flow_desc* desc, int prec = 0);
 bool live_blob_has_backward(const LiveBlob* lb);
 int live_blob_hidden_rows(const LiveBlob* lb);      // 16 x the hidden tiles of the kernel variant behind it
 // The backward kernel leaves the ActNorm / BatchNorm parameter gradients as per-workgroup partial sums; adding them up (in a
@@ -65,6 +70,10 @@ int live_blob_backward(LiveBlob* lb, int64_t n, const float* trace, float* acts,
                        const float* g_z, const float* g_ldj, float* g_x, float* grads, const unsigned* gmax, void* stream,
                        LiveReduce* reduce_out = nullptr, const LiveRange* range = nullptr);
 void live_blob_destroy(LiveBlob* lb);
+// The two halves of a repairing trainer (gbnf_trainer_create_mode, GBNF_MATH_DEFAULT).  sat: the f16x3 blob's launches count the waves
+// that met the fp16 range in this word (64-bit, trainer-owned) instead of the device's training counter.  gate: the bf16x6 blob's
+// launches (re-pack, both sweeps) return at once while this device word is 0 -- the re-run of a call that did not meet the range.
+void live_blob_set_repair(LiveBlob* lb, unsigned* sat, const unsigned* gate);
 // trace: [K][d][np] normalised states (slot layout); acts: the operand workspace (FlowLaunch::acts_out); np: padded rows
 int live_blob_forward(LiveBlob* lb, const float* x, int64_t n, float* z, float* ldj, float* trace, float* acts, int64_t np,
                       int ip, int hp, int op, void* stream, const LiveRange* range = nullptr);

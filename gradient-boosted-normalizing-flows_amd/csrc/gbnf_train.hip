@@ -37,6 +37,7 @@
 #include <cstdint>
 #include <cstdlib>
 #include <cstring>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -56,6 +57,7 @@ constexpr int TR_MAX_LAYERS = 6;    // Linear layers per coupling net (depth <= 
 constexpr int TR_MAX_IN = 32;       // coupling-net input / coupled-half width
 constexpr int TR_MAX_HIDDEN = 512;  // hidden width (32 output tiles = 16 tile pairs per layer)
 constexpr int TR_LDS_BYTES = 160 * 1024;
+constexpr int TR_CHAIN_MAX_STEPS = CHAIN_TABLE_STEPS;  // steps the chained sweeps keep tables for (gbnf_internal.h: = LDS_TABLE_STEPS of the kernels)
 constexpr int TR_WS_SLACK_ROWS = 320;   // workspace rows behind the last operand region: a block of wgrad_kernel reads up to 256 rows
 #ifndef GBNF_TR_WAVES
 #define GBNF_TR_WAVES 8
@@ -1301,9 +1303,174 @@ static void wg_shape(int M, int N, WgProblem& P, int cap = 256) {
     if (e.bm == P.bm && e.bn == P.bn) { P.wm = e.wm; P.wn = e.wn; }
 }
 
+// ---- the range-safe weight gradients (trainers of GBNF_MATH_BF16X6) -----------------------------------------------------------
+// The same contraction dW = D . A^T over the samples, from the same operand workspace, on the bf16 pipe: an operand value is three
+// bf16 pieces p_k = bf16_rne(x - p_0 - .. - p_{k-1}) (the range of f32, >= 24 significand bits) and a product six
+// v_mfma_f32_16x16x32_bf16 on three running sums, one per magnitude class, added once at the end (Products<3> of
+// gbnf_flow_kernel_hx3.hip.h).  Nothing is clamped.  wgrad_kernel's LDS staging holds two pieces per operand row at 128 KB; with three
+// the block would have to shrink anyway, so this form takes the smallest one and no staging at all (NOT measured against other
+// block shapes or a staged form: it is the simplest form that is right, and the cost of this mode has no bar): a 64 x 64 block of dW per
+// workgroup of 4 waves (2 x 2, every wave 2 x 2 tiles), every wave reads its own rows of the workspace -- a lane's 8 samples of a row
+// are 32 contiguous bytes of the tiled region [16-sample tile][row][16] -- and splits them in registers.  The four waves read each
+// row twice (L1 / L2 hits).  The k numbering of the 32 samples of a step is the same for D and A, which is all the contraction needs.
+constexpr int WGS_THREADS = 256;
+constexpr int WGS_BLOCK = 64;
+using bf16x8 = __attribute__((ext_vector_type(8))) __bf16;
+
+__device__ __forceinline__ void wgs_split8(f32x4 lo, f32x4 hi4, u32x4 (&p)[3]) {
+  typedef __bf16 bf2 __attribute__((ext_vector_type(2)));
+  typedef float f2 __attribute__((ext_vector_type(2)));
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f32x4& v = q < 2 ? lo : hi4;
+    const int e = 2 * (q & 1);
+    const float x0 = v[e], x1 = v[e + 1];
+    const unsigned w0 = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{x0, x1}, bf2));
+    const float r0 = x0 - __builtin_bit_cast(float, w0 << 16), r1 = x1 - __builtin_bit_cast(float, w0 & 0xffff0000u);
+    const unsigned w1 = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{r0, r1}, bf2));
+    const float s0 = r0 - __builtin_bit_cast(float, w1 << 16), s1 = r1 - __builtin_bit_cast(float, w1 & 0xffff0000u);
+    p[0][q] = w0;
+    p[1][q] = w1;
+    p[2][q] = __builtin_bit_cast(unsigned, __builtin_convertvector(f2{s0, s1}, bf2));
+  }
+}
+__device__ __forceinline__ f32x4 wgs_mfma(u32x4 a, u32x4 b, f32x4 c) {
+  return __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0);
+}
+
+// grid: x = the 64 x 64 blocks of every problem (WgProblem::blk_begin, bm = bn = 64), then 2 K blocks that add up the backward
+// kernel's ActNorm / BatchNorm partials (LiveReduce, as in wgrad_kernel); y = sample chunks of `chunk` samples (a multiple of 32)
+__global__ void __launch_bounds__(WGS_THREADS) wgrad_safe_kernel(const WgProblem* __restrict__ probs, int n_probs,
+                                                                 const float* __restrict__ ws, float* __restrict__ grads, int64_t np,
+                                                                 int chunk, const unsigned* __restrict__ gmax, int n_blocks,
+                                                                 const LiveReduce red, const unsigned* __restrict__ gate) {
+  __shared__ float rsum[4][64];
+  if (gate != nullptr && *gate == 0u) return;        // (the bf16x6 re-run of a repairing trainer's call that did not meet the range)
+  const int bx = blockIdx.x, by = blockIdx.y;
+  if (bx >= n_blocks) {
+    if (by != 0 || red.partials == nullptr || bx - n_blocks >= 2 * red.K) return;
+    const int kw = bx - n_blocks, j = threadIdx.x & 63, part = threadIdx.x >> 6;      // 4 parts
+    if ((red.skip_steps >> (kw >> 1)) & 1u) return;
+    const float* src = red.partials + kw * 64 + j;
+    const int64_t stride = (int64_t)red.K * 128;
+    float a[8];
+#pragma unroll
+    for (int q = 0; q < 8; ++q) a[q] = 0.0f;
+    int b = part;
+    for (; b + 4 * 7 < red.n_wg; b += 4 * 8) {
+#pragma unroll
+      for (int q = 0; q < 8; ++q) a[q] += src[(int64_t)(b + 4 * q) * stride];
+    }
+    for (; b < red.n_wg; b += 4) a[0] += src[(int64_t)b * stride];
+    rsum[part][j] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
+    __syncthreads();
+    if (part == 0 && j < red.d) grads[red.goff[kw] + j] += (rsum[0][j] + rsum[1][j]) + (rsum[2][j] + rsum[3][j]);
+    return;
+  }
+  float alpha = 1.0f, inv_alpha = 1.0f;          // the gradient-side operands were emitted on the scaled gradient
+  if (gmax != nullptr) tr_grad_scale(__builtin_amdgcn_readfirstlane(*gmax), alpha, inv_alpha);
+  int pi = 0;
+  while (pi + 1 < n_probs && bx >= probs[pi + 1].blk_begin) ++pi;
+  const WgProblem P = probs[pi];
+  const int blk = bx - P.blk_begin;
+  const int m0 = (blk / P.nb) * WGS_BLOCK, n0 = (blk % P.nb) * WGS_BLOCK;
+  const int64_t s_begin = (int64_t)by * chunk;
+  const int64_t s_end = (s_begin + chunk < np) ? s_begin + chunk : np;
+  const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
+  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
+  const int wmi = wave >> 1, wni = wave & 1;
+  typedef const f32x4 __attribute__((address_space(1)))* gv4;
+  // this lane's rows (clamped into the operand's own sub-region: a row past it only feeds outputs that are never stored) and its
+  // 8 samples of a 32-sample step: tile g / 2, samples 8 (g & 1) .. + 7
+  unsigned doff[2], aoff[2];
+#pragma unroll
+  for (int x = 0; x < 2; ++x) {
+    const int rd = m0 + 32 * wmi + 16 * x + i, ra = n0 + 32 * wni + 16 * x + i;
+    doff[x] = (unsigned)((g >> 1) * P.d_rows * 16 + (rd < P.d_rows ? rd : P.d_rows - 1) * 16 + 8 * (g & 1));
+    aoff[x] = (unsigned)((g >> 1) * P.a_rows * 16 + (ra < P.a_rows ? ra : P.a_rows - 1) * 16 + 8 * (g & 1));
+  }
+  const float* dbase = ws + P.d_row * np;
+  const float* abase = ws + P.a_row * np;
+  auto fetch = [&](f32x4 (&dv)[2][2], f32x4 (&av)[2][2], int64_t s) {
+    const gv4 dp = (gv4)(dbase + s * P.d_rows), ap = (gv4)(abase + s * P.a_rows);
+#pragma unroll
+    for (int x = 0; x < 2; ++x) {
+      dv[x][0] = dp[doff[x] >> 2]; dv[x][1] = dp[(doff[x] >> 2) + 1];
+      av[x][0] = ap[aoff[x] >> 2]; av[x][1] = ap[(aoff[x] >> 2) + 1];
+    }
+  };
+  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
+  f32x4 acc[2][2][3];
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y)
+#pragma unroll
+      for (int c = 0; c < 3; ++c) acc[x][y][c] = zero;
+  float bs[2] = {0.0f, 0.0f};
+  const bool own_bias = n0 == 0 && wni == 0;
+  // the products of one f32 product, smallest terms first, and the running sum each goes to (Products<3>)
+  constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0}, PA[6] = {2, 2, 2, 1, 1, 0};
+  f32x4 dv[2][2], av[2][2], dn[2][2], an[2][2];
+  fetch(dv, av, s_begin);
+  for (int64_t s = s_begin; s < s_end; s += 32) {
+    fetch(dn, an, s + 32 < s_end ? s + 32 : s);        // one step ahead (past the end: this step again, unused)
+    u32x4 dp[2][3], ap[2][3];
+#pragma unroll
+    for (int x = 0; x < 2; ++x) {
+      wgs_split8(dv[x][0], dv[x][1], dp[x]);
+      wgs_split8(av[x][0], av[x][1], ap[x]);
+      if (own_bias) {
+        const f32x4 u = dv[x][0] + dv[x][1];
+        bs[x] += (u[0] + u[1]) + (u[2] + u[3]);
+      }
+    }
+#pragma unroll
+    for (int pr = 0; pr < 6; ++pr)
+#pragma unroll
+      for (int x = 0; x < 2; ++x)
+#pragma unroll
+        for (int y = 0; y < 2; ++y) acc[x][y][PA[pr]] = wgs_mfma(dp[x][PW[pr]], ap[y][PX[pr]], acc[x][y][PA[pr]]);
+#pragma unroll
+    for (int x = 0; x < 2; ++x) { dv[x][0] = dn[x][0]; dv[x][1] = dn[x][1]; av[x][0] = an[x][0]; av[x][1] = an[x][1]; }
+  }
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+      tr_mfma_drain(acc[x][y][0], acc[x][y][1]);
+      tr_mfma_drain(acc[x][y][2], acc[x][y][2]);
+    }
+  if (own_bias) {      // db[m] = sum over samples of D[m][.]: the four lane groups hold 8 samples each of row i
+#pragma unroll
+    for (int x = 0; x < 2; ++x) {
+      float v = bs[x];
+      v += __shfl_xor(v, 16);
+      v += __shfl_xor(v, 32);
+      const int m = m0 + 32 * wmi + 16 * x + i;
+      if (g == 0 && m < P.M) atomicAdd(grads + P.b_off + m, v * inv_alpha);
+    }
+  }
+  float* C = grads + P.c_off;
+#pragma unroll
+  for (int x = 0; x < 2; ++x)
+#pragma unroll
+    for (int y = 0; y < 2; ++y) {
+      const f32x4 v = acc[x][y][0] + (acc[x][y][1] + acc[x][y][2]);
+      const int n = n0 + 32 * wni + 16 * y + i;
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        const int m = m0 + 32 * wmi + 16 * x + 4 * g + r;
+        if (m < P.M && n < P.N) atomicAdd(C + (size_t)m * P.N + n, v[r] * inv_alpha);
+      }
+    }
+}
+
 // ---- batch-statistics BatchNorm (models/layers.py:338-358 in train mode): the pieces that need the whole batch ----------
 // (n, d) row-major <-> slot layout [d][np] (slot j = feature j at the input of step 0)
-__global__ void __launch_bounds__(256) rows_to_slots_kernel(const float* __restrict__ x, float* __restrict__ st, int64_t n, int64_t np, int d) {
+__global__ void __launch_bounds__(256) rows_to_slots_kernel(const float* __restrict__ x, float* __restrict__ st, int64_t n, int64_t np, int d,
+                                                            const unsigned* __restrict__ gate) {
+  if (gate != nullptr && *gate == 0u) return;        // (the bf16x6 re-run of a repairing trainer's call that did not meet the range)
   const int64_t s = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (s >= np) return;
   for (int j = 0; j < d; ++j) st[(size_t)j * np + s] = s < n ? x[s * d + j] : 0.0f;
@@ -1327,8 +1494,10 @@ __device__ __forceinline__ float tr_block_sum(float v, float* red) {
 }
 
 // One block per slot: mean and UNBIASED variance over the n valid samples of the state (two passes, fixed order).
-__global__ void __launch_bounds__(256) bn_stats_kernel(const TrStep* __restrict__ steps, int k, const float* __restrict__ st, int64_t n, int64_t np) {
+__global__ void __launch_bounds__(256) bn_stats_kernel(const TrStep* __restrict__ steps, int k, const float* __restrict__ st, int64_t n, int64_t np,
+                                                       const unsigned* __restrict__ gate) {
   __shared__ float red[4];
+  if (gate != nullptr && *gate == 0u) return;
   const TrStep& S = steps[k];
   const int slot = blockIdx.x, f = S.feat[slot];
   const float* col = st + (size_t)slot * np;
@@ -1353,8 +1522,9 @@ __global__ void __launch_bounds__(256) bn_stats_kernel(const TrStep* __restrict_
 //   the centred squares -> pq[slot][NB];  finalize: mean, unbiased variance -> the caller's buffers.
 constexpr int BN_CHUNKS = 64;
 __global__ void __launch_bounds__(256) bn_stats_part_kernel(const float* __restrict__ st, int64_t n, int64_t np, int nb, int pass,
-                                                            const float* __restrict__ ps, float* __restrict__ out) {
+                                                            const float* __restrict__ ps, float* __restrict__ out, const unsigned* __restrict__ gate) {
   __shared__ float red[4];
+  if (gate != nullptr && *gate == 0u) return;
   const int slot = blockIdx.x, b = blockIdx.y;
   const float* col = st + (size_t)slot * np;
   const int64_t per = (n + nb - 1) / nb, s0 = (int64_t)b * per, s1 = s0 + per < n ? s0 + per : n;
@@ -1373,7 +1543,8 @@ __global__ void __launch_bounds__(256) bn_stats_part_kernel(const float* __restr
   if (threadIdx.x == 0) out[slot * nb + b] = tot;
 }
 __global__ void __launch_bounds__(64) bn_stats_final_kernel(const TrStep* __restrict__ steps, int k, int d, int64_t n, int nb,
-                                                            const float* __restrict__ ps, const float* __restrict__ pq) {
+                                                            const float* __restrict__ ps, const float* __restrict__ pq, const unsigned* __restrict__ gate) {
+  if (gate != nullptr && *gate == 0u) return;
   const int slot = threadIdx.x;
   if (slot >= d) return;
   const TrStep& S = steps[k];
@@ -1476,7 +1647,54 @@ struct gbnf_trainer {
   std::vector<float*> bmean_ptr, bvar_ptr;   // per step: the caller's device buffers (host copies of TrStep::bmean / bvar)
   LiveBlob* live = nullptr;            // round 3: the forward sweep on flow_kernel_hx3<TRAIN> (depth-1 TanhNet / ReLUNet), else null
   mutable int last_fwd_ranges = 0, last_bwd_ranges = 0;     // (tests) launches of the register-chained kernels by the last forward / backward call; 0 = the round-1 kernels ran
+  // GBNF_MATH_BF16X6 (gbnf_trainer_create_mode): `live` is the bf16x6 blob, every sweep and the weight gradients have the range of
+  // f32, and the per-step kernels of this file never run -- a call they would have served runs the chained pair on the buffer below
+  int math = GBNF_MATH_F16X3;
+  WgProblem* probs_safe_dev = nullptr;      // the weight-gradient problems cut into 64 x 64 blocks (wgrad_safe_kernel)
+  int wg_blocks_safe = 0;
+  mutable float* own_dev = nullptr;         // trace + operand workspace + ldj of the untraced entries of a range-safe trainer
+  mutable int64_t own_floats = 0;
+  // GBNF_MATH_DEFAULT, the repairing trainer: two whole trainers on the same parameter tensors.  A call runs rep_f (f16x3), whose
+  // launches count the waves that met the fp16 range in rep_dev[0..1] instead of the device's training counter; repair_decide_kernel
+  // turns that into this call's decision word rep_dev[2]; rep_s (bf16x6) follows in stream order with every launch gated on that word.
+  // rep_dev: [0..1] range events of the call in flight (64-bit), [2] decision, [3] the last forward call was re-run, [4] re-run calls
+  gbnf_trainer* rep_f = nullptr;
+  gbnf_trainer* rep_s = nullptr;
+  unsigned* rep_dev = nullptr;
+  unsigned* sat_override = nullptr;         // (rep_f) = rep_dev
+  const unsigned* gate = nullptr;           // (rep_s) = rep_dev + 2
+  mutable float* rep_scratch = nullptr;     // backward: [2][grad_floats] zeroed gradient buffers + [2][n d] g_x of the two forms
+  mutable int64_t rep_scratch_floats = 0;
+  mutable const float* last_fwd_trace = nullptr;      // the trace buffer rep_dev[3] speaks about (the repaired flag is keyed to it)
 };
+
+namespace gbnf {
+// mode: where "the forward that wrote this trace was re-run" comes from -- 0: no trace, 1: rep[3], 2: unknown trace, assume it was.
+// False positives are harmless (another stream's launches may raise the counter in between: an extra re-run is still right).
+__global__ void repair_decide_kernel(unsigned* rep, int mode, unsigned* eval_counter, int is_forward) {
+  const unsigned sat = rep[0];
+  const unsigned prev = mode == 1 ? rep[3] : (mode == 2 ? 1u : 0u);
+  const unsigned flag = (sat != 0u || prev != 0u) ? 1u : 0u;
+  rep[2] = flag;
+  if (is_forward) rep[3] = flag;
+  if (flag) {
+    rep[4] += 1u;
+    if (eval_counter != nullptr) atomicAdd(eval_counter, sat != 0u ? sat : 1u);      // counts like an evaluation repair, not as a wrong step
+  }
+  rep[0] = 0u; rep[1] = 0u;
+}
+// grads += the gradients of the form that counts; g_x likewise
+__global__ void __launch_bounds__(256) repair_commit_kernel(const unsigned* __restrict__ flag, const float* __restrict__ gf, const float* __restrict__ gs,
+                                                            float* __restrict__ grads, int64_t n_grads, const float* __restrict__ xf,
+                                                            const float* __restrict__ xs, float* __restrict__ g_x, int64_t n_x) {
+  const bool safe = *flag != 0u;
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_grads; e += stride) grads[e] += safe ? gs[e] : gf[e];
+  if (g_x != nullptr)
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < n_x; e += stride) g_x[e] = safe ? xs[e] : xf[e];
+}
+}  // namespace gbnf
+
 
 // tuning / test knob: GBNF_TRAIN_PATH=old keeps the round-1 kernels for every call
 static bool tr_fast_path_enabled() {
@@ -1519,8 +1737,42 @@ static void launch_train(const gbnf_trainer* t, const TrainLaunch& p, hipStream_
 extern "C" {
 
 int gbnf_trainer_create(const gbnf_flow_desc* desc, gbnf_trainer** out) {
+  return gbnf_trainer_create_mode(desc, GBNF_MATH_F16X3, out);
+}
+
+int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf_trainer** out) {
   if (out == nullptr) return fail(GBNF_ERR_INVALID, "gbnf_trainer_create: out is null");
   *out = nullptr;
+  if (math_mode == GBNF_MATH_F32)
+    return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_create_mode: there is no exact-f32 trainer (GBNF_MATH_BF16X6 is the f32-faithful mode)");
+  if (math_mode == GBNF_MATH_DEFAULT) {      // the repairing trainer: both of the others; a geometry without bf16x6 sweeps is refused with their reason
+    if (desc == nullptr) return fail(GBNF_ERR_INVALID, "gbnf_trainer_create_mode: desc is null");
+    gbnf_trainer* f = nullptr;
+    gbnf_trainer* sf = nullptr;
+    int rc = gbnf_trainer_create_mode(desc, GBNF_MATH_F16X3, &f);
+    if (rc) return rc;
+    rc = gbnf_trainer_create_mode(desc, GBNF_MATH_BF16X6, &sf);
+    if (rc) { gbnf_trainer_destroy(f); return rc; }
+    gbnf_trainer* t = new gbnf_trainer();
+    t->math = GBNF_MATH_DEFAULT;
+    t->kind = f->kind; t->d = f->d; t->K = f->K; t->grad_floats = f->grad_floats;
+    t->rep_f = f; t->rep_s = sf;
+    hipError_t e = hipMalloc((void**)&t->rep_dev, 8 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(t->rep_dev, 0, 8 * sizeof(unsigned));
+    if (e != hipSuccess) {
+      gbnf_trainer_destroy(t);
+      return fail(GBNF_ERR_HIP, "gbnf_trainer_create_mode: %s", hipGetErrorString(e));
+    }
+    f->sat_override = t->rep_dev;
+    live_blob_set_repair(f->live, t->rep_dev, nullptr);
+    sf->gate = t->rep_dev + 2;
+    live_blob_set_repair(sf->live, nullptr, t->rep_dev + 2);
+    *out = t;
+    return GBNF_OK;
+  }
+  if (math_mode != GBNF_MATH_F16X3 && math_mode != GBNF_MATH_BF16X6)
+    return fail(GBNF_ERR_INVALID, "gbnf_trainer_create_mode: unknown math mode %d", math_mode);
+  const bool safe = math_mode == GBNF_MATH_BF16X6;
   // Validate the descriptor with the evaluation path's own checks (shape rules are identical); that call dereferences
   // only the HOST fields (perm_indices, sizes), never the parameter arrays, when asked to validate only.
   int rc = gbnf_flow_validate(desc);
@@ -1536,6 +1788,7 @@ int gbnf_trainer_create(const gbnf_flow_desc* desc, gbnf_trainer** out) {
   if (d2 > TR_MAX_IN) return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_create: half width %d > %d", d2, TR_MAX_IN);
 
   gbnf_trainer* t = new gbnf_trainer();
+  t->math = math_mode;
   t->kind = desc->kind; t->d = d; t->K = K; t->additive = additive ? 1 : 0;
   t->nnets = glow ? 1 : 2;
   t->residual = residual ? 1 : 0;
@@ -1543,11 +1796,24 @@ int gbnf_trainer_create(const gbnf_flow_desc* desc, gbnf_trainer** out) {
   t->hp = ceil16(h);
   // (round 5) a width no TRAIN kernel variant is compiled for trains on the next wider one: the operand rows follow the VARIANT's
   // hidden tiles (the extra units have zero weights: their activations, gradients and operand rows are zeros)
-  const bool chained_shape = (residual ? (nl == 4 || nl == 6) : (nl >= 2 && nl <= 4)) && tr_fast_path_enabled();
+  // (a range-safe trainer has the chained kernels only: the GBNF_TRAIN_PATH knob does not apply to it)
+  const bool chained_shape = (residual ? (nl == 4 || nl == 6) : (nl >= 2 && nl <= 4)) && (safe || tr_fast_path_enabled());
   int hp_wide = 0;
   if (chained_shape) {
-    const int rows = live_blob_train_rows(desc);
+    const int rows = live_blob_train_rows(desc, safe ? 1 : 0);
     if (rows > t->hp && rows <= TR_MAX_HIDDEN) hp_wide = rows;
+    if (safe && rows == 0) {
+      const std::string why = gbnf_last_error();
+      delete t;
+      return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_create_mode: no bf16x6 training sweeps are compiled for this geometry (%s)", why.c_str());
+    }
+  }
+  if (safe && (!chained_shape || K > TR_CHAIN_MAX_STEPS)) {
+    delete t;
+    if (K > TR_CHAIN_MAX_STEPS)
+      return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_create_mode: the bf16x6 training sweeps hold at most %d steps (K = %d)", TR_CHAIN_MAX_STEPS, K);
+    return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_create_mode: no bf16x6 training sweeps for coupling nets of %d Linear layers%s", nl,
+                residual ? " (ResidualNet)" : "");
   }
   t->ip = ceil16(d2);
   t->op = ceil16(glow && !additive ? 2 * d2 : d2);
@@ -1574,9 +1840,10 @@ int gbnf_trainer_create(const gbnf_flow_desc* desc, gbnf_trainer** out) {
   // (the variant's wider rows only if the per-step kernels -- untraced forward calls, the fall-backs -- still fit with them)
   const int hp_own = t->hp;
   if (hp_wide) size_lds(hp_wide);
-  if (!hp_wide || t->lds_bwd[1] > (size_t)TR_LDS_BYTES) size_lds(hp_own);
+  // (a range-safe trainer never runs the per-step kernels: their LDS does not bound it)
+  if (!hp_wide || (!safe && t->lds_bwd[1] > (size_t)TR_LDS_BYTES)) size_lds(hp_own);
   t->net_rows = (int64_t)t->ip + 2LL * t->n_hidden * t->hp + 2LL * t->op;
-  if (t->lds_bwd[1] > (size_t)TR_LDS_BYTES) {
+  if (!safe && t->lds_bwd[1] > (size_t)TR_LDS_BYTES) {
     const size_t need = t->lds_bwd[1];
     delete t;
     return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_create: K*d = %d needs %zu bytes of LDS per workgroup (> %d)", K * d, need,
@@ -1714,6 +1981,19 @@ int gbnf_trainer_create(const gbnf_flow_desc* desc, gbnf_trainer** out) {
     if (e == hipSuccess) e = hipMalloc((void**)&t->probs_small_dev, sizeof(WgProblem) * small.size());
     if (e == hipSuccess) e = hipMemcpy(t->probs_small_dev, small.data(), sizeof(WgProblem) * small.size(), hipMemcpyHostToDevice);
   }
+  if (safe) {          // the same problems in 64 x 64 blocks, in operand order (wgrad_safe_kernel)
+    std::vector<WgProblem> sp = probs;
+    int b = 0;
+    for (WgProblem& P : sp) {
+      P.bm = P.bn = WGS_BLOCK; P.wm = P.wn = 2;
+      P.nb = (P.N + WGS_BLOCK - 1) / WGS_BLOCK;
+      P.blk_begin = b;
+      b += ((P.M + WGS_BLOCK - 1) / WGS_BLOCK) * P.nb;
+    }
+    t->wg_blocks_safe = b;
+    if (e == hipSuccess) e = hipMalloc((void**)&t->probs_safe_dev, sizeof(WgProblem) * sp.size());
+    if (e == hipSuccess) e = hipMemcpy(t->probs_safe_dev, sp.data(), sizeof(WgProblem) * sp.size(), hipMemcpyHostToDevice);
+  }
   if (e == hipSuccess) e = hipMalloc((void**)&t->prep_dev, sizeof(PrepProblem) * preps.size());
   if (e == hipSuccess) e = hipMemcpy(t->prep_dev, preps.data(), sizeof(PrepProblem) * preps.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc((void**)&t->frag_dev, (size_t)frag_off * 16);
@@ -1742,10 +2022,16 @@ int gbnf_trainer_create(const gbnf_flow_desc* desc, gbnf_trainer** out) {
     // (32-bit offsets inside one step's operand region: net_rows * np must stay below 2^31 -- checked per call)
     // (the kernels save one row per hidden unit of their COMPILED width: a variant wider than this flow's padded width -- the
     //  nearest compiled one for an unlisted geometry -- would write past the rows the workspace has; such flows keep the old path)
-    if (live_blob_create(desc, goff.data(), &lb) == GBNF_OK) {
+    if (live_blob_create(desc, goff.data(), &lb, safe ? 1 : 0) == GBNF_OK) {
       if (live_blob_hidden_rows(lb) == t->hp) t->live = lb;
       else live_blob_destroy(lb);
     }
+  }
+  // nothing falls back to a saturating kernel: a range-safe trainer without both of its sweeps does not exist
+  if (safe && !live_blob_has_backward(t->live)) {
+    const std::string why = t->live ? "the backward sweep's tables and stage slots do not fit a CU's LDS" : gbnf_last_error();
+    gbnf_trainer_destroy(t);
+    return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_create_mode: no bf16x6 training sweeps for this geometry (%s)", why.c_str());
   }
   *out = t;
   return GBNF_OK;
@@ -1753,6 +2039,10 @@ int gbnf_trainer_create(const gbnf_flow_desc* desc, gbnf_trainer** out) {
 
 int gbnf_trainer_destroy(gbnf_trainer* t) {
   if (t == nullptr) return GBNF_OK;
+  if (t->rep_f) gbnf_trainer_destroy(t->rep_f);
+  if (t->rep_s) gbnf_trainer_destroy(t->rep_s);
+  if (t->rep_dev) (void)hipFree(t->rep_dev);
+  if (t->rep_scratch) (void)hipFree(t->rep_scratch);
   if (t->steps_dev) (void)hipFree(t->steps_dev);
   if (t->tail_dev) (void)hipFree(t->tail_dev);
   if (t->probs_dev) (void)hipFree(t->probs_dev);
@@ -1761,6 +2051,8 @@ int gbnf_trainer_destroy(gbnf_trainer* t) {
   if (t->frag_dev) (void)hipFree(t->frag_dev);
   if (t->gmax_dev) (void)hipFree(t->gmax_dev);
   if (t->bn_part_dev) (void)hipFree(t->bn_part_dev);
+  if (t->probs_safe_dev) (void)hipFree(t->probs_safe_dev);
+  if (t->own_dev) (void)hipFree(t->own_dev);
   live_blob_destroy(t->live);
   delete t;
   return GBNF_OK;
@@ -1774,6 +2066,13 @@ int gbnf_trainer_grad_floats(const gbnf_trainer* t, int64_t* n_floats) {
 
 int gbnf_trainer_workspace_bytes(const gbnf_trainer* t, int64_t n, int64_t* bytes) {
   if (!t || !bytes || n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_workspace_bytes: bad argument");
+  if (t->rep_f) {          // both forms use the caller's workspace, one after the other
+    int64_t a = 0, b = 0;
+    gbnf_trainer_workspace_bytes(t->rep_f, n, &a);
+    gbnf_trainer_workspace_bytes(t->rep_s, n, &b);
+    *bytes = a > b ? a : b;
+    return GBNF_OK;
+  }
   const int64_t np = tr_padded(n);
   // operand regions + 256 slack rows (a 256-row block of wgrad_kernel may run past the last region)
   // ... + the gradient state of step-by-step launches (batch-statistics BatchNorm)
@@ -1792,7 +2091,7 @@ static void fill_launch(const gbnf_trainer* t, TrainLaunch& p, const float* x, i
   p.dbg = g_train_stamp_buf;
 #endif
   p.steps = t->steps_dev; p.tail = t->tail_dev; p.x = x;
-  p.sat = training_saturation_counter();
+  p.sat = t->sat_override != nullptr ? t->sat_override : training_saturation_counter();
   p.n = n; p.np = tr_padded(n);
   p.d = t->d; p.K = t->K; p.kind = t->kind; p.additive = t->additive;
   p.residual = t->residual;
@@ -1804,15 +2103,15 @@ static void fill_launch(const gbnf_trainer* t, TrainLaunch& p, const float* x, i
 // batch mean / unbiased variance of step k's input state (slot layout) into the caller's buffers
 static void launch_bn_stats(const gbnf_trainer* t, int k, const float* state, int64_t n, int64_t np, hipStream_t s) {
   if (n < 16384) {
-    hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)t->d), dim3(256), 0, s, (const TrStep*)t->steps_dev, k, state, n, np);
+    hipLaunchKernelGGL(bn_stats_kernel, dim3((unsigned)t->d), dim3(256), 0, s, (const TrStep*)t->steps_dev, k, state, n, np, t->gate);
     return;
   }
   const int nb = BN_CHUNKS;
   float* ps = t->bn_part_dev;
   float* pq = t->bn_part_dev + 64 * BN_CHUNKS;
-  hipLaunchKernelGGL(bn_stats_part_kernel, dim3((unsigned)t->d, (unsigned)nb), dim3(256), 0, s, state, n, np, nb, 1, (const float*)nullptr, ps);
-  hipLaunchKernelGGL(bn_stats_part_kernel, dim3((unsigned)t->d, (unsigned)nb), dim3(256), 0, s, state, n, np, nb, 2, (const float*)ps, pq);
-  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(1), dim3(64), 0, s, (const TrStep*)t->steps_dev, k, t->d, n, nb, (const float*)ps, (const float*)pq);
+  hipLaunchKernelGGL(bn_stats_part_kernel, dim3((unsigned)t->d, (unsigned)nb), dim3(256), 0, s, state, n, np, nb, 1, (const float*)nullptr, ps, t->gate);
+  hipLaunchKernelGGL(bn_stats_part_kernel, dim3((unsigned)t->d, (unsigned)nb), dim3(256), 0, s, state, n, np, nb, 2, (const float*)ps, pq, t->gate);
+  hipLaunchKernelGGL(bn_stats_final_kernel, dim3(1), dim3(64), 0, s, (const TrStep*)t->steps_dev, k, t->d, n, nb, (const float*)ps, (const float*)pq, t->gate);
 }
 
 // batch-statistics mode is on and some step has a BatchNorm whose statistics must come from the batch
@@ -1825,6 +2124,12 @@ static bool needs_step_launches(const gbnf_trainer* t) {
 
 int gbnf_trainer_set_batch_stats(gbnf_trainer* t, int32_t on) {
   if (!t) return fail(GBNF_ERR_INVALID, "gbnf_trainer_set_batch_stats: trainer is null");
+  if (t->rep_f) {
+    int rc = gbnf_trainer_set_batch_stats(t->rep_f, on);
+    if (rc == GBNF_OK) rc = gbnf_trainer_set_batch_stats(t->rep_s, on);
+    if (rc == GBNF_OK) t->batch_stats = on ? 1 : 0;
+    return rc;
+  }
   // (the step ranges of a batch-statistics sweep are tracked in a 32-bit mask: LiveReduce::skip_steps)
   if (on && t->K > 32) return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_set_batch_stats: batch statistics support at most 32 steps (K = %d)", t->K);
   if (on && t->kind == GBNF_KIND_REALNVP)
@@ -1839,6 +2144,10 @@ int gbnf_trainer_set_batch_stats(gbnf_trainer* t, int32_t on) {
 int gbnf_trainer_bind_batch_stats(gbnf_trainer* t, int32_t step, float* mean_dev, float* var_dev) {
   if (!t || step < 0 || step >= t->K || !mean_dev || !var_dev)
     return fail(GBNF_ERR_INVALID, "gbnf_trainer_bind_batch_stats: bad argument");
+  if (t->rep_f) {
+    const int rc = gbnf_trainer_bind_batch_stats(t->rep_f, step, mean_dev, var_dev);
+    return rc ? rc : gbnf_trainer_bind_batch_stats(t->rep_s, step, mean_dev, var_dev);
+  }
   if (!t->has_norm[step] || t->kind != GBNF_KIND_REALNVP)
     return fail(GBNF_ERR_INVALID, "gbnf_trainer_bind_batch_stats: step %d has no BatchNorm", step);
   float* ptrs[2] = {mean_dev, var_dev};
@@ -1854,11 +2163,40 @@ int gbnf_trainer_bind_batch_stats(gbnf_trainer* t, int32_t step, float* mean_dev
 
 int gbnf_trainer_trace_floats(const gbnf_trainer* t, int64_t n, int64_t* n_floats) {
   if (!t || !n_floats || n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_trace_floats: bad argument");
+  if (t->rep_f) {          // the two forms may run variants of different widths: the larger of their layouts
+    int64_t a = 0, b = 0;
+    gbnf_trainer_trace_floats(t->rep_f, n, &a);
+    gbnf_trainer_trace_floats(t->rep_s, n, &b);
+    *n_floats = a > b ? a : b;
+    return GBNF_OK;
+  }
   *n_floats = ((int64_t)t->K + 1) * t->d * tr_padded(n);     // K normalised states + the running state
   if (t->live)       // + the operand workspace the forward sweep fills (and the slack rows wgrad_kernel may read behind it)
     *n_floats += ((int64_t)t->K * t->nnets * t->net_rows + TR_WS_SLACK_ROWS) * tr_padded(n);
   return GBNF_OK;
 }
+
+}  // extern "C"
+
+// A range-safe trainer's own trace buffer (gbnf_trainer_trace_floats) + np floats of ldj behind it, for the calls that come without
+// a trace: grown on demand and kept (a growing call synchronises the device once).
+static int own_buffer(const gbnf_trainer* t, int64_t n, float** trace, float** ldj) {
+  int64_t need = 0;
+  gbnf_trainer_trace_floats(t, n, &need);
+  const int64_t np = tr_padded(n);
+  if (t->own_floats < need + np) {
+    if (t->own_dev) (void)hipFree(t->own_dev);
+    t->own_dev = nullptr; t->own_floats = 0;
+    const hipError_t e = hipMalloc((void**)&t->own_dev, (size_t)(need + np) * 4);
+    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer: %lld bytes of trace scratch: %s", (long long)((need + np) * 4), hipGetErrorString(e));
+    t->own_floats = need + np;
+  }
+  *trace = t->own_dev;
+  *ldj = t->own_dev + need;
+  return GBNF_OK;
+}
+
+extern "C" {
 
 int gbnf_trainer_forward(const gbnf_trainer* t, const float* x, int64_t n, float* z, float* ldj, float* trace,
                          void* stream) {
@@ -1866,6 +2204,30 @@ int gbnf_trainer_forward(const gbnf_trainer* t, const float* x, int64_t n, float
   if (n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: n < 0");
   if (n == 0) return GBNF_OK;
   if (!x) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: x is null");
+  if (t->rep_f) {
+    // f16x3 as ever; then, in stream order, the decision on the device and the bf16x6 form of the same call, which overwrites z, ldj,
+    // the trace and the operand workspace if this call met the range and returns at once if not.  No host read, no synchronisation.
+    hipStream_t s = (hipStream_t)stream;
+    int rc = gbnf_trainer_forward(t->rep_f, x, n, z, ldj, trace, stream);
+    if (rc) return rc;
+    hipLaunchKernelGGL(repair_decide_kernel, dim3(1), dim3(1), 0, s, t->rep_dev, 0, saturation_counter(), 1);
+    rc = gbnf_trainer_forward(t->rep_s, x, n, z, ldj, trace, stream);
+    if (rc) return rc;
+    t->last_fwd_trace = trace;
+    t->last_fwd_ranges = t->rep_f->last_fwd_ranges;
+    return GBNF_OK;
+  }
+  const bool safe = t->math == GBNF_MATH_BF16X6;
+  if (safe) {          // without a trace: the same sweep into the trainer's own buffer
+    float* own_trace = nullptr;
+    float* own_ldj = nullptr;
+    if (trace == nullptr || (ldj == nullptr && needs_step_launches(t))) {
+      const int rc = own_buffer(t, n, &own_trace, &own_ldj);
+      if (rc) return rc;
+    }
+    if (trace == nullptr) trace = own_trace;
+    if (ldj == nullptr && needs_step_launches(t)) ldj = own_ldj;
+  }
   TrainLaunch p;
   fill_launch(t, p, x, n);
   p.z_out = z; p.ldj_out = ldj; p.trace_out = trace;
@@ -1888,7 +2250,7 @@ int gbnf_trainer_forward(const gbnf_trainer* t, const float* x, int64_t n, float
       // in HBM in slot layout between the launches (the last d * np floats of the trace buffer)
       float* state = trace + (int64_t)t->K * t->d * p.np;
       const unsigned nb = (unsigned)((p.np + 255) / 256);
-      hipLaunchKernelGGL(rows_to_slots_kernel, dim3(nb), dim3(256), 0, s, x, state, n, p.np, t->d);
+      hipLaunchKernelGGL(rows_to_slots_kernel, dim3(nb), dim3(256), 0, s, x, state, n, p.np, t->d, t->gate);
       bool first = true;
       for (int k0 = 0; k0 < t->K;) {
         int k1 = k0 + 1;
@@ -1913,6 +2275,12 @@ int gbnf_trainer_forward(const gbnf_trainer* t, const float* x, int64_t n, float
     if (e2 != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_forward launch: %s", hipGetErrorString(e2));
     return GBNF_OK;
   }
+  if (safe) {          // no per-step kernel ever runs for a range-safe trainer: say why the sweep cannot
+    if ((int64_t)t->nnets * t->net_rows * p.np >= (1LL << 31))
+      return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_forward: %lld rows exceed the 32-bit operand offsets of the bf16x6 sweep", (long long)n);
+    if (n < 2) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: batch statistics need n >= 2");
+    return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: batch-statistics mode needs every BatchNorm step's buffers (gbnf_trainer_bind_batch_stats)");
+  }
   // the parameters may have changed since the last call: split them into this call's MFMA fragments
   t->last_fwd_ranges = 0;
   hipLaunchKernelGGL(prep_kernel, dim3((unsigned)t->prep_blocks), dim3(64), 0, s, (const PrepProblem*)t->prep_dev, t->n_prep, t->frag_dev);
@@ -1925,7 +2293,7 @@ int gbnf_trainer_forward(const gbnf_trainer* t, const float* x, int64_t n, float
     if (n < 2) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: batch statistics need n >= 2");
     float* state = trace + (int64_t)t->K * t->d * p.np;
     const unsigned nb = (unsigned)((p.np + 255) / 256);
-    hipLaunchKernelGGL(rows_to_slots_kernel, dim3(nb), dim3(256), 0, s, x, state, n, p.np, t->d);
+    hipLaunchKernelGGL(rows_to_slots_kernel, dim3(nb), dim3(256), 0, s, x, state, n, p.np, t->d, t->gate);
     for (int k = 0; k < t->K; ++k) {
       if (t->has_norm[k])
         launch_bn_stats(t, k, state, n, p.np, s);
@@ -1948,11 +2316,57 @@ int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, cons
   if (n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: n < 0");
   if (n == 0) return GBNF_OK;
   if (!x || !grads || !workspace) return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: x / grads / workspace is null");
+  if (t->rep_f) {
+    // Both forms into the trainer's own zeroed gradient buffers (the ABI accumulates into `grads`: the f16x3 result must not reach it
+    // when the step is re-run), then repair_commit_kernel adds the one that counts and selects g_x the same way.  The re-run happens
+    // when this call's f16x3 launches met the range or the forward call that wrote `trace` was re-run (rep_dev[3], keyed to the trace
+    // pointer in last_fwd_trace; a trace this trainer does not know counts as re-run).  The two forms may run variants of different
+    // widths, i.e. different operand layouts behind the trace: the re-run writes its own forward sweep into the buffer first.
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t ng = t->grad_floats, nx = g_x ? n * (int64_t)t->d : 0;
+    if (t->rep_scratch_floats < 2 * ng + 2 * nx) {
+      if (t->rep_scratch) (void)hipFree(t->rep_scratch);
+      t->rep_scratch = nullptr; t->rep_scratch_floats = 0;
+      const hipError_t e = hipMalloc((void**)&t->rep_scratch, (size_t)(2 * ng + 2 * nx) * 4);
+      if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward: gradient scratch: %s", hipGetErrorString(e));
+      t->rep_scratch_floats = 2 * ng + 2 * nx;
+    }
+    float* gf = t->rep_scratch;
+    float* gs = gf + ng;
+    float* xf = g_x ? gs + ng : nullptr;
+    float* xs = g_x ? xf + nx : nullptr;
+    (void)hipMemsetAsync(gf, 0, (size_t)ng * 4, s);
+    (void)hipMemsetAsync(gs, 0, (size_t)ng * 4, s);
+    int rc = gbnf_trainer_backward(t->rep_f, x, n, trace, g_z, g_ldj, xf, gf, workspace, workspace_bytes, stream);
+    if (rc) return rc;
+    const int mode = trace == nullptr ? 0 : (trace == t->last_fwd_trace ? 1 : 2);
+    hipLaunchKernelGGL(repair_decide_kernel, dim3(1), dim3(1), 0, s, t->rep_dev, mode, saturation_counter(), 0);
+    if (trace != nullptr) rc = gbnf_trainer_forward(t->rep_s, x, n, nullptr, nullptr, const_cast<float*>(trace), stream);
+    if (rc == GBNF_OK) rc = gbnf_trainer_backward(t->rep_s, x, n, trace, g_z, g_ldj, xs, gs, workspace, workspace_bytes, stream);
+    if (rc) return rc;
+    const int64_t work = ng > nx ? ng : nx;
+    const unsigned cb = (unsigned)((work + 255) / 256 < 1024 ? (work + 255) / 256 : 1024);
+    hipLaunchKernelGGL(repair_commit_kernel, dim3(cb ? cb : 1), dim3(256), 0, s, (const unsigned*)(t->rep_dev + 2), (const float*)gf, (const float*)gs,
+                       grads, ng, (const float*)xf, (const float*)xs, g_x, nx);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward commit: %s", hipGetErrorString(e));
+    t->last_bwd_ranges = t->rep_f->last_bwd_ranges;
+    return GBNF_OK;
+  }
   int64_t need = 0;
   gbnf_trainer_workspace_bytes(t, n, &need);
   if (workspace_bytes < need)
     return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: workspace of %lld bytes < %lld", (long long)workspace_bytes,
                 (long long)need);
+  const bool safe = t->math == GBNF_MATH_BF16X6;
+  if (safe && trace == nullptr) {      // without a trace: the traced pair, the forward into the trainer's own buffer
+    float* own_trace = nullptr;
+    float* own_ldj = nullptr;
+    int rc = own_buffer(t, n, &own_trace, &own_ldj);
+    if (rc == GBNF_OK) rc = gbnf_trainer_forward(t, x, n, nullptr, own_ldj, own_trace, stream);
+    if (rc) return rc;
+    trace = own_trace;
+  }
   TrainLaunch p;
   fill_launch(t, p, x, n);
   p.g_z = g_z; p.g_ldj = g_ldj; p.g_x = g_x; p.grads = grads; p.ws = (float*)workspace; p.trace = trace;
@@ -1995,6 +2409,8 @@ int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, cons
         if (t->has_norm[k0]) {
           LiveReduce one = red;
           one.skip_steps = ~(1u << k0);
+          // (n_blocks = 0: only the reduce blocks of wgrad_kernel run -- plain f32 sums of the partials, nothing is split or clamped, so
+          //  a range-safe trainer shares this launch)
           hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)(2 * red.K), 1u), dim3(WG_THREADS), 2048, s, t->probs_dev, t->n_probs, (const float*)acts, grads,
                              p.np, 512, (const unsigned*)t->gmax_dev, 0, one);
           done |= 1u << k0;
@@ -2022,12 +2438,29 @@ int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, cons
     while (chunk2 < 2048 && (int64_t)wg_blocks * (p.np / (2 * chunk2)) >= 240) chunk2 *= 2;
     if (const char* e = getenv("GBNF_WG_CHUNK")) { if (atoi(e) > 0) chunk2 = atoi(e); }      // (A/B runs)
     // (+ 2 K blocks: the sums of the backward kernel's parameter-gradient partials ride in this launch)
+    if (safe) {
+      // 64 x 64 blocks of 4 waves: samples per block so that ~4 workgroups per CU remain (the threshold of 1024 is reasoned from the
+      // 256 CUs, not measured)
+      int chunk3 = 128;
+      while (chunk3 < 2048 && (int64_t)t->wg_blocks_safe * (p.np / (2 * chunk3)) >= 1024) chunk3 *= 2;
+      const dim3 wgrid3((unsigned)(t->wg_blocks_safe + 2 * red.K), (unsigned)((p.np + chunk3 - 1) / chunk3));
+      hipLaunchKernelGGL(wgrad_safe_kernel, wgrid3, dim3(WGS_THREADS), 0, s, (const WgProblem*)t->probs_safe_dev, t->n_probs,
+                         (const float*)acts, grads, p.np, chunk3, (const unsigned*)t->gmax_dev, t->wg_blocks_safe, red, t->gate);
+      const hipError_t e3 = hipGetLastError();
+      if (e3 != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward launch: %s", hipGetErrorString(e3));
+      return GBNF_OK;
+    }
     const dim3 wgrid2((unsigned)(wg_blocks + 2 * red.K), (unsigned)((p.np + chunk2 - 1) / chunk2));
     hipLaunchKernelGGL(wgrad_kernel, wgrid2, dim3(WG_THREADS), WG_LDS_BYTES, s, wg_probs, t->n_probs,
                        (const float*)acts, grads, p.np, chunk2, (const unsigned*)t->gmax_dev, wg_blocks, red);
     const hipError_t e2 = hipGetLastError();
     if (e2 != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward launch: %s", hipGetErrorString(e2));
     return GBNF_OK;
+  }
+  if (safe) {
+    if ((int64_t)t->nnets * t->net_rows * p.np >= (1LL << 31))
+      return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_backward: %lld rows exceed the 32-bit operand offsets of the bf16x6 sweep", (long long)n);
+    return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: batch-statistics mode needs every BatchNorm step's buffers (gbnf_trainer_bind_batch_stats)");
   }
   // a trace is valid only while the parameters are what they were in the forward call that wrote it (include/gbnf.h):
   // that call split them into this trainer's fragment buffer, so the fragments are still the right ones
@@ -2068,6 +2501,19 @@ int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, cons
                      (const unsigned*)t->gmax_dev, t->wg_blocks, LiveReduce{});
   e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward wgrad launch: %s", hipGetErrorString(e));
+  return GBNF_OK;
+}
+
+int gbnf_trainer_repair_count(const gbnf_trainer* t, int64_t* calls, int32_t reset) {
+  if (!t || !calls) return fail(GBNF_ERR_INVALID, "gbnf_trainer_repair_count: null argument");
+  *calls = 0;
+  if (t->rep_dev == nullptr) return GBNF_OK;          // GBNF_MATH_F16X3 and GBNF_MATH_BF16X6 trainers never re-run a call
+  hipError_t e = hipDeviceSynchronize();
+  unsigned v = 0;
+  if (e == hipSuccess) e = hipMemcpy(&v, t->rep_dev + 4, sizeof(v), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && reset) e = hipMemset(t->rep_dev + 4, 0, sizeof(unsigned));
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_repair_count: %s", hipGetErrorString(e));
+  *calls = (int64_t)v;
   return GBNF_OK;
 }
 

@@ -1,7 +1,11 @@
-// One translation unit per backward-kernel variant of the training path: -DGBNF_V_ARGS="KIND,HT,OT,ACTA,ACTB,DEPTH"
+// One translation unit per backward-kernel variant of the training path: -DGBNF_V_ARGS="KIND,HT,OT,ACTA,ACTB,DEPTH" [-DGBNF_V_SAFE=1: bf16x6]
 #include "gbnf_train_bwd.hip.h"
 #ifndef GBNF_V_ARGS
 #error "compile with -DGBNF_V_ARGS=KIND,HT,OT,ACTA,ACTB,DEPTH"
 #endif
+#ifdef GBNF_V_SAFE
+#define GBNF_INST2(...) GBNF_INSTANTIATE_HX3_BWD_SAFE(__VA_ARGS__)
+#else
 #define GBNF_INST2(...) GBNF_INSTANTIATE_HX3_BWD(__VA_ARGS__)
+#endif
 GBNF_INST2(GBNF_V_ARGS)

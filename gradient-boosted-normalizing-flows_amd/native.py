@@ -33,7 +33,7 @@ ABI_SYMBOLS = (
     "gbnf_actnorm_init", "gbnf_boosting_weights",
     "gbnf_flow_validate", "gbnf_trainer_create", "gbnf_trainer_destroy", "gbnf_trainer_forward",
     "gbnf_trainer_grad_floats", "gbnf_trainer_workspace_bytes", "gbnf_trainer_backward", "gbnf_trainer_trace_floats",
-    "gbnf_trainer_bind_batch_stats", "gbnf_trainer_set_batch_stats",
+    "gbnf_trainer_bind_batch_stats", "gbnf_trainer_set_batch_stats", "gbnf_trainer_create_mode", "gbnf_trainer_repair_count",
     "gbnf_image_flow_create", "gbnf_image_flow_destroy", "gbnf_image_flow_info", "gbnf_image_flow_workspace_bytes",
     "gbnf_image_flow_forward", "gbnf_image_flow_prior", "gbnf_image_flow_eps_floats", "gbnf_image_flow_inverse",
     "gbnf_image_flow_numerics", "gbnf_image_flow_repair_counts", "gbnf_image_flow_create_mode", "gbnf_image_flow_actnorm_stats",
@@ -162,6 +162,8 @@ def lib():
     L.gbnf_tuning_set.argtypes = [C.c_char_p, i32]
     L.gbnf_tuning_get.argtypes = [C.c_char_p, C.POINTER(i32)]
     L.gbnf_trainer_create.argtypes = [C.POINTER(_FlowDesc), C.POINTER(vp)]
+    L.gbnf_trainer_create_mode.argtypes = [C.POINTER(_FlowDesc), C.c_int32, C.POINTER(vp)]
+    L.gbnf_trainer_repair_count.argtypes = [vp, C.POINTER(i64), C.c_int32]
     L.gbnf_trainer_destroy.argtypes = [vp]
     L.gbnf_trainer_forward.argtypes = [vp, vp, i64, vp, vp, vp, vp]
     L.gbnf_trainer_trace_floats.argtypes = [vp, i64, C.POINTER(i64)]
@@ -552,10 +554,20 @@ class NativeTrainer:
 
     ``dev_spec`` has the shape of a flow spec (spec.py) but every float array is a contiguous float32 CUDA tensor --
     the caller's parameter / buffer storage itself (``perm`` stays a host int64 array).  Nothing is copied: the
-    library keeps the addresses, this object keeps the tensors alive."""
+    library keeps the addresses, this object keeps the tensors alive.
 
-    def __init__(self, dev_spec):
+    ``math``: "f16x3" (default: the fast sweeps, operands beyond +-65504 saturate and are counted) or "bf16x6" (range-safe: f32
+    range in every sweep, the re-pack and the weight gradients) or "repair" (f16x3 first; a call that met the range is re-run in
+    bf16x6 within the same call, decided on the device: GBNF_MATH_DEFAULT) -- gbnf_trainer_create_mode.  A geometry without the
+    kernels of the mode raises GbnfError; nothing falls back."""
+
+    TRAIN_MATH = {"f16x3": MATH["f16x3"], "bf16x6": MATH["bf16x6"], "repair": MATH["default"]}
+
+    def __init__(self, dev_spec, math="f16x3"):
         import torch
+        if math not in self.TRAIN_MATH:
+            raise GbnfError(f"NativeTrainer: math must be one of {sorted(self.TRAIN_MATH)}, got {math!r}")
+        self.math = math
         self._tensors = []        # keep-alive; also the identity check for re-creation
         self.params = []          # tensors in the order of the flat gradient buffer (None = reserved, unused region)
         self._sizes = []
@@ -621,7 +633,7 @@ class NativeTrainer:
                 steps[k] = s
             desc.realnvp_steps = steps
         h = C.c_void_p()
-        _check(lib().gbnf_trainer_create(C.byref(desc), C.byref(h)))
+        _check(lib().gbnf_trainer_create_mode(C.byref(desc), self.TRAIN_MATH[math], C.byref(h)))
         self.handle = h
         # BatchNorm on batch statistics (the reference's train() mode): bind the buffers that receive them
         self.has_batch_stats = False
@@ -700,6 +712,13 @@ class NativeTrainer:
             grads.append(None if t is None else flat[off:off + size].view(t.shape))
             off += size
         return g_x, grads
+
+    def repair_count(self, reset=False):
+        """Forward / backward calls of this trainer whose bf16x6 re-run actually ran (a "repair" trainer; always 0 otherwise).
+        Synchronises with the device (gbnf_trainer_repair_count)."""
+        n = C.c_int64(0)
+        _check(lib().gbnf_trainer_repair_count(self.handle, C.byref(n), 1 if reset else 0))
+        return int(n.value)
 
     def close(self):
         if getattr(self, "handle", None):

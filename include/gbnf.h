@@ -137,14 +137,23 @@ const char* gbnf_last_error(void);
 
 /* The split-f16 kernels (evaluation, training) represent an f32 operand by two fp16 pieces: beyond +-65504 it cannot be
  * stored (the normalised input of a coupling net, a ReLU activation; in training also scaled gradients).  The EVALUATION
- * kernels repair such samples themselves (bf16x6 pass, see GBNF_MATH_F16X3); the training kernels saturate (and a trainer's
- * re-pack counts a WEIGHT beyond the range: it cannot be split at all).  This
- * returns how many waves ran into that since the last reset -- 0 for z-scored data on a trained flow -- and optionally
- * resets the counter.  One counter per device: this reports (and resets) the CURRENT device's, after a
+ * kernels repair such samples themselves (bf16x6 pass, see GBNF_MATH_F16X3).  What TRAINING does depends on the trainer's
+ * math mode (gbnf_trainer_create_mode):
+ *   GBNF_MATH_F16X3   the kernels saturate: the operand is clamped to +-65504, the step stays finite, the gradients of the
+ *                     affected samples are wrong, and the wave is counted here (so is a WEIGHT beyond the range met by the
+ *                     trainer's re-pack: it cannot be split at all).  What gbnf_trainer_create builds.
+ *   GBNF_MATH_BF16X6  range-safe: every sweep, the re-pack and the weight gradients run on three bf16 pieces with the range
+ *                     of f32; nothing is clamped and nothing is counted.
+ *   GBNF_MATH_DEFAULT repairing: f16x3 first; a forward or backward call whose f16x3 launches met the range is re-run in bf16x6 within
+ *                     the same call (decided on the device, no host read).  Such a step counts in gbnf_saturation_count like an
+ *                     evaluation repair and in gbnf_trainer_repair_count, NOT in gbnf_training_saturation_count: its gradients are right.
+ * This returns how many waves ran into the range since the last reset -- 0 for z-scored data on a trained flow -- and
+ * optionally resets the counter.  One counter per device: this reports (and resets) the CURRENT device's, after a
  * hipDeviceSynchronize() (every stream of that device). */
 int gbnf_saturation_count(int64_t* count, int32_t reset);
-/* The part of that count that came from TRAINING launches (gbnf_trainer_forward / _backward: traced and untraced sweeps, the weight
- * re-pack): these saturate and are NOT repaired, so a non-zero value means steps with wrong gradients -- while the rest of
+/* The part of that count that came from TRAINING launches of GBNF_MATH_F16X3 trainers (gbnf_trainer_forward / _backward: traced and
+ * untraced sweeps, the weight re-pack): these saturate and are NOT repaired, so a non-zero value means steps with wrong gradients
+ * (a GBNF_MATH_BF16X6 trainer never moves it) -- while the rest of
  * gbnf_saturation_count() (evaluation launches) was re-evaluated in the same call.  Same device, same synchronisation; `reset` clears
  * this part only.  (The drop-in module reads it when it leaves training mode: BoostedFlow.train / .eval.) */
 int gbnf_training_saturation_count(int64_t* count, int32_t reset);
@@ -344,7 +353,40 @@ typedef struct gbnf_trainer gbnf_trainer;
 int gbnf_flow_validate(const gbnf_flow_desc* desc);
 
 int gbnf_trainer_create(const gbnf_flow_desc* desc_device_params, gbnf_trainer** out);
+/* ... with an explicit GBNF_MATH_* mode.  GBNF_MATH_F16X3: what gbnf_trainer_create does (that function is this call).
+ * GBNF_MATH_BF16X6: the RANGE-SAFE trainer -- every forward and backward call of it, with and without a trace buffer, on running
+ * and on batch statistics, runs the bf16x6 forms of the register-chained sweeps (three pieces per operand, six products), the
+ * bf16x6 re-pack of the live weights and the bf16 weight-gradient kernel: f32 range throughout, no clamp, and
+ * gbnf_training_saturation_count does not move.  A call without a trace runs the traced pair on a trace buffer the trainer owns
+ * (it grows on demand; gbnf_trainer_trace_floats says how much); the per-step kernels never run.  Covered geometries, K <= 24:
+ *   Glow and RealNVP with TanhNet / ReLUNet coupling nets (any mix per step and net) of coupling_network_depth 0, 1, 2, h <= 256;
+ *   RealNVP with one-block ResidualNets, h <= 256;  d <= 64 as everywhere.
+ * Everything else -- 256 < h <= 512, two-block ResidualNets, K > 24, a flow whose backward tables do not fit a CU's LDS --
+ * answers GBNF_ERR_UNSUPPORTED with the reason in gbnf_last_error(): nothing falls back to a saturating kernel.
+ * GBNF_MATH_DEFAULT: the REPAIRING trainer, for the same geometries (anything else: GBNF_ERR_UNSUPPORTED with the reason, K > 24
+ * included).  A call launches the f16x3 kernels as ever; their range events go to a counter of the trainer; one thread on the device
+ * turns it into the call's decision word; the bf16x6 form of the same call follows in stream order, every launch gated on that word
+ * (a launch with nothing to do returns at once; the forward sweep's grid is capped like an evaluation repair launch).  No host read, no
+ * synchronisation.  False positives are possible (an extra re-run is still right), false negatives are not.
+ *   forward   the re-run overwrites z, ldj, the trace and the operand workspace.
+ *   backward  both forms accumulate into zeroed scratch of the trainer (grad_floats floats each; it grows at the first call of a
+ *             size, which synchronises once); a commit kernel adds the one that counts into `grads` and selects g_x the same way.
+ *             It is re-run when its own f16x3 launches met the range OR the forward call that wrote `trace` was re-run.  That
+ *             fact is trainer state keyed to the trace POINTER of the last forward call (a trace the trainer does not know counts as
+ *             re-run).  The f16x3 and bf16x6 forms may run variants of different widths, i.e. different operand layouts behind the
+ *             trace, so a backward re-run first writes its own forward sweep into the trace buffer (gbnf_trainer_trace_floats and
+ *             gbnf_trainer_workspace_bytes return the larger of the two forms' sizes).
+ *   re-pack   a weight beyond the range met by the f16x3 re-pack counts as "met the range".
+ * The backward sweep's and the weight gradients' re-run launches are gated but not capped: their workgroups return at once.
+ * GBNF_MATH_F32: GBNF_ERR_UNSUPPORTED, there is no exact-f32 trainer.
+ * Calls of ONE trainer are not safe to issue concurrently from two threads or streams: the untraced entries of a range-safe trainer
+ * and the backward of a repairing one use buffers the trainer owns, which grow (hipFree + hipMalloc: a device synchronisation) when
+ * a call needs more than any call before it. */
+int gbnf_trainer_create_mode(const gbnf_flow_desc* desc_device_params, int32_t math_mode, gbnf_trainer** out);
 int gbnf_trainer_destroy(gbnf_trainer* trainer);
+/* Forward and backward calls of this trainer whose bf16x6 re-run actually ran (a GBNF_MATH_DEFAULT trainer); synchronises like
+ * gbnf_saturation_count.  Always 0 for GBNF_MATH_F16X3 and GBNF_MATH_BF16X6 trainers. */
+int gbnf_trainer_repair_count(const gbnf_trainer* trainer, int64_t* calls, int32_t reset);
 
 /* z, ldj = flows[c](x) on the live parameters (same semantics and outputs as gbnf_flow_forward).  `trace` (optional,
  * gbnf_trainer_trace_floats(n) floats of DEVICE memory) receives every step's normalised state; handing it to

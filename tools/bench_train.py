@@ -76,6 +76,9 @@ def main():
     ap.add_argument("--tune", action="append", default=[], help="key=value for gbnf_tuning_set (A/B runs)")
     ap.add_argument("--graph", action="store_true", help="also time the step captured once in a HIP graph and replayed (torch.cuda.CUDAGraph)")
     ap.add_argument("--batch-stats", action="store_true", help="RealNVP: BatchNorm on batch statistics (the reference's train() mode, its default training configuration)")
+    ap.add_argument("--math", choices=["f16x3", "bf16x6", "repair"], default="f16x3",
+                    help="the trainer's math mode (native.NativeTrainer): the saturating f16x3 sweeps, the range-safe bf16x6 ones, or f16x3 with the same-call bf16x6 re-run")
+    ap.add_argument("--out-of-range-rows", type=int, default=0, help="put this many rows of the batch beyond the fp16 range (3e5): the cost of a repaired step")
     ap.add_argument("--no-torch-legs", action="store_true", help="skip the eager-PyTorch GPU leg (profiler runs: thousands of tiny dispatches)")
     a = ap.parse_args()
     cfg = CONFIGS[a.config]
@@ -91,10 +94,13 @@ def main():
             if st.get("bn") is not None:
                 st["bn"]["batch_mean"] = torch.zeros(cfg["d"], device=dev)
                 st["bn"]["batch_var"] = torch.zeros(cfg["d"], device=dev)
-    tr = native.NativeTrainer(dv)
+    tr = native.NativeTrainer(dv, math=a.math)
     if a.batch_stats:
         tr.set_batch_stats(True)
-    x = torch.from_numpy(synth.synth_batch(a.batch, cfg["d"], seed=0)).to(dev)
+    xh = synth.synth_batch(a.batch, cfg["d"], seed=0)
+    for r in range(a.out_of_range_rows):
+        xh[(7 + 143 * r) % a.batch, :] = 3.0e5
+    x = torch.from_numpy(xh).to(dev)
     n = a.batch
 
     def hip_step():
@@ -172,7 +178,7 @@ def main():
     kern_s = (fw + bw) * 1e-3
     print(json.dumps({
         "metric": f"training step (forward+backward) samples/sec, one component, {a.config}", "unit": "samples/s",
-        "value": n / t_hip, "ms_per_step": t_hip * 1e3, "batch": n, "dtype": "f16x3", "data": "synthetic", "batch_stats": bool(a.batch_stats),
+        "value": n / t_hip, "ms_per_step": t_hip * 1e3, "batch": n, "dtype": a.math, "data": "synthetic", "batch_stats": bool(a.batch_stats),
         "config": {"workload": f"{a.config}: one component, batch {n}: traced forward, loss gradient, backward (dgrad + wgrad), synthetic weights"},
         "hip_graph_replay": None if t_graph is None else {"value": n / t_graph, "ms_per_step": t_graph * 1e3},
         "forward_kernel_ms": fw, "backward_kernels_ms": bw,
