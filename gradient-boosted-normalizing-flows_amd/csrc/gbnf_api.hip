@@ -134,7 +134,6 @@ constexpr float PROBE_MAX_REL_ERR = 2.5e-6f;
 
 // One counter per device (a kernel may only touch memory of the device it runs on): allocated on first use by a launch
 // on that device, never freed.
-constexpr int MAX_DEVICES = 64;
 static std::mutex g_dev_mu;
 static unsigned* g_sat_counter[MAX_DEVICES] = {};
 
@@ -2192,9 +2191,8 @@ int live_blob_hidden_rows(const LiveBlob* lb) { return lb ? 16 * lb->ht : 0; }
 
 // g_z / g_ldj (either may be null) -> g_x (or null), the ActNorm / BatchNorm entries of `grads`, and the gradient-side
 // operands of the weight gradients in `acts` (the workspace the forward sweep filled); gmax: gmax_kernel's result
-int live_blob_backward(LiveBlob* lb, int64_t n, const float* trace, float* acts, int64_t np, int ip, int hp, int op,
-                       const float* g_z, const float* g_ldj, float* g_x, float* grads, const unsigned* gmax, void* stream,
-                       LiveReduce* reduce_out, const LiveRange* range) {
+int live_blob_backward(LiveBlob* lb, const TrainLayout& lay, float* trace, const float* g_z, const float* g_ldj, float* g_x,
+                       float* grads, const unsigned* gmax, void* stream, LiveReduce* reduce_out, const LiveRange* range) {
   hipStream_t s = (hipStream_t)stream;
   // the transposed tiles were packed by the forward call that wrote the trace (the parameters are unchanged since: the trace
   // contract of include/gbnf.h); a trainer that has not run one yet packs them here
@@ -2208,24 +2206,23 @@ int live_blob_backward(LiveBlob* lb, int64_t n, const float* trace, float* acts,
   }
   FlowLaunch p{};
   p.blobs = lb->table_dev; p.blobs_bwd = lb->tableB_dev;
-  p.n = n; p.d = lb->d; p.n_steps = lb->K; p.n_comp = 1; p.n_batches = 1; p.additive = lb->additive;
+  p.n = lay.n; p.d = lb->d; p.n_steps = lb->K; p.n_comp = 1; p.n_batches = 1; p.additive = lb->additive;
   p.sat = reinterpret_cast<unsigned long long*>(live_sat(lb));
   if (lb->gate != nullptr) { p.repair = 2; p.guard = lb->gate; }      // (bwd_kernel_hx3_safe returns at once while *gate == 0)
-  p.acts_out = acts; p.np = np; p.tr_ip = ip; p.tr_hp = hp; p.tr_op = op; p.net_rows = ip + 2 * (lb->depth + 1) * hp + 2 * op;
+  p.acts_out = trace + lay.acts_off(); p.np = lay.np; p.tr_ip = lay.ip; p.tr_hp = lay.hp; p.tr_op = lay.op; p.net_rows = (int32_t)lay.net_rows();
   p.bwd_tab = lb->bwd_tab_dev; p.bwd_goff = lb->bwd_goff_dev; p.trace_in = trace;
   p.g_z = g_z; p.g_ldj = g_ldj; p.g_x = g_x; p.grads = grads; p.gmax = gmax;
 #if defined(GBNF_STAMPS)
   p.dbg = g_stamp_buf;
 #endif
-  // the workgroups' parameter-gradient sums go to the slack rows behind the last operand region (their contents are of no
-  // consequence to wgrad_kernel): 4-wave workgroups at most => np / 64 * K * 128 <= 24 np floats of the 320 np there
-  p.partials = acts + (int64_t)lb->K * lb->nnets * p.net_rows * np;
+  // the workgroups' parameter-gradient sums go to the slack rows behind the last operand region (TrainLayout: they fit, asserted there)
+  p.partials = trace + lay.partials_off();
   if (range != nullptr) {
     p.k_begin = range->k_begin; p.k_end = range->k_end; p.state_in = range->state_in; p.state_out = range->state_out;
   }
   hipError_t e = lb->launch_bwd(p, 0u, s);
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "launch of %s failed: %s", lb->name_bwd, hipGetErrorString(e));
-  const int n_wg = (int)((np / 16 + lb->bwd_waves - 1) / lb->bwd_waves);
+  const int n_wg = (int)((lay.np / 16 + lb->bwd_waves - 1) / lb->bwd_waves);
   if (reduce_out != nullptr) {
     *reduce_out = LiveReduce{p.partials, n_wg, lb->K, lb->d, lb->bwd_goff_dev, 0u};
     return GBNF_OK;
@@ -2264,9 +2261,10 @@ int live_blob_words(const LiveBlob* lb, uint32_t* out_host, int64_t* n_words) {
   return GBNF_OK;
 }
 
-int live_blob_forward(LiveBlob* lb, const float* x, int64_t n, float* z, float* ldj, float* trace, float* acts, int64_t np,
-                      int ip, int hp, int op, void* stream, const LiveRange* range) {
+int live_blob_forward(LiveBlob* lb, const TrainLayout& lay, const float* x, float* z, float* ldj, float* trace, void* stream,
+                      const LiveRange* range) {
   hipStream_t s = (hipStream_t)stream;
+  const int64_t n = lay.n;
   if (range == nullptr || range->repack)
     live_blob_repack(lb, s, /*with_backward=*/true);      // (a traced forward call: the backward call follows on the same parameters)
   if (range != nullptr && range->bmean != nullptr)
@@ -2286,7 +2284,8 @@ int live_blob_forward(LiveBlob* lb, const float* x, int64_t n, float* z, float* 
   // once while it is 0, else walks the whole work list with the capped grid of a repair launch)
   if (lb->gate != nullptr) { p.repair = 2; p.guard = lb->gate; }
   p.seq = next_serial();
-  p.trace_out = trace; p.acts_out = acts; p.np = np; p.tr_ip = ip; p.tr_hp = hp; p.tr_op = op; p.net_rows = ip + 2 * (lb->depth + 1) * hp + 2 * op;
+  p.trace_out = trace; p.acts_out = trace + lay.acts_off(); p.np = lay.np; p.tr_ip = lay.ip; p.tr_hp = lay.hp; p.tr_op = lay.op;
+  p.net_rows = (int32_t)lay.net_rows();
   if (range != nullptr) {
     p.k_begin = range->k_begin; p.k_end = range->k_end; p.state_in = range->state_in; p.state_out = range->state_out;
     p.ldj_accumulate = range->ldj_accumulate;

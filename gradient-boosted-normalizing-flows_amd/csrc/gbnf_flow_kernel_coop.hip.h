@@ -809,13 +809,8 @@ static hipError_t coop_launch(FlowLaunch p, hipStream_t s) {
   const long long grid = (long long)p.n_tiles * p.n_comp * p.n_batches;
   if (grid > 0x7fffffffLL) return hipErrorInvalidValue;
   p.n_items = (int32_t)grid;
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)flow_kernel_coop<KIND, HT, OT, NT, ACTA, ACTB, WV>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  static DynamicLdsOptIn opt_in;
+  if (hipError_t e = opt_in({(const void*)flow_kernel_coop<KIND, HT, OT, NT, ACTA, ACTB, WV>}); e != hipSuccess) return e;
   hipLaunchKernelGGL((flow_kernel_coop<KIND, HT, OT, NT, ACTA, ACTB, WV>), dim3((unsigned)grid), dim3(64 * WV), lds, s, p);
   return hipGetLastError();
 }

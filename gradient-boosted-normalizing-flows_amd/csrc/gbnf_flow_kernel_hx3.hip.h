@@ -34,6 +34,7 @@
 #include <type_traits>
 
 #include "gbnf_flow_kernel.hip.h"
+#include "gbnf_internal.h"
 
 namespace gbnf {
 
@@ -1662,13 +1663,8 @@ static hipError_t hx3_launch_wv(FlowLaunch p, bool staggered, hipStream_t s) {
     static const int forced = [] { const char* e = getenv("GBNF_STAGGER"); return e ? atoi(e) : 0; }();
     p.stagger = forced;
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    hipError_t e = hipFuncSetAttribute((const void*)flow_kernel_hx3<KIND, HT, OT, ENT, ACTA, ACTB, PREC, WV, DEPTH, TRAIN>,
-                                       hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    if (e != hipSuccess) return e;
-    attr_set = true;
-  }
+  static DynamicLdsOptIn opt_in;
+  if (hipError_t e = opt_in({(const void*)flow_kernel_hx3<KIND, HT, OT, ENT, ACTA, ACTB, PREC, WV, DEPTH, TRAIN>}); e != hipSuccess) return e;
   hipLaunchKernelGGL((flow_kernel_hx3<KIND, HT, OT, ENT, ACTA, ACTB, PREC, WV, DEPTH, TRAIN>), dim3((unsigned)grid), dim3(64 * WV), lds, s, p);
   return hipGetLastError();
 }

@@ -7,6 +7,7 @@
 #include <type_traits>
 
 #include "gbnf_image_net.h"
+#include "gbnf_internal.h"
 
 namespace gbnf {
 
@@ -915,30 +916,20 @@ static hipError_t img_net_hx3_launch4(const NetLaunch& q0, int64_t n, hipStream_
   if constexpr (W == 8 && KH == 1) {
     // 6 / 7 chunks (18 .. 24 input channels: the third level of a 3 x 32 x 32 input, a 4 x 4 map in 8 x 8 storage -- never FULL)
     if (pk == 7) {
-      static bool attr7 = false;
-      if (!attr7) {
-        const hipError_t e = hipFuncSetAttribute((const void*)img_net_hx3_kernel<W, 7, EPI, OT3, false, KH>,
-                                                 hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-        if (e != hipSuccess) return e;
-        attr7 = true;
-      }
+      static gbnf::DynamicLdsOptIn opt_in7;
+      if (const hipError_t e = opt_in7({(const void*)img_net_hx3_kernel<W, 7, EPI, OT3, false, KH>}); e != hipSuccess) return e;
       hipLaunchKernelGGL((img_net_hx3_kernel<W, 7, EPI, OT3, false, KH>), grid, blk, lds, s, q);
       return hipGetLastError();
     }
   } else {
     if (pk == 7) return hipErrorInvalidValue;
   }
-  static bool attr_set = false;
-  if (!attr_set) {
-    const void* fns[6] = {(const void*)img_net_hx3_kernel<W, 2, EPI, OT3, false, KH>, (const void*)img_net_hx3_kernel<W, 4, EPI, OT3, false, KH>,
-                          (const void*)img_net_hx3_kernel<W, 5, EPI, OT3, false, KH>, (const void*)img_net_hx3_kernel<W, 2, EPI, OT3, true, KH>,
-                          (const void*)img_net_hx3_kernel<W, 4, EPI, OT3, true, KH>, (const void*)img_net_hx3_kernel<W, 5, EPI, OT3, true, KH>};
-    for (int k = 0; k < 6; ++k) {
-      const hipError_t e = hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-    }
-    attr_set = true;
-  }
+  static gbnf::DynamicLdsOptIn opt_in;
+  if (const hipError_t e = opt_in({(const void*)img_net_hx3_kernel<W, 2, EPI, OT3, false, KH>, (const void*)img_net_hx3_kernel<W, 4, EPI, OT3, false, KH>,
+                                   (const void*)img_net_hx3_kernel<W, 5, EPI, OT3, false, KH>, (const void*)img_net_hx3_kernel<W, 2, EPI, OT3, true, KH>,
+                                   (const void*)img_net_hx3_kernel<W, 4, EPI, OT3, true, KH>, (const void*)img_net_hx3_kernel<W, 5, EPI, OT3, true, KH>});
+      e != hipSuccess)
+    return e;
   if (full) {
     if (pk == 2) hipLaunchKernelGGL((img_net_hx3_kernel<W, 2, EPI, OT3, true, KH>), grid, blk, lds, s, q);
     else if (pk == 4) hipLaunchKernelGGL((img_net_hx3_kernel<W, 4, EPI, OT3, true, KH>), grid, blk, lds, s, q);

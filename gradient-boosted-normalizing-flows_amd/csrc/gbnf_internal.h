@@ -1,6 +1,8 @@
 // gbnf_internal.h -- shared between the translation units of libgbnf_hip.so (not part of the C ABI).
 #pragma once
+#include <hip/hip_runtime.h>
 #include <cstdint>
+#include <initializer_list>
 #include "../../include/gbnf.h"
 
 namespace gbnf {
@@ -24,6 +26,76 @@ constexpr int GBNF_ACT_PER_STEP = 3;
 // Steps whose tables the chained training sweeps keep in LDS: LDS_TABLE_STEPS of gbnf_flow_kernel.hip.h (gbnf_api.hip asserts the two
 // are equal), for the translation units that do not see the kernels
 constexpr int CHAIN_TABLE_STEPS = 24;
+// Per-device state of the library (the saturation counters, the dynamic-LDS opt-ins) is indexed by hipGetDevice up to here
+constexpr int MAX_DEVICES = 64;
+
+// The opt-in of a launcher's kernels to 160 KB of dynamic LDS, once per DEVICE: hipFuncSetAttribute applies to the current device's
+// function object, so a process that drives several GPUs needs it on each of them.  One `static DynamicLdsOptIn` per launcher (per
+// template instantiation); call it with the launch's device current.  A failed attribute call is returned and not remembered as done.
+struct DynamicLdsOptIn {
+  bool done[MAX_DEVICES] = {};
+  hipError_t operator()(std::initializer_list<const void*> kernels) {
+    // (a process that sees one device has nothing to look up: hipGetDevice per launch measured +0.2 us on a 52 us evaluation step)
+    static const int n_devices = [] { int n = 0; return hipGetDeviceCount(&n) == hipSuccess ? n : 0; }();
+    int dev = 0;
+    hipError_t e = n_devices == 1 ? hipSuccess : hipGetDevice(&dev);
+    if (e != hipSuccess) return e;
+    if (dev < 0 || dev >= MAX_DEVICES) return hipErrorInvalidDevice;
+    if (done[dev]) return hipSuccess;
+    for (const void* k : kernels) {
+      e = hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+      if (e != hipSuccess) return e;
+    }
+    done[dev] = true;
+    return hipSuccess;
+  }
+};
+
+// ---- the buffers of the training path: the caller's trace buffer and backward workspace ------------------------------
+constexpr int TR_MAX_NT = 2;            // 16-sample tiles per workgroup of the per-step kernels (they share every weight fragment a wave loads)
+constexpr int TR_WS_SLACK_ROWS = 320;   // workspace rows behind the last operand region: a block of wgrad_kernel reads up to 256 rows
+// The chained backward leaves its ActNorm / BatchNorm parameter sums per workgroup in those slack rows ([n_wg][K][2][64] floats, whose
+// contents are of no consequence to wgrad_kernel): at least 4 waves of 16 samples per workgroup => n_wg <= np / 64, K * 128 floats each
+static_assert(2 * CHAIN_TABLE_STEPS <= TR_WS_SLACK_ROWS, "the backward sweep's per-workgroup partial sums must fit the slack rows");
+
+// Where everything lives, for a flow of K steps on d features with `nnets` coupling nets per step (padded widths ip / hp / op, `n_hidden`
+// hidden layers per net) at a batch of n rows.  All rows are np floats long.
+//   trace buffer:  K normalised states | the parked state | operand regions [K][nnets][net_rows] | slack rows (partial sums)
+//                  (the last two only for a trainer with a live blob: its forward sweep fills them)
+//   workspace:     operand regions | slack rows | the gradient state parked between step launches
+//   one net's operand region: net input (ip) | hidden activations (n_hidden x hp) | hidden gradients (n_hidden x hp) |
+//                  output gradient (op) | the net's output as the forward sweep saved it (op)
+struct TrainLayout {
+  int K = 0, d = 0, nnets = 1, ip = 0, hp = 0, op = 0, n_hidden = 0;
+  int64_t n = 0, np = 0;
+  TrainLayout() = default;
+  TrainLayout(int K_, int d_, int nnets_, int ip_, int hp_, int op_, int n_hidden_, int64_t n_ = 0)
+      : K(K_), d(d_), nnets(nnets_), ip(ip_), hp(hp_), op(op_), n_hidden(n_hidden_), n(n_), np(padded(n_)) {}
+  TrainLayout at(int64_t rows) const { return TrainLayout(K, d, nnets, ip, hp, op, n_hidden, rows); }
+  // whole workgroups for every tile count of every kernel (32 rows)
+  static int64_t padded(int64_t rows) { return (rows + 16 * TR_MAX_NT - 1) / (16 * TR_MAX_NT) * (16 * TR_MAX_NT); }
+
+  // rows inside one net's operand region
+  int64_t input_row() const { return 0; }
+  int64_t hidden_row(int j) const { return (int64_t)ip + (int64_t)j * hp; }                       // activation of hidden layer j
+  int64_t hidden_grad_row(int j) const { return (int64_t)ip + (int64_t)(n_hidden + j) * hp; }     // its gradient
+  int64_t out_grad_row() const { return (int64_t)ip + 2LL * n_hidden * hp; }
+  int64_t net_rows() const { return out_grad_row() + 2LL * op; }
+  int64_t net_base_row(int step, int net) const { return ((int64_t)step * nnets + net) * net_rows(); }
+  int64_t operand_rows() const { return (int64_t)K * nnets * net_rows(); }
+  // the sweeps address one step's operand regions with 32-bit offsets
+  bool fits_32bit() const { return (int64_t)nnets * net_rows() * np < (1LL << 31); }
+
+  // float offsets inside the trace buffer
+  int64_t state_floats() const { return (int64_t)d * np; }
+  int64_t parked_off() const { return (int64_t)K * state_floats(); }           // the running state between step-range launches
+  int64_t acts_off() const { return ((int64_t)K + 1) * state_floats(); }
+  int64_t partials_off() const { return acts_off() + operand_rows() * np; }
+  int64_t trace_floats(bool live) const { return acts_off() + (live ? (operand_rows() + TR_WS_SLACK_ROWS) * np : 0); }
+  // float offset of the gradient state inside the backward workspace / its size
+  int64_t gstate_off() const { return (operand_rows() + TR_WS_SLACK_ROWS) * np; }
+  int64_t workspace_bytes() const { return (gstate_off() + state_floats()) * 4; }
+};
 
 // ---- the training path's forward sweep on the evaluation kernels (gbnf_api.hip; used by gbnf_train.hip) -------------
 // A "live blob": the packed hx3 (f16x3) parameter blob of ONE component whose parameters live in device tensors that an
@@ -52,7 +124,7 @@ struct LiveReduce {
   const int64_t* goff;        // [K][2] float offsets into the flat gradient buffer
   unsigned skip_steps;        // bit k: step k's two sums are NOT added (they were, by an earlier launch: batch-statistics BatchNorm)
 };
-// One step RANGE of a training sweep (round 4: BatchNorm on batch statistics; FlowLaunch::k_begin ..).  Forward: state_in / state_out =
+// One step RANGE of a training sweep (BatchNorm on batch statistics; FlowLaunch::k_begin ..).  Forward: state_in / state_out =
 // the state parked in slot layout [d][np] (null: x rows / the flow's z, ldj outputs); bmean / bvar: device (d,) batch statistics
 // of step k_begin's BatchNorm, or null (running statistics: what the re-pack derived); repack: re-derive the blob from the live
 // parameters first (the first range of a sweep).  Backward: state_in / state_out = the scaled gradient state behind step
@@ -66,17 +138,19 @@ struct LiveRange {
   const float* bmean;
   const float* bvar;
 };
-int live_blob_backward(LiveBlob* lb, int64_t n, const float* trace, float* acts, int64_t np, int ip, int hp, int op,
-                       const float* g_z, const float* g_ldj, float* g_x, float* grads, const unsigned* gmax, void* stream,
-                       LiveReduce* reduce_out = nullptr, const LiveRange* range = nullptr);
+// trace: the buffer the forward sweep filled (layout: TrainLayout at this batch); the states are read, the gradient-side operands of
+// the weight gradients written behind them
+int live_blob_backward(LiveBlob* lb, const TrainLayout& lay, float* trace, const float* g_z, const float* g_ldj, float* g_x,
+                       float* grads, const unsigned* gmax, void* stream, LiveReduce* reduce_out = nullptr,
+                       const LiveRange* range = nullptr);
 void live_blob_destroy(LiveBlob* lb);
 // The two halves of a repairing trainer (gbnf_trainer_create_mode, GBNF_MATH_DEFAULT).  sat: the f16x3 blob's launches count the waves
 // that met the fp16 range in this word (64-bit, trainer-owned) instead of the device's training counter.  gate: the bf16x6 blob's
 // launches (re-pack, both sweeps) return at once while this device word is 0 -- the re-run of a call that did not meet the range.
 void live_blob_set_repair(LiveBlob* lb, unsigned* sat, const unsigned* gate);
-// trace: [K][d][np] normalised states (slot layout); acts: the operand workspace (FlowLaunch::acts_out); np: padded rows
-int live_blob_forward(LiveBlob* lb, const float* x, int64_t n, float* z, float* ldj, float* trace, float* acts, int64_t np,
-                      int ip, int hp, int op, void* stream, const LiveRange* range = nullptr);
+// trace: [K][d][np] normalised states (slot layout), the parked state and the operand workspace (FlowLaunch::acts_out) of `lay`
+int live_blob_forward(LiveBlob* lb, const TrainLayout& lay, const float* x, float* z, float* ldj, float* trace, void* stream,
+                      const LiveRange* range = nullptr);
 // (tests) the blob as the device packer left it / size in words
 int live_blob_words(const LiveBlob* lb, uint32_t* out_host, int64_t* n_words);
 

@@ -52,13 +52,11 @@ using u32x4 = __attribute__((ext_vector_type(4))) unsigned;
 using u32x2 = __attribute__((ext_vector_type(2))) unsigned;
 using f16x8 = __attribute__((ext_vector_type(8))) _Float16;
 
-constexpr int TR_MAX_NT = 2;        // 16-sample tiles per workgroup (they share every weight fragment a wave loads)
 constexpr int TR_MAX_LAYERS = 6;    // Linear layers per coupling net (depth <= 2; a ResidualNet of 2 blocks has 6)
 constexpr int TR_MAX_IN = 32;       // coupling-net input / coupled-half width
 constexpr int TR_MAX_HIDDEN = 512;  // hidden width (32 output tiles = 16 tile pairs per layer)
 constexpr int TR_LDS_BYTES = 160 * 1024;
 constexpr int TR_CHAIN_MAX_STEPS = CHAIN_TABLE_STEPS;  // steps the chained sweeps keep tables for (gbnf_internal.h: = LDS_TABLE_STEPS of the kernels)
-constexpr int TR_WS_SLACK_ROWS = 320;   // workspace rows behind the last operand region: a block of wgrad_kernel reads up to 256 rows
 #ifndef GBNF_TR_WAVES
 #define GBNF_TR_WAVES 8
 #endif
@@ -1625,9 +1623,12 @@ __global__ void __launch_bounds__(64) prep_kernel(const PrepProblem* __restrict_
 
 using namespace gbnf;
 
+struct StepRange { int k0, k1; };     // steps [k0, k1)
+
 struct gbnf_trainer {
   int kind = 0, d = 0, K = 0, additive = 0, n_hidden = 0, hp = 0, ip = 0, op = 0, nnets = 1;
-  int64_t net_rows = 0, grad_floats = 0;
+  int64_t grad_floats = 0;
+  TrainLayout lay;                     // the trace buffer and the backward workspace of this geometry (lay.at(n): at a batch of n rows)
   size_t lds_fwd[TR_MAX_NT + 1] = {0, 0, 0}, lds_bwd[TR_MAX_NT + 1] = {0, 0, 0};   // dynamic LDS bytes by tiles per workgroup
   TrStep* steps_dev = nullptr;
   int* tail_dev = nullptr;
@@ -1643,10 +1644,13 @@ struct gbnf_trainer {
   float* bn_part_dev = nullptr;        // [2][64 slots][BN_CHUNKS]: chunk sums of the batch statistics (bn_stats_part_kernel)
   int batch_stats = 0;                 // BatchNorm on batch statistics (the reference's train() mode)
   std::vector<int> has_norm;           // per step
+  // The step ranges of a batch-statistics sweep: a step with a norm needs the statistics of the whole batch in front of it, so a range
+  // starts at step 0 and at every step that has one.  `single_steps`: ranges of one step each, the walk of the per-step kernels.
+  std::vector<StepRange> ranges, single_steps;
   std::vector<char> stats_bound;       // per step: bmean / bvar bound by the caller
   std::vector<float*> bmean_ptr, bvar_ptr;   // per step: the caller's device buffers (host copies of TrStep::bmean / bvar)
-  LiveBlob* live = nullptr;            // round 3: the forward sweep on flow_kernel_hx3<TRAIN> (depth-1 TanhNet / ReLUNet), else null
-  mutable int last_fwd_ranges = 0, last_bwd_ranges = 0;     // (tests) launches of the register-chained kernels by the last forward / backward call; 0 = the round-1 kernels ran
+  LiveBlob* live = nullptr;            // the sweeps on flow_kernel_hx3<TRAIN> / bwd_kernel_hx3 (TanhNet / ReLUNet / ResidualNet of a compiled width), else null
+  mutable int last_fwd_ranges = 0, last_bwd_ranges = 0;     // (tests) launches of the register-chained kernels by the last forward / backward call; 0 = the per-step kernels ran
   // GBNF_MATH_BF16X6 (gbnf_trainer_create_mode): `live` is the bf16x6 blob, every sweep and the weight gradients have the range of
   // f32, and the per-step kernels of this file never run -- a call they would have served runs the chained pair on the buffer below
   int math = GBNF_MATH_F16X3;
@@ -1654,18 +1658,20 @@ struct gbnf_trainer {
   int wg_blocks_safe = 0;
   mutable float* own_dev = nullptr;         // trace + operand workspace + ldj of the untraced entries of a range-safe trainer
   mutable int64_t own_floats = 0;
-  // GBNF_MATH_DEFAULT, the repairing trainer: two whole trainers on the same parameter tensors.  A call runs rep_f (f16x3), whose
-  // launches count the waves that met the fp16 range in rep_dev[0..1] instead of the device's training counter; repair_decide_kernel
-  // turns that into this call's decision word rep_dev[2]; rep_s (bf16x6) follows in stream order with every launch gated on that word.
-  // rep_dev: [0..1] range events of the call in flight (64-bit), [2] decision, [3] the last forward call was re-run, [4] re-run calls
-  gbnf_trainer* rep_f = nullptr;
-  gbnf_trainer* rep_s = nullptr;
-  unsigned* rep_dev = nullptr;
-  unsigned* sat_override = nullptr;         // (rep_f) = rep_dev
-  const unsigned* gate = nullptr;           // (rep_s) = rep_dev + 2
-  mutable float* rep_scratch = nullptr;     // backward: [2][grad_floats] zeroed gradient buffers + [2][n d] g_x of the two forms
-  mutable int64_t rep_scratch_floats = 0;
-  mutable const float* last_fwd_trace = nullptr;      // the trace buffer rep_dev[3] speaks about (the repaired flag is keyed to it)
+  // The two halves of a repairing pair point into their owner's device words (Repair::dev below)
+  unsigned* sat_override = nullptr;         // (the f16x3 half) = dev: its launches count range events here, not in the device's training counter
+  const unsigned* gate = nullptr;           // (the bf16x6 half) = dev + 2: its launches return at once while this word is 0
+  // GBNF_MATH_DEFAULT, the repairing trainer: two whole trainers on the same parameter tensors; only their owner uses this.  A call runs
+  // `f` (f16x3), whose launches count the waves that met the fp16 range in dev[0..1]; repair_decide_kernel turns that into this call's
+  // decision word dev[2]; `s` (bf16x6) follows in stream order with every launch gated on that word.
+  struct Repair {
+    gbnf_trainer* f = nullptr;
+    gbnf_trainer* s = nullptr;
+    unsigned* dev = nullptr;                  // [0..1] range events of the call in flight (64-bit), [2] decision, [3] the last forward call was re-run, [4] re-run calls
+    mutable float* scratch = nullptr;         // backward: [2][grad_floats] zeroed gradient buffers + [2][n d] g_x of the two forms
+    mutable int64_t scratch_floats = 0;
+    mutable const float* last_fwd_trace = nullptr;      // the trace buffer dev[3] speaks about (the repaired flag is keyed to it)
+  } rep;
 };
 
 namespace gbnf {
@@ -1696,24 +1702,15 @@ __global__ void __launch_bounds__(256) repair_commit_kernel(const unsigned* __re
 }  // namespace gbnf
 
 
-// tuning / test knob: GBNF_TRAIN_PATH=old keeps the round-1 kernels for every call
-static bool tr_fast_path_enabled() {
-  static const bool on = [] { const char* e = getenv("GBNF_TRAIN_PATH"); return !(e && !strcmp(e, "old")); }();
-  return on;
-}
-
 static int ceil16(int v) { return (v + 15) / 16 * 16; }
-static int64_t tr_padded(int64_t n) { return (n + 16 * TR_MAX_NT - 1) / (16 * TR_MAX_NT) * (16 * TR_MAX_NT); }   // np: whole workgroups for every NT
 
 // 16-sample tiles per workgroup.  Two tiles halve the weight-fragment traffic per sample (the bound of these kernels,
 // DESIGN.md section 4.7) at twice the LDS per workgroup: worth it once there are enough workgroups to cover the chip.
 static int pick_nt(const gbnf_trainer* t, int64_t np, int mode) {
-  static const int forced = [] { const char* e = getenv("GBNF_TRAIN_NT"); return e ? atoi(e) : 0; }();
   const size_t* lds = mode == 0 ? t->lds_fwd : t->lds_bwd;
   // measured (MINIBOONE Glow): one tile per workgroup is the faster of the two up to 1024 samples (a lone workgroup's
   // pass through the layers is the whole latency there), two tiles from 2048 on even while they leave CUs idle
   int nt = np / 16 > 96 ? TR_MAX_NT : 1;
-  if (forced >= 1 && forced <= TR_MAX_NT) nt = forced;
   while (nt > 1 && lds[nt] > (size_t)TR_LDS_BYTES) --nt;
   return nt;
 }
@@ -1756,17 +1753,17 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
     gbnf_trainer* t = new gbnf_trainer();
     t->math = GBNF_MATH_DEFAULT;
     t->kind = f->kind; t->d = f->d; t->K = f->K; t->grad_floats = f->grad_floats;
-    t->rep_f = f; t->rep_s = sf;
-    hipError_t e = hipMalloc((void**)&t->rep_dev, 8 * sizeof(unsigned));
-    if (e == hipSuccess) e = hipMemset(t->rep_dev, 0, 8 * sizeof(unsigned));
+    t->rep.f = f; t->rep.s = sf;
+    hipError_t e = hipMalloc((void**)&t->rep.dev, 8 * sizeof(unsigned));
+    if (e == hipSuccess) e = hipMemset(t->rep.dev, 0, 8 * sizeof(unsigned));
     if (e != hipSuccess) {
       gbnf_trainer_destroy(t);
       return fail(GBNF_ERR_HIP, "gbnf_trainer_create_mode: %s", hipGetErrorString(e));
     }
-    f->sat_override = t->rep_dev;
-    live_blob_set_repair(f->live, t->rep_dev, nullptr);
-    sf->gate = t->rep_dev + 2;
-    live_blob_set_repair(sf->live, nullptr, t->rep_dev + 2);
+    f->sat_override = t->rep.dev;
+    live_blob_set_repair(f->live, t->rep.dev, nullptr);
+    sf->gate = t->rep.dev + 2;
+    live_blob_set_repair(sf->live, nullptr, t->rep.dev + 2);
     *out = t;
     return GBNF_OK;
   }
@@ -1794,10 +1791,9 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
   t->residual = residual ? 1 : 0;
   t->n_hidden = nl - 1;
   t->hp = ceil16(h);
-  // (round 5) a width no TRAIN kernel variant is compiled for trains on the next wider one: the operand rows follow the VARIANT's
+  // a width no TRAIN kernel variant is compiled for trains on the next wider one: the operand rows follow the VARIANT's
   // hidden tiles (the extra units have zero weights: their activations, gradients and operand rows are zeros)
-  // (a range-safe trainer has the chained kernels only: the GBNF_TRAIN_PATH knob does not apply to it)
-  const bool chained_shape = (residual ? (nl == 4 || nl == 6) : (nl >= 2 && nl <= 4)) && (safe || tr_fast_path_enabled());
+  const bool chained_shape = residual ? (nl == 4 || nl == 6) : (nl >= 2 && nl <= 4);
   int hp_wide = 0;
   if (chained_shape) {
     const int rows = live_blob_train_rows(desc, safe ? 1 : 0);
@@ -1817,9 +1813,6 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
   }
   t->ip = ceil16(d2);
   t->op = ceil16(glow && !additive ? 2 * d2 : d2);
-  // operand rows per (step, net): net input | hidden activations | hidden gradients | output gradient | (round 3) the net's
-  // output as the forward sweep saved it for the backward sweep
-  t->net_rows = (int64_t)t->ip + 2LL * t->n_hidden * t->hp + 2LL * t->op;
   t->xw = (d2 + 31) / 32 * 32; t->ow = ((glow && !additive ? 2 * d2 : d2) + 31) / 32 * 32;
   if (t->hp > TR_MAX_HIDDEN) {
     delete t;
@@ -1842,7 +1835,8 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
   if (hp_wide) size_lds(hp_wide);
   // (a range-safe trainer never runs the per-step kernels: their LDS does not bound it)
   if (!hp_wide || (!safe && t->lds_bwd[1] > (size_t)TR_LDS_BYTES)) size_lds(hp_own);
-  t->net_rows = (int64_t)t->ip + 2LL * t->n_hidden * t->hp + 2LL * t->op;
+  t->lay = TrainLayout(K, d, t->nnets, t->ip, t->hp, t->op, t->n_hidden);      // (the operand rows follow the width settled above)
+  const TrainLayout& lay = t->lay;
   if (!safe && t->lds_bwd[1] > (size_t)TR_LDS_BYTES) {
     const size_t need = t->lds_bwd[1];
     delete t;
@@ -1893,13 +1887,16 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
     }
     t->has_norm.push_back(st.has_norm);
     t->stats_bound.push_back(0);
+    if (s == 0 || st.has_norm) t->ranges.push_back(StepRange{s, s + 1});
+    else t->ranges.back().k1 = s + 1;
+    t->single_steps.push_back(StepRange{s, s + 1});
     st.in_f = in_f; st.out_f = out_f;
     for (int j = 0; j < in_f; ++j) st.in_slot[j] = sigma[j];
     for (int j = 0; j < out_f; ++j) st.out_slot[j] = sigma[in_f + j];
     for (int q = 0; q < t->nnets; ++q) {
       TrNet& net = st.net[q];
       net.n_layers = nl; net.act = residual ? GBNF_ACT_RELU : nets[q]->activation;
-      const int64_t base_row = ((int64_t)s * t->nnets + q) * t->net_rows;
+      const int64_t base_row = lay.net_base_row(s, q);
       for (int l = 0; l < nl; ++l) {
         const gbnf_linear& lin = nets[q]->layers[l];
         TrLayer& L = net.layer[l];
@@ -1933,9 +1930,8 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
         WgProblem P{};
         P.M = L.rows; P.N = L.cols;
         // gradient-side operand: D of this layer's output; activation-side operand: this layer's input
-        P.d_row = base_row + (l == nl - 1 ? (int64_t)t->ip + 2LL * t->n_hidden * t->hp
-                                          : (int64_t)t->ip + (int64_t)t->n_hidden * t->hp + (int64_t)l * t->hp);
-        P.a_row = base_row + (l == 0 ? 0 : (int64_t)t->ip + (int64_t)(l - 1) * t->hp);
+        P.d_row = base_row + (last ? lay.out_grad_row() : lay.hidden_grad_row(l));
+        P.a_row = base_row + (first ? lay.input_row() : lay.hidden_row(l - 1));
         P.c_off = L.gW; P.b_off = L.gb;
         P.d_rows = (l == nl - 1) ? t->op : t->hp;
         P.a_rows = (l == 0) ? t->ip : t->hp;
@@ -2039,10 +2035,10 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
 
 int gbnf_trainer_destroy(gbnf_trainer* t) {
   if (t == nullptr) return GBNF_OK;
-  if (t->rep_f) gbnf_trainer_destroy(t->rep_f);
-  if (t->rep_s) gbnf_trainer_destroy(t->rep_s);
-  if (t->rep_dev) (void)hipFree(t->rep_dev);
-  if (t->rep_scratch) (void)hipFree(t->rep_scratch);
+  if (t->rep.f) gbnf_trainer_destroy(t->rep.f);
+  if (t->rep.s) gbnf_trainer_destroy(t->rep.s);
+  if (t->rep.dev) (void)hipFree(t->rep.dev);
+  if (t->rep.scratch) (void)hipFree(t->rep.scratch);
   if (t->steps_dev) (void)hipFree(t->steps_dev);
   if (t->tail_dev) (void)hipFree(t->tail_dev);
   if (t->probs_dev) (void)hipFree(t->probs_dev);
@@ -2066,17 +2062,14 @@ int gbnf_trainer_grad_floats(const gbnf_trainer* t, int64_t* n_floats) {
 
 int gbnf_trainer_workspace_bytes(const gbnf_trainer* t, int64_t n, int64_t* bytes) {
   if (!t || !bytes || n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_workspace_bytes: bad argument");
-  if (t->rep_f) {          // both forms use the caller's workspace, one after the other
+  if (t->rep.f) {          // both forms use the caller's workspace, one after the other
     int64_t a = 0, b = 0;
-    gbnf_trainer_workspace_bytes(t->rep_f, n, &a);
-    gbnf_trainer_workspace_bytes(t->rep_s, n, &b);
+    gbnf_trainer_workspace_bytes(t->rep.f, n, &a);
+    gbnf_trainer_workspace_bytes(t->rep.s, n, &b);
     *bytes = a > b ? a : b;
     return GBNF_OK;
   }
-  const int64_t np = tr_padded(n);
-  // operand regions + 256 slack rows (a 256-row block of wgrad_kernel may run past the last region)
-  // ... + the gradient state of step-by-step launches (batch-statistics BatchNorm)
-  *bytes = (((int64_t)t->K * t->nnets * t->net_rows + TR_WS_SLACK_ROWS) * np + (int64_t)t->d * np) * 4;
+  *bytes = t->lay.at(n).workspace_bytes();
   return GBNF_OK;
 }
 
@@ -2085,19 +2078,20 @@ static unsigned long long* g_train_stamp_buf = nullptr;
 extern "C" void gbnf_debug_set_train_stamp_buffer(unsigned long long* p) { g_train_stamp_buf = p; }
 #endif
 
-static void fill_launch(const gbnf_trainer* t, TrainLaunch& p, const float* x, int64_t n) {
+static void fill_launch(const gbnf_trainer* t, const TrainLayout& lay, TrainLaunch& p, const float* x) {
   std::memset(&p, 0, sizeof(p));
 #ifdef GBNF_TRAIN_STAMPS
   p.dbg = g_train_stamp_buf;
 #endif
   p.steps = t->steps_dev; p.tail = t->tail_dev; p.x = x;
   p.sat = t->sat_override != nullptr ? t->sat_override : training_saturation_counter();
-  p.n = n; p.np = tr_padded(n);
+  p.n = lay.n; p.np = lay.np;
   p.d = t->d; p.K = t->K; p.kind = t->kind; p.additive = t->additive;
   p.residual = t->residual;
-  p.n_hidden = t->n_hidden; p.hp = t->hp; p.ip = t->ip; p.op = t->op; p.net_rows = t->net_rows;
+  p.n_hidden = t->n_hidden; p.hp = t->hp; p.ip = t->ip; p.op = t->op; p.net_rows = lay.net_rows();
   p.hw = t->hw; p.xw = t->xw; p.ow = t->ow; p.frag = t->frag_dev;
   p.k_begin = 0; p.k_end = t->K;
+  p.batch_stats = t->batch_stats;
 }
 
 // batch mean / unbiased variance of step k's input state (slot layout) into the caller's buffers
@@ -2124,9 +2118,9 @@ static bool needs_step_launches(const gbnf_trainer* t) {
 
 int gbnf_trainer_set_batch_stats(gbnf_trainer* t, int32_t on) {
   if (!t) return fail(GBNF_ERR_INVALID, "gbnf_trainer_set_batch_stats: trainer is null");
-  if (t->rep_f) {
-    int rc = gbnf_trainer_set_batch_stats(t->rep_f, on);
-    if (rc == GBNF_OK) rc = gbnf_trainer_set_batch_stats(t->rep_s, on);
+  if (t->rep.f) {
+    int rc = gbnf_trainer_set_batch_stats(t->rep.f, on);
+    if (rc == GBNF_OK) rc = gbnf_trainer_set_batch_stats(t->rep.s, on);
     if (rc == GBNF_OK) t->batch_stats = on ? 1 : 0;
     return rc;
   }
@@ -2144,9 +2138,9 @@ int gbnf_trainer_set_batch_stats(gbnf_trainer* t, int32_t on) {
 int gbnf_trainer_bind_batch_stats(gbnf_trainer* t, int32_t step, float* mean_dev, float* var_dev) {
   if (!t || step < 0 || step >= t->K || !mean_dev || !var_dev)
     return fail(GBNF_ERR_INVALID, "gbnf_trainer_bind_batch_stats: bad argument");
-  if (t->rep_f) {
-    const int rc = gbnf_trainer_bind_batch_stats(t->rep_f, step, mean_dev, var_dev);
-    return rc ? rc : gbnf_trainer_bind_batch_stats(t->rep_s, step, mean_dev, var_dev);
+  if (t->rep.f) {
+    const int rc = gbnf_trainer_bind_batch_stats(t->rep.f, step, mean_dev, var_dev);
+    return rc ? rc : gbnf_trainer_bind_batch_stats(t->rep.s, step, mean_dev, var_dev);
   }
   if (!t->has_norm[step] || t->kind != GBNF_KIND_REALNVP)
     return fail(GBNF_ERR_INVALID, "gbnf_trainer_bind_batch_stats: step %d has no BatchNorm", step);
@@ -2163,151 +2157,342 @@ int gbnf_trainer_bind_batch_stats(gbnf_trainer* t, int32_t step, float* mean_dev
 
 int gbnf_trainer_trace_floats(const gbnf_trainer* t, int64_t n, int64_t* n_floats) {
   if (!t || !n_floats || n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_trace_floats: bad argument");
-  if (t->rep_f) {          // the two forms may run variants of different widths: the larger of their layouts
+  if (t->rep.f) {          // the two forms may run variants of different widths: the larger of their layouts
     int64_t a = 0, b = 0;
-    gbnf_trainer_trace_floats(t->rep_f, n, &a);
-    gbnf_trainer_trace_floats(t->rep_s, n, &b);
+    gbnf_trainer_trace_floats(t->rep.f, n, &a);
+    gbnf_trainer_trace_floats(t->rep.s, n, &b);
     *n_floats = a > b ? a : b;
     return GBNF_OK;
   }
-  *n_floats = ((int64_t)t->K + 1) * t->d * tr_padded(n);     // K normalised states + the running state
-  if (t->live)       // + the operand workspace the forward sweep fills (and the slack rows wgrad_kernel may read behind it)
-    *n_floats += ((int64_t)t->K * t->nnets * t->net_rows + TR_WS_SLACK_ROWS) * tr_padded(n);
+  *n_floats = t->lay.at(n).trace_floats(t->live != nullptr);
   return GBNF_OK;
 }
 
 }  // extern "C"
 
-// A range-safe trainer's own trace buffer (gbnf_trainer_trace_floats) + np floats of ldj behind it, for the calls that come without
+// A range-safe trainer's own trace buffer (TrainLayout::trace_floats) + np floats of ldj behind it, for the calls that come without
 // a trace: grown on demand and kept (a growing call synchronises the device once).
-static int own_buffer(const gbnf_trainer* t, int64_t n, float** trace, float** ldj) {
-  int64_t need = 0;
-  gbnf_trainer_trace_floats(t, n, &need);
-  const int64_t np = tr_padded(n);
-  if (t->own_floats < need + np) {
+static int own_buffer(const gbnf_trainer* t, const TrainLayout& lay, float** trace, float** ldj) {
+  const int64_t need = lay.trace_floats(t->live != nullptr);
+  if (t->own_floats < need + lay.np) {
     if (t->own_dev) (void)hipFree(t->own_dev);
     t->own_dev = nullptr; t->own_floats = 0;
-    const hipError_t e = hipMalloc((void**)&t->own_dev, (size_t)(need + np) * 4);
-    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer: %lld bytes of trace scratch: %s", (long long)((need + np) * 4), hipGetErrorString(e));
-    t->own_floats = need + np;
+    const hipError_t e = hipMalloc((void**)&t->own_dev, (size_t)(need + lay.np) * 4);
+    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer: %lld bytes of trace scratch: %s", (long long)((need + lay.np) * 4), hipGetErrorString(e));
+    t->own_floats = need + lay.np;
   }
   *trace = t->own_dev;
   *ldj = t->own_dev + need;
   return GBNF_OK;
 }
 
-extern "C" {
+// ---- which kernels serve a call --------------------------------------------------------------------------------------
+// The register-chained sweeps (live blob), or the first reason a call cannot run on them: the per-step kernels of this file serve
+// it then -- or, for a range-safe trainer, which has none, the call is refused with that reason (refuse_range_safe).
+enum class Chain { Yes, NoSweep, NoTrace, Offsets32, NoLdj, OneRow, StatsUnbound };
 
-int gbnf_trainer_forward(const gbnf_trainer* t, const float* x, int64_t n, float* z, float* ldj, float* trace,
-                         void* stream) {
-  if (!t) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: trainer is null");
-  if (n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: n < 0");
-  if (n == 0) return GBNF_OK;
-  if (!x) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: x is null");
-  if (t->rep_f) {
-    // f16x3 as ever; then, in stream order, the decision on the device and the bf16x6 form of the same call, which overwrites z, ldj,
-    // the trace and the operand workspace if this call met the range and returns at once if not.  No host read, no synchronisation.
-    hipStream_t s = (hipStream_t)stream;
-    int rc = gbnf_trainer_forward(t->rep_f, x, n, z, ldj, trace, stream);
-    if (rc) return rc;
-    hipLaunchKernelGGL(repair_decide_kernel, dim3(1), dim3(1), 0, s, t->rep_dev, 0, saturation_counter(), 1);
-    rc = gbnf_trainer_forward(t->rep_s, x, n, z, ldj, trace, stream);
-    if (rc) return rc;
-    t->last_fwd_trace = trace;
-    t->last_fwd_ranges = t->rep_f->last_fwd_ranges;
-    return GBNF_OK;
+static Chain chained_or_why(const gbnf_trainer* t, const TrainLayout& lay, bool forward, const float* trace, const float* ldj) {
+  if (forward ? t->live == nullptr : !live_blob_has_backward(t->live)) return Chain::NoSweep;
+  if (trace == nullptr) return Chain::NoTrace;        // the sweeps save their operands behind the trace
+  if (!lay.fits_32bit()) return Chain::Offsets32;
+  if (needs_step_launches(t)) {
+    if (forward && ldj == nullptr) return Chain::NoLdj;
+    if (forward && lay.n < 2) return Chain::OneRow;
+    if ((int)t->bmean_ptr.size() != t->K) return Chain::StatsUnbound;
   }
-  const bool safe = t->math == GBNF_MATH_BF16X6;
-  if (safe) {          // without a trace: the same sweep into the trainer's own buffer
-    float* own_trace = nullptr;
-    float* own_ldj = nullptr;
-    if (trace == nullptr || (ldj == nullptr && needs_step_launches(t))) {
-      const int rc = own_buffer(t, n, &own_trace, &own_ldj);
-      if (rc) return rc;
+  return Chain::Yes;
+}
+
+// (its own buffers give a range-safe trainer a live blob, a trace and ldj: what is left is the batch and the bound statistics)
+static int refuse_range_safe(const char* fn, Chain why, int64_t n) {
+  if (why == Chain::Offsets32)
+    return fail(GBNF_ERR_UNSUPPORTED, "%s: %lld rows exceed the 32-bit operand offsets of the bf16x6 sweep", fn, (long long)n);
+  if (why == Chain::OneRow) return fail(GBNF_ERR_INVALID, "%s: batch statistics need n >= 2", fn);
+  return fail(GBNF_ERR_INVALID, "%s: batch-statistics mode needs every BatchNorm step's buffers (gbnf_trainer_bind_batch_stats)", fn);
+}
+
+// ---- BatchNorm on batch statistics (the reference's train() mode, models/layers.py:338-346): one launch per step range ---------------
+// Forward: a sweep is cut in front of every BatchNorm step -- its statistics need the whole batch: one column reduction of the parked
+// state (bn_stats_kernel) -- and the state is parked in HBM in slot layout between the launches (TrainLayout::parked_off: the last
+// d * np floats of the states).  sweep(range): the launch of one range; first range to last.
+template <class Sweep>
+static int bn_forward_walk(const gbnf_trainer* t, const std::vector<StepRange>& ranges, const TrainLayout& lay, const float* x, float* state,
+                           hipStream_t s, Sweep&& sweep) {
+  hipLaunchKernelGGL(rows_to_slots_kernel, dim3((unsigned)((lay.np + 255) / 256)), dim3(256), 0, s, x, state, lay.n, lay.np, t->d, t->gate);
+  for (const StepRange& r : ranges) {
+    if (t->has_norm[r.k0]) launch_bn_stats(t, r.k0, state, lay.n, lay.np, s);
+    if (const int rc = sweep(r)) return rc;
+  }
+  return GBNF_OK;
+}
+
+// Backward, the mirror image: last range first.  Behind a range that starts with a BatchNorm step the parked gradient state is corrected
+// for the dependence of the batch statistics on every sample (bn_bwd_fix_kernel: its two batch sums are that step's d/d beta and
+// d/d log_gamma, which sweep(range) must have added into `grads`); the last launch's state goes out as g_x rows.
+template <class Sweep>
+static int bn_backward_walk(const gbnf_trainer* t, const std::vector<StepRange>& ranges, const TrainLayout& lay, const float* trace,
+                            const float* grads, float* gstate, float* g_x, hipStream_t s, Sweep&& sweep) {
+  for (auto r = ranges.rbegin(); r != ranges.rend(); ++r) {
+    if (const int rc = sweep(*r)) return rc;
+    if (t->has_norm[r->k0]) {
+      const dim3 fg((unsigned)((lay.n + 255) / 256), (unsigned)t->d);
+      hipLaunchKernelGGL(bn_bwd_fix_kernel, fg, dim3(256), 0, s, (const TrStep*)t->steps_dev, r->k0, t->d, trace, grads, gstate, lay.n, lay.np,
+                         (const unsigned*)t->gmax_dev);
     }
-    if (trace == nullptr) trace = own_trace;
-    if (ldj == nullptr && needs_step_launches(t)) ldj = own_ldj;
   }
-  TrainLaunch p;
-  fill_launch(t, p, x, n);
-  p.z_out = z; p.ldj_out = ldj; p.trace_out = trace;
-  p.batch_stats = t->batch_stats;
-  hipStream_t s = (hipStream_t)stream;
-  if (t->live != nullptr && trace != nullptr && (int64_t)t->nnets * t->net_rows * p.np < (1LL << 31) &&
-      (!needs_step_launches(t) || (ldj != nullptr && n >= 2 && (int)t->bmean_ptr.size() == t->K))) {
-    // round 3: the forward sweep on the evaluation kernel (register-chained, weights staged once per workgroup): re-pack
-    // the live parameters on the device, then x -> z, ldj + trace + the activation-side operands of the weight gradients
-    float* acts = trace + ((int64_t)t->K + 1) * t->d * p.np;
-    t->last_fwd_ranges = 1;
-    if (!needs_step_launches(t)) {
-      const int rc = live_blob_forward(t->live, x, n, z, ldj, trace, acts, p.np, t->ip, t->hp, t->op, stream);
-      if (rc) return rc;
-    } else {
-      t->last_fwd_ranges = 0;
-      // round 4: BatchNorm on batch statistics (the reference's train() mode, models/layers.py:338-346) on the same kernels: the
-      // sweep is cut in front of every BatchNorm step -- its statistics need the whole batch: one column reduction of the parked
-      // state (bn_stats_kernel), the step's table entries re-derived from them (live_norm_step_kernel) -- and the state is parked
-      // in HBM in slot layout between the launches (the last d * np floats of the trace buffer)
-      float* state = trace + (int64_t)t->K * t->d * p.np;
-      const unsigned nb = (unsigned)((p.np + 255) / 256);
-      hipLaunchKernelGGL(rows_to_slots_kernel, dim3(nb), dim3(256), 0, s, x, state, n, p.np, t->d, t->gate);
-      bool first = true;
-      for (int k0 = 0; k0 < t->K;) {
-        int k1 = k0 + 1;
-        while (k1 < t->K && !t->has_norm[k1]) ++k1;
-        LiveRange rg{k0, k1, state, k1 < t->K ? state : nullptr, k0 > 0 ? 1 : 0, first, nullptr, nullptr};
-        if (t->has_norm[k0]) {
-          launch_bn_stats(t, k0, state, n, p.np, s);
-          rg.bmean = t->bmean_ptr[k0]; rg.bvar = t->bvar_ptr[k0];
-        }
-        const int rc = live_blob_forward(t->live, x, n, z, ldj, trace, acts, p.np, t->ip, t->hp, t->op, stream, &rg);
-        if (rc) return rc;
-        ++t->last_fwd_ranges;
-        first = false;
-        k0 = k1;
-      }
-    }
-    // without a matching backward variant the backward kernels of this file run, on prep_kernel's fragments (valid while
-    // the parameters are what they are now: the trace contract)
-    if (!live_blob_has_backward(t->live))
-      hipLaunchKernelGGL(prep_kernel, dim3((unsigned)t->prep_blocks), dim3(64), 0, s, (const PrepProblem*)t->prep_dev, t->n_prep, t->frag_dev);
-    const hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_forward launch: %s", hipGetErrorString(e2));
-    return GBNF_OK;
-  }
-  if (safe) {          // no per-step kernel ever runs for a range-safe trainer: say why the sweep cannot
-    if ((int64_t)t->nnets * t->net_rows * p.np >= (1LL << 31))
-      return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_forward: %lld rows exceed the 32-bit operand offsets of the bf16x6 sweep", (long long)n);
-    if (n < 2) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: batch statistics need n >= 2");
-    return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: batch-statistics mode needs every BatchNorm step's buffers (gbnf_trainer_bind_batch_stats)");
-  }
-  // the parameters may have changed since the last call: split them into this call's MFMA fragments
-  t->last_fwd_ranges = 0;
+  if (g_x != nullptr)
+    hipLaunchKernelGGL(slots_to_rows_kernel, dim3((unsigned)((lay.n + 255) / 256)), dim3(256), 0, s, (const float*)gstate, g_x, lay.n, lay.np, t->d,
+                       (const unsigned*)t->gmax_dev);
+  return GBNF_OK;
+}
+
+static void launch_prep(const gbnf_trainer* t, hipStream_t s) {
   hipLaunchKernelGGL(prep_kernel, dim3((unsigned)t->prep_blocks), dim3(64), 0, s, (const PrepProblem*)t->prep_dev, t->n_prep, t->frag_dev);
+}
+
+// samples per block of a weight-gradient launch: the largest power of two in [lo, hi] that still leaves `min_blocks` blocks
+static int wgrad_chunk(int blocks, int64_t np, int lo, int hi, int min_blocks) {
+  int chunk = lo;
+  while (chunk < hi && (int64_t)blocks * (np / (2 * chunk)) >= min_blocks) chunk *= 2;
+  return chunk;
+}
+
+// ---- forward ---------------------------------------------------------------------------------------------------------
+// f16x3 as ever; then, in stream order, the decision on the device and the bf16x6 form of the same call, which overwrites z, ldj,
+// the trace and the operand workspace if this call met the range and returns at once if not.  No host read, no synchronisation.
+static int forward_repairing(const gbnf_trainer* t, const float* x, int64_t n, float* z, float* ldj, float* trace, hipStream_t s) {
+  int rc = gbnf_trainer_forward(t->rep.f, x, n, z, ldj, trace, s);
+  if (rc) return rc;
+  hipLaunchKernelGGL(repair_decide_kernel, dim3(1), dim3(1), 0, s, t->rep.dev, 0, saturation_counter(), 1);
+  rc = gbnf_trainer_forward(t->rep.s, x, n, z, ldj, trace, s);
+  if (rc) return rc;
+  t->rep.last_fwd_trace = trace;
+  t->last_fwd_ranges = t->rep.f->last_fwd_ranges;
+  return GBNF_OK;
+}
+
+// The forward sweep on the evaluation kernel (register-chained, weights staged once per workgroup): re-pack the live parameters on the
+// device, then x -> z, ldj + trace + the activation-side operands of the weight gradients
+static int forward_chained(const gbnf_trainer* t, const TrainLayout& lay, const float* x, float* z, float* ldj, float* trace, hipStream_t s) {
+  t->last_fwd_ranges = 1;
+  if (!needs_step_launches(t)) {
+    const int rc = live_blob_forward(t->live, lay, x, z, ldj, trace, s);
+    if (rc) return rc;
+  } else {
+    // a range's BatchNorm table entries are re-derived from its batch statistics (live_norm_step_kernel)
+    t->last_fwd_ranges = 0;
+    float* state = trace + lay.parked_off();
+    const int rc = bn_forward_walk(t, t->ranges, lay, x, state, s, [&](const StepRange& r) -> int {
+      const bool norm = t->has_norm[r.k0] != 0;
+      LiveRange rg{r.k0, r.k1, state, r.k1 < t->K ? state : nullptr, r.k0 > 0 ? 1 : 0, /*repack=*/r.k0 == 0,
+                   norm ? t->bmean_ptr[r.k0] : nullptr, norm ? t->bvar_ptr[r.k0] : nullptr};
+      const int rc2 = live_blob_forward(t->live, lay, x, z, ldj, trace, s, &rg);
+      if (rc2 == GBNF_OK) ++t->last_fwd_ranges;
+      return rc2;
+    });
+    if (rc) return rc;
+  }
+  // without a matching backward variant the backward kernels of this file run, on prep_kernel's fragments (valid while
+  // the parameters are what they are now: the trace contract)
+  if (!live_blob_has_backward(t->live)) launch_prep(t, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_forward launch: %s", hipGetErrorString(e));
+  return GBNF_OK;
+}
+
+static int forward_per_step(const gbnf_trainer* t, const TrainLayout& lay, const float* x, float* z, float* ldj, float* trace, hipStream_t s) {
+  TrainLaunch p;
+  fill_launch(t, lay, p, x);
+  p.z_out = z; p.ldj_out = ldj; p.trace_out = trace;
+  t->last_fwd_ranges = 0;
+  // the parameters may have changed since the last call: split them into this call's MFMA fragments
+  launch_prep(t, s);
   if (!needs_step_launches(t)) {
     launch_train<0>(t, p, s);
   } else {
-    // BatchNorm on batch statistics: a step's statistics need the whole batch, so the steps run one launch at a time
-    // with the state parked in HBM in slot layout (the last d*np floats of the trace buffer)
+    // the steps run one launch at a time
     if (!trace || !ldj) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: batch-statistics mode needs the trace buffer and ldj");
-    if (n < 2) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: batch statistics need n >= 2");
-    float* state = trace + (int64_t)t->K * t->d * p.np;
-    const unsigned nb = (unsigned)((p.np + 255) / 256);
-    hipLaunchKernelGGL(rows_to_slots_kernel, dim3(nb), dim3(256), 0, s, x, state, n, p.np, t->d, t->gate);
-    for (int k = 0; k < t->K; ++k) {
-      if (t->has_norm[k])
-        launch_bn_stats(t, k, state, n, p.np, s);
+    if (lay.n < 2) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: batch statistics need n >= 2");
+    float* state = trace + lay.parked_off();
+    (void)bn_forward_walk(t, t->single_steps, lay, x, state, s, [&](const StepRange& r) -> int {
       TrainLaunch q = p;
-      q.k_begin = k; q.k_end = k + 1;
+      q.k_begin = r.k0; q.k_end = r.k1;
       q.state_in = state; q.state_out = state;
-      q.ldj_accumulate = k > 0;
+      q.ldj_accumulate = r.k0 > 0;
       launch_train<0>(t, q, s);
-    }
+      return GBNF_OK;
+    });
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_forward launch: %s", hipGetErrorString(e));
   return GBNF_OK;
 }
+
+extern "C" int gbnf_trainer_forward(const gbnf_trainer* t, const float* x, int64_t n, float* z, float* ldj, float* trace,
+                                    void* stream) {
+  if (!t) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: trainer is null");
+  if (n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: n < 0");
+  if (n == 0) return GBNF_OK;
+  if (!x) return fail(GBNF_ERR_INVALID, "gbnf_trainer_forward: x is null");
+  hipStream_t s = (hipStream_t)stream;
+  if (t->rep.f) return forward_repairing(t, x, n, z, ldj, trace, s);
+  const TrainLayout lay = t->lay.at(n);
+  const bool safe = t->math == GBNF_MATH_BF16X6;
+  const bool own_ldj_wanted = ldj == nullptr && needs_step_launches(t);
+  if (safe && (trace == nullptr || own_ldj_wanted)) {          // without a trace: the same sweep into the trainer's own buffer
+    float* own_trace = nullptr;
+    float* own_ldj = nullptr;
+    if (const int rc = own_buffer(t, lay, &own_trace, &own_ldj)) return rc;
+    if (trace == nullptr) trace = own_trace;
+    if (own_ldj_wanted) ldj = own_ldj;
+  }
+  const Chain why = chained_or_why(t, lay, /*forward=*/true, trace, ldj);
+  if (why == Chain::Yes) return forward_chained(t, lay, x, z, ldj, trace, s);
+  if (safe) return refuse_range_safe("gbnf_trainer_forward", why, n);      // no per-step kernel ever runs for a range-safe trainer
+  return forward_per_step(t, lay, x, z, ldj, trace, s);
+}
+
+// ---- backward --------------------------------------------------------------------------------------------------------
+// Both forms into the trainer's own zeroed gradient buffers (the ABI accumulates into `grads`: the f16x3 result must not reach it
+// when the step is re-run), then repair_commit_kernel adds the one that counts and selects g_x the same way.  The re-run happens
+// when this call's f16x3 launches met the range or the forward call that wrote `trace` was re-run (rep.dev[3], keyed to the trace
+// pointer in last_fwd_trace; a trace this trainer does not know counts as re-run).  The two forms may run variants of different
+// widths, i.e. different operand layouts behind the trace: the re-run writes its own forward sweep into the buffer first.
+static int backward_repairing(const gbnf_trainer* t, const float* x, int64_t n, const float* trace, const float* g_z, const float* g_ldj,
+                              float* g_x, float* grads, void* workspace, int64_t workspace_bytes, hipStream_t s) {
+  const int64_t ng = t->grad_floats, nx = g_x ? n * (int64_t)t->d : 0;
+  if (t->rep.scratch_floats < 2 * ng + 2 * nx) {
+    if (t->rep.scratch) (void)hipFree(t->rep.scratch);
+    t->rep.scratch = nullptr; t->rep.scratch_floats = 0;
+    const hipError_t e = hipMalloc((void**)&t->rep.scratch, (size_t)(2 * ng + 2 * nx) * 4);
+    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward: gradient scratch: %s", hipGetErrorString(e));
+    t->rep.scratch_floats = 2 * ng + 2 * nx;
+  }
+  float* gf = t->rep.scratch;
+  float* gs = gf + ng;
+  float* xf = g_x ? gs + ng : nullptr;
+  float* xs = g_x ? xf + nx : nullptr;
+  (void)hipMemsetAsync(gf, 0, (size_t)ng * 4, s);
+  (void)hipMemsetAsync(gs, 0, (size_t)ng * 4, s);
+  int rc = gbnf_trainer_backward(t->rep.f, x, n, trace, g_z, g_ldj, xf, gf, workspace, workspace_bytes, s);
+  if (rc) return rc;
+  const int mode = trace == nullptr ? 0 : (trace == t->rep.last_fwd_trace ? 1 : 2);
+  hipLaunchKernelGGL(repair_decide_kernel, dim3(1), dim3(1), 0, s, t->rep.dev, mode, saturation_counter(), 0);
+  if (trace != nullptr) rc = gbnf_trainer_forward(t->rep.s, x, n, nullptr, nullptr, const_cast<float*>(trace), s);
+  if (rc == GBNF_OK) rc = gbnf_trainer_backward(t->rep.s, x, n, trace, g_z, g_ldj, xs, gs, workspace, workspace_bytes, s);
+  if (rc) return rc;
+  const int64_t work = ng > nx ? ng : nx;
+  const unsigned cb = (unsigned)((work + 255) / 256 < 1024 ? (work + 255) / 256 : 1024);
+  hipLaunchKernelGGL(repair_commit_kernel, dim3(cb ? cb : 1), dim3(256), 0, s, (const unsigned*)(t->rep.dev + 2), (const float*)gf, (const float*)gs,
+                     grads, ng, (const float*)xf, (const float*)xs, g_x, nx);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward commit: %s", hipGetErrorString(e));
+  t->last_bwd_ranges = t->rep.f->last_bwd_ranges;
+  return GBNF_OK;
+}
+
+// The weight gradients of the chained backward, from the operand workspace behind the trace (+ 2 K blocks: the sums of the backward
+// kernel's parameter-gradient partials ride in this launch)
+static int wgrad_chained(const gbnf_trainer* t, const TrainLayout& lay, const float* acts, float* grads, const LiveReduce& red, hipStream_t s) {
+  if (t->math == GBNF_MATH_BF16X6) {
+    // 64 x 64 blocks of 4 waves: samples per block so that ~4 workgroups per CU remain (the threshold of 1024 is reasoned from the
+    // 256 CUs, not measured)
+    const int chunk = wgrad_chunk(t->wg_blocks_safe, lay.np, 128, 2048, 1024);
+    const dim3 grid((unsigned)(t->wg_blocks_safe + 2 * red.K), (unsigned)((lay.np + chunk - 1) / chunk));
+    hipLaunchKernelGGL(wgrad_safe_kernel, grid, dim3(WGS_THREADS), 0, s, (const WgProblem*)t->probs_safe_dev, t->n_probs, acts, grads, lay.np,
+                       chunk, (const unsigned*)t->gmax_dev, t->wg_blocks_safe, red, t->gate);
+  } else {
+    // samples per block: the largest power of two in [128, 2048] that still leaves ~a block per CU (>= 240 blocks; one 128 KB
+    // workgroup of 8 waves per CU).  Measured (MINIBOONE step, 15 blocks per chunk): N = 65536 with 1024 / 2048 / 4096 samples
+    // per block 64.9 / 66.7 / 63.8 M samples/s, N = 16384 with 512 / 1024 / 2048: 46.1 / 49.2 / 41.2 M, N = 4096 with 128 / 256 /
+    // 512: 16.5 / 19.1 / 18.8 M; every further chunk adds a bm x bn tile of float atomics per block of dW, every chunk less leaves
+    // CUs idle.
+    // (up to 16 k rows the operands fit the L2s: blocks of at most 128 x 128 -- twice the workgroups)
+    const bool small = lay.np <= 16384 && t->probs_small_dev != nullptr;
+    const WgProblem* probs = small ? t->probs_small_dev : t->probs_dev;
+    const int blocks = small ? t->wg_blocks_small : t->wg_blocks;
+    const int chunk = wgrad_chunk(blocks, lay.np, 128, 2048, 240);
+    const dim3 grid((unsigned)(blocks + 2 * red.K), (unsigned)((lay.np + chunk - 1) / chunk));
+    hipLaunchKernelGGL(wgrad_kernel, grid, dim3(WG_THREADS), WG_LDS_BYTES, s, probs, t->n_probs, acts, grads, lay.np, chunk,
+                       (const unsigned*)t->gmax_dev, blocks, red);
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward launch: %s", hipGetErrorString(e));
+  return GBNF_OK;
+}
+
+// The register-chained backward sweep on what the forward sweep saved behind the trace, then the weight gradients from the operand
+// workspace that now lives there too
+static int backward_chained(const gbnf_trainer* t, const TrainLayout& lay, float* trace, const float* g_z, const float* g_ldj, float* g_x,
+                            float* grads, float* gstate, hipStream_t s) {
+  const float* acts = trace + lay.acts_off();
+  LiveReduce red{};
+  t->last_bwd_ranges = 1;
+  if (!needs_step_launches(t)) {
+    const int rc = live_blob_backward(t->live, lay, trace, g_z, g_ldj, g_x, grads, t->gmax_dev, s, &red);
+    if (rc) return rc;
+  } else {
+    t->last_bwd_ranges = 0;
+    unsigned done = 0u;
+    const int rc = bn_backward_walk(t, t->ranges, lay, trace, grads, gstate, g_x, s, [&](const StepRange& r) -> int {
+      LiveRange rg{r.k0, r.k1, r.k1 < t->K ? gstate : nullptr, gstate, 0, false, nullptr, nullptr};
+      const int rc2 = live_blob_backward(t->live, lay, trace, g_z, g_ldj, nullptr, grads, t->gmax_dev, s, &red, &rg);
+      if (rc2) return rc2;
+      ++t->last_bwd_ranges;
+      if (t->has_norm[r.k0]) {      // the step's two parameter sums are added up now: exactly the two batch sums the correction needs
+        LiveReduce one = red;
+        one.skip_steps = ~(1u << r.k0);
+        // (n_blocks = 0: only the reduce blocks of wgrad_kernel run -- plain f32 sums of the partials, nothing is split or clamped, so
+        //  a range-safe trainer shares this launch)
+        hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)(2 * red.K), 1u), dim3(WG_THREADS), 2048, s, t->probs_dev, t->n_probs, acts, grads,
+                           lay.np, 512, (const unsigned*)t->gmax_dev, 0, one);
+        done |= 1u << r.k0;
+      }
+      return GBNF_OK;
+    });
+    if (rc) return rc;
+    red.skip_steps = done;
+  }
+  return wgrad_chained(t, lay, acts, grads, red, s);
+}
+
+static int backward_per_step(const gbnf_trainer* t, const TrainLayout& lay, const float* x, const float* trace, const float* g_z,
+                             const float* g_ldj, float* g_x, float* grads, float* workspace, float* gstate, hipStream_t s) {
+  TrainLaunch p;
+  fill_launch(t, lay, p, x);
+  p.g_z = g_z; p.g_ldj = g_ldj; p.g_x = g_x; p.grads = grads; p.ws = workspace; p.trace = trace;
+  p.gmax = t->gmax_dev;
+  // a trace is valid only while the parameters are what they were in the forward call that wrote it (include/gbnf.h):
+  // that call split them into this trainer's fragment buffer, so the fragments are still the right ones
+  t->last_bwd_ranges = 0;
+  if (trace == nullptr) launch_prep(t, s);
+  if (!needs_step_launches(t)) {
+    launch_train<1>(t, p, s);
+  } else {
+    // one launch per step (the kernel adds a step's parameter sums itself)
+    if (!trace) return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: batch-statistics mode needs the forward call's trace");
+    (void)bn_backward_walk(t, t->single_steps, lay, trace, grads, gstate, g_x, s, [&](const StepRange& r) -> int {
+      TrainLaunch q = p;
+      q.k_begin = r.k0; q.k_end = r.k1;
+      q.gstate_in = r.k1 == t->K ? nullptr : gstate;
+      q.gstate_out = gstate;
+      launch_train<1>(t, q, s);
+      return GBNF_OK;
+    });
+  }
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward launch: %s", hipGetErrorString(e));
+  // samples per block: every block ends in 4096 atomic adds, so as many samples as still leave a few thousand waves
+  const int chunk = wgrad_chunk(t->wg_blocks, lay.np, 512, 4096, 768);     // (a block = 4 waves)
+  const dim3 wgrid((unsigned)t->wg_blocks, (unsigned)((lay.np + chunk - 1) / chunk));
+  hipLaunchKernelGGL(wgrad_kernel, wgrid, dim3(WG_THREADS), WG_LDS_BYTES, s, t->probs_dev, t->n_probs, (const float*)workspace, grads, lay.np, chunk,
+                     (const unsigned*)t->gmax_dev, t->wg_blocks, LiveReduce{});
+  e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward wgrad launch: %s", hipGetErrorString(e));
+  return GBNF_OK;
+}
+
+extern "C" {
 
 int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, const float* trace, const float* g_z,
                           const float* g_ldj, float* g_x, float* grads, void* workspace, int64_t workspace_bytes,
@@ -2316,63 +2501,22 @@ int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, cons
   if (n < 0) return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: n < 0");
   if (n == 0) return GBNF_OK;
   if (!x || !grads || !workspace) return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: x / grads / workspace is null");
-  if (t->rep_f) {
-    // Both forms into the trainer's own zeroed gradient buffers (the ABI accumulates into `grads`: the f16x3 result must not reach it
-    // when the step is re-run), then repair_commit_kernel adds the one that counts and selects g_x the same way.  The re-run happens
-    // when this call's f16x3 launches met the range or the forward call that wrote `trace` was re-run (rep_dev[3], keyed to the trace
-    // pointer in last_fwd_trace; a trace this trainer does not know counts as re-run).  The two forms may run variants of different
-    // widths, i.e. different operand layouts behind the trace: the re-run writes its own forward sweep into the buffer first.
-    hipStream_t s = (hipStream_t)stream;
-    const int64_t ng = t->grad_floats, nx = g_x ? n * (int64_t)t->d : 0;
-    if (t->rep_scratch_floats < 2 * ng + 2 * nx) {
-      if (t->rep_scratch) (void)hipFree(t->rep_scratch);
-      t->rep_scratch = nullptr; t->rep_scratch_floats = 0;
-      const hipError_t e = hipMalloc((void**)&t->rep_scratch, (size_t)(2 * ng + 2 * nx) * 4);
-      if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward: gradient scratch: %s", hipGetErrorString(e));
-      t->rep_scratch_floats = 2 * ng + 2 * nx;
-    }
-    float* gf = t->rep_scratch;
-    float* gs = gf + ng;
-    float* xf = g_x ? gs + ng : nullptr;
-    float* xs = g_x ? xf + nx : nullptr;
-    (void)hipMemsetAsync(gf, 0, (size_t)ng * 4, s);
-    (void)hipMemsetAsync(gs, 0, (size_t)ng * 4, s);
-    int rc = gbnf_trainer_backward(t->rep_f, x, n, trace, g_z, g_ldj, xf, gf, workspace, workspace_bytes, stream);
-    if (rc) return rc;
-    const int mode = trace == nullptr ? 0 : (trace == t->last_fwd_trace ? 1 : 2);
-    hipLaunchKernelGGL(repair_decide_kernel, dim3(1), dim3(1), 0, s, t->rep_dev, mode, saturation_counter(), 0);
-    if (trace != nullptr) rc = gbnf_trainer_forward(t->rep_s, x, n, nullptr, nullptr, const_cast<float*>(trace), stream);
-    if (rc == GBNF_OK) rc = gbnf_trainer_backward(t->rep_s, x, n, trace, g_z, g_ldj, xs, gs, workspace, workspace_bytes, stream);
-    if (rc) return rc;
-    const int64_t work = ng > nx ? ng : nx;
-    const unsigned cb = (unsigned)((work + 255) / 256 < 1024 ? (work + 255) / 256 : 1024);
-    hipLaunchKernelGGL(repair_commit_kernel, dim3(cb ? cb : 1), dim3(256), 0, s, (const unsigned*)(t->rep_dev + 2), (const float*)gf, (const float*)gs,
-                       grads, ng, (const float*)xf, (const float*)xs, g_x, nx);
-    const hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward commit: %s", hipGetErrorString(e));
-    t->last_bwd_ranges = t->rep_f->last_bwd_ranges;
-    return GBNF_OK;
-  }
-  int64_t need = 0;
-  gbnf_trainer_workspace_bytes(t, n, &need);
-  if (workspace_bytes < need)
+  hipStream_t s = (hipStream_t)stream;
+  if (t->rep.f) return backward_repairing(t, x, n, trace, g_z, g_ldj, g_x, grads, workspace, workspace_bytes, s);
+  const TrainLayout lay = t->lay.at(n);
+  if (workspace_bytes < lay.workspace_bytes())
     return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: workspace of %lld bytes < %lld", (long long)workspace_bytes,
-                (long long)need);
+                (long long)lay.workspace_bytes());
   const bool safe = t->math == GBNF_MATH_BF16X6;
   if (safe && trace == nullptr) {      // without a trace: the traced pair, the forward into the trainer's own buffer
     float* own_trace = nullptr;
     float* own_ldj = nullptr;
-    int rc = own_buffer(t, n, &own_trace, &own_ldj);
+    int rc = own_buffer(t, lay, &own_trace, &own_ldj);
     if (rc == GBNF_OK) rc = gbnf_trainer_forward(t, x, n, nullptr, own_ldj, own_trace, stream);
     if (rc) return rc;
     trace = own_trace;
   }
-  TrainLaunch p;
-  fill_launch(t, p, x, n);
-  p.g_z = g_z; p.g_ldj = g_ldj; p.g_x = g_x; p.grads = grads; p.ws = (float*)workspace; p.trace = trace;
-  p.batch_stats = t->batch_stats;
-  float* gstate = (float*)workspace + ((int64_t)t->K * t->nnets * t->net_rows + TR_WS_SLACK_ROWS) * p.np;   // [d][np]: gradient state between step launches
-  hipStream_t s = (hipStream_t)stream;
+  float* gstate = (float*)workspace + lay.gstate_off();      // [d][np]: gradient state between step launches
   // the scale of this call's gradients: the largest upstream entry (tr_grad_scale)
   (void)hipMemsetAsync(t->gmax_dev, 0, sizeof(unsigned), s);
   {
@@ -2380,145 +2524,28 @@ int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, cons
     const unsigned gb = (unsigned)((work + 256 * 16 - 1) / (256 * 16) < 256 ? (work + 256 * 16 - 1) / (256 * 16) : 256);
     hipLaunchKernelGGL(gmax_kernel, dim3(gb ? gb : 1), dim3(256), 0, s, g_z, g_ldj, n, t->d, t->gmax_dev);
   }
-  p.gmax = t->gmax_dev;
-  if (live_blob_has_backward(t->live) && trace != nullptr && (int64_t)t->nnets * t->net_rows * p.np < (1LL << 31) &&
-      (!needs_step_launches(t) || (int)t->bmean_ptr.size() == t->K)) {
-    // round 3: the register-chained backward sweep on what the forward sweep saved behind the trace, then the weight
-    // gradients from the operand workspace that now lives there too
-    float* acts = const_cast<float*>(trace) + ((int64_t)t->K + 1) * t->d * p.np;
-    LiveReduce red{};
-    t->last_bwd_ranges = 1;
-    if (!needs_step_launches(t)) {
-      const int rc = live_blob_backward(t->live, n, trace, acts, p.np, t->ip, t->hp, t->op, g_z, g_ldj, g_x, grads, t->gmax_dev, stream, &red);
-      if (rc) return rc;
-    } else {
-      t->last_bwd_ranges = 0;
-      // round 4, the mirror image of the forward: one launch per step range, last range first; behind a range that starts with a
-      // BatchNorm step its two parameter sums are added up (they are that step's d/d beta and d/d log_gamma: exactly the two batch
-      // sums the correction needs) and the parked gradient state is corrected for the dependence of the batch statistics on
-      // every sample (bn_bwd_fix_kernel); the last launch's state goes out as g_x rows
-      std::vector<int> starts;
-      for (int k0 = 0; k0 < t->K;) { starts.push_back(k0); int k1 = k0 + 1; while (k1 < t->K && !t->has_norm[k1]) ++k1; k0 = k1; }
-      unsigned done = 0u;
-      for (int ri = (int)starts.size() - 1; ri >= 0; --ri) {
-        const int k0 = starts[ri], k1 = ri + 1 < (int)starts.size() ? starts[ri + 1] : t->K;
-        LiveRange rg{k0, k1, k1 < t->K ? gstate : nullptr, gstate, 0, false, nullptr, nullptr};
-        const int rc = live_blob_backward(t->live, n, trace, acts, p.np, t->ip, t->hp, t->op, g_z, g_ldj, nullptr, grads, t->gmax_dev, stream, &red, &rg);
-        if (rc) return rc;
-        ++t->last_bwd_ranges;
-        if (t->has_norm[k0]) {
-          LiveReduce one = red;
-          one.skip_steps = ~(1u << k0);
-          // (n_blocks = 0: only the reduce blocks of wgrad_kernel run -- plain f32 sums of the partials, nothing is split or clamped, so
-          //  a range-safe trainer shares this launch)
-          hipLaunchKernelGGL(wgrad_kernel, dim3((unsigned)(2 * red.K), 1u), dim3(WG_THREADS), 2048, s, t->probs_dev, t->n_probs, (const float*)acts, grads,
-                             p.np, 512, (const unsigned*)t->gmax_dev, 0, one);
-          done |= 1u << k0;
-          const dim3 fg((unsigned)((n + 255) / 256), (unsigned)t->d);
-          hipLaunchKernelGGL(bn_bwd_fix_kernel, fg, dim3(256), 0, s, (const TrStep*)t->steps_dev, k0, t->d, trace, (const float*)grads,
-                             gstate, n, p.np, (const unsigned*)t->gmax_dev);
-        }
-      }
-      if (g_x != nullptr)
-        hipLaunchKernelGGL(slots_to_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)gstate, g_x, n, p.np, t->d,
-                           (const unsigned*)t->gmax_dev);
-      red.skip_steps = done;
-    }
-    // samples per block: the largest power of two in [128, 2048] that still leaves ~a block per CU (>= 240 blocks; one 128 KB
-    // workgroup of 8 waves per CU).  Measured (MINIBOONE step, 15 blocks per chunk): N = 65536 with 1024 / 2048 / 4096 samples
-    // per block 64.9 / 66.7 / 63.8 M samples/s, N = 16384 with 512 / 1024 / 2048: 46.1 / 49.2 / 41.2 M, N = 4096 with 128 / 256 /
-    // 512: 16.5 / 19.1 / 18.8 M; every further chunk adds a bm x bn tile of float atomics per block of dW, every chunk less leaves
-    // CUs idle.
-    // (up to 16 k rows the operands fit the L2s: blocks of at most 128 x 128 -- twice the workgroups)
-    static const int small_np = [] { const char* e = getenv("GBNF_WG_SMALL_NP"); return e ? atoi(e) : 16384; }();
-    const bool small = p.np <= small_np && t->probs_small_dev != nullptr;
-    const WgProblem* wg_probs = small ? t->probs_small_dev : t->probs_dev;
-    const int wg_blocks = small ? t->wg_blocks_small : t->wg_blocks;
-    int chunk2 = 128;
-    while (chunk2 < 2048 && (int64_t)wg_blocks * (p.np / (2 * chunk2)) >= 240) chunk2 *= 2;
-    if (const char* e = getenv("GBNF_WG_CHUNK")) { if (atoi(e) > 0) chunk2 = atoi(e); }      // (A/B runs)
-    // (+ 2 K blocks: the sums of the backward kernel's parameter-gradient partials ride in this launch)
-    if (safe) {
-      // 64 x 64 blocks of 4 waves: samples per block so that ~4 workgroups per CU remain (the threshold of 1024 is reasoned from the
-      // 256 CUs, not measured)
-      int chunk3 = 128;
-      while (chunk3 < 2048 && (int64_t)t->wg_blocks_safe * (p.np / (2 * chunk3)) >= 1024) chunk3 *= 2;
-      const dim3 wgrid3((unsigned)(t->wg_blocks_safe + 2 * red.K), (unsigned)((p.np + chunk3 - 1) / chunk3));
-      hipLaunchKernelGGL(wgrad_safe_kernel, wgrid3, dim3(WGS_THREADS), 0, s, (const WgProblem*)t->probs_safe_dev, t->n_probs,
-                         (const float*)acts, grads, p.np, chunk3, (const unsigned*)t->gmax_dev, t->wg_blocks_safe, red, t->gate);
-      const hipError_t e3 = hipGetLastError();
-      if (e3 != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward launch: %s", hipGetErrorString(e3));
-      return GBNF_OK;
-    }
-    const dim3 wgrid2((unsigned)(wg_blocks + 2 * red.K), (unsigned)((p.np + chunk2 - 1) / chunk2));
-    hipLaunchKernelGGL(wgrad_kernel, wgrid2, dim3(WG_THREADS), WG_LDS_BYTES, s, wg_probs, t->n_probs,
-                       (const float*)acts, grads, p.np, chunk2, (const unsigned*)t->gmax_dev, wg_blocks, red);
-    const hipError_t e2 = hipGetLastError();
-    if (e2 != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward launch: %s", hipGetErrorString(e2));
-    return GBNF_OK;
-  }
-  if (safe) {
-    if ((int64_t)t->nnets * t->net_rows * p.np >= (1LL << 31))
-      return fail(GBNF_ERR_UNSUPPORTED, "gbnf_trainer_backward: %lld rows exceed the 32-bit operand offsets of the bf16x6 sweep", (long long)n);
-    return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: batch-statistics mode needs every BatchNorm step's buffers (gbnf_trainer_bind_batch_stats)");
-  }
-  // a trace is valid only while the parameters are what they were in the forward call that wrote it (include/gbnf.h):
-  // that call split them into this trainer's fragment buffer, so the fragments are still the right ones
-  t->last_bwd_ranges = 0;
-  if (trace == nullptr)
-    hipLaunchKernelGGL(prep_kernel, dim3((unsigned)t->prep_blocks), dim3(64), 0, s, (const PrepProblem*)t->prep_dev, t->n_prep, t->frag_dev);
-  if (!needs_step_launches(t)) {
-    launch_train<1>(t, p, s);
-  } else {
-    // the mirror image of the forward: one launch per step; after a BatchNorm step the gradient state is corrected for
-    // the dependence of the batch statistics on every sample (its two batch sums are that step's d/d beta, d/d log_gamma)
-    if (!trace) return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: batch-statistics mode needs the forward call's trace");
-    for (int k = t->K - 1; k >= 0; --k) {
-      TrainLaunch q = p;
-      q.k_begin = k; q.k_end = k + 1;
-      q.gstate_in = (k == t->K - 1) ? nullptr : gstate;
-      q.gstate_out = gstate;
-      launch_train<1>(t, q, s);
-      if (t->has_norm[k]) {
-        const dim3 fg((unsigned)((n + 255) / 256), (unsigned)t->d);
-        hipLaunchKernelGGL(bn_bwd_fix_kernel, fg, dim3(256), 0, s, (const TrStep*)t->steps_dev, k, t->d, trace, (const float*)grads,
-                           gstate, n, p.np, (const unsigned*)t->gmax_dev);
-      }
-    }
-    if (g_x != nullptr)
-      hipLaunchKernelGGL(slots_to_rows_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)gstate, g_x, n, p.np, t->d,
-                         (const unsigned*)t->gmax_dev);
-  }
-  hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward launch: %s", hipGetErrorString(e));
-  // samples per block: every block ends in 4096 atomic adds, so as many samples as still leave a few thousand waves
-  static const int forced_chunk = [] { const char* e = getenv("GBNF_WGRAD_CHUNK"); return e ? atoi(e) : 0; }();
-  int chunk = 512;
-  while (chunk < 4096 && (int64_t)t->wg_blocks * (p.np / (2 * chunk)) >= 768) chunk *= 2;     // (a block = 4 waves)
-  if (forced_chunk >= 32 && forced_chunk % 32 == 0) chunk = forced_chunk;
-  const dim3 wgrid((unsigned)t->wg_blocks, (unsigned)((p.np + chunk - 1) / chunk));
-  hipLaunchKernelGGL(wgrad_kernel, wgrid, dim3(WG_THREADS), WG_LDS_BYTES, s, t->probs_dev, t->n_probs, (const float*)workspace, grads, p.np, chunk,
-                     (const unsigned*)t->gmax_dev, t->wg_blocks, LiveReduce{});
-  e = hipGetLastError();
-  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward wgrad launch: %s", hipGetErrorString(e));
-  return GBNF_OK;
+  const Chain why = chained_or_why(t, lay, /*forward=*/false, trace, nullptr);
+  // (the sweep writes the gradient-side operands behind the states: `trace` is const for the states only, include/gbnf.h)
+  if (why == Chain::Yes) return backward_chained(t, lay, const_cast<float*>(trace), g_z, g_ldj, g_x, grads, gstate, s);
+  if (safe) return refuse_range_safe("gbnf_trainer_backward", why, n);
+  return backward_per_step(t, lay, x, trace, g_z, g_ldj, g_x, grads, (float*)workspace, gstate, s);
 }
 
 int gbnf_trainer_repair_count(const gbnf_trainer* t, int64_t* calls, int32_t reset) {
   if (!t || !calls) return fail(GBNF_ERR_INVALID, "gbnf_trainer_repair_count: null argument");
   *calls = 0;
-  if (t->rep_dev == nullptr) return GBNF_OK;          // GBNF_MATH_F16X3 and GBNF_MATH_BF16X6 trainers never re-run a call
+  if (t->rep.dev == nullptr) return GBNF_OK;          // GBNF_MATH_F16X3 and GBNF_MATH_BF16X6 trainers never re-run a call
   hipError_t e = hipDeviceSynchronize();
   unsigned v = 0;
-  if (e == hipSuccess) e = hipMemcpy(&v, t->rep_dev + 4, sizeof(v), hipMemcpyDeviceToHost);
-  if (e == hipSuccess && reset) e = hipMemset(t->rep_dev + 4, 0, sizeof(unsigned));
+  if (e == hipSuccess) e = hipMemcpy(&v, t->rep.dev + 4, sizeof(v), hipMemcpyDeviceToHost);
+  if (e == hipSuccess && reset) e = hipMemset(t->rep.dev + 4, 0, sizeof(unsigned));
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_repair_count: %s", hipGetErrorString(e));
   *calls = (int64_t)v;
   return GBNF_OK;
 }
 
 // (tests) how the last forward / backward call of a trainer ran: launches of the register-chained kernels (1 = the whole sweep in one
-// launch, > 1 = one per step range of a batch-statistics BatchNorm sweep), 0 = the round-1 per-step kernels
+// launch, > 1 = one per step range of a batch-statistics BatchNorm sweep), 0 = the per-step kernels
 int gbnf_debug_trainer_last_path(const gbnf_trainer* t, int32_t* fwd_ranges, int32_t* bwd_ranges) {
   if (!t) return fail(GBNF_ERR_INVALID, "gbnf_debug_trainer_last_path: trainer is null");
   if (fwd_ranges) *fwd_ranges = t->last_fwd_ranges;

@@ -151,59 +151,41 @@ inline int bwd_hx3_waves(int n_steps, int stage_frags, int d) {
   return bwd_hx3_lds_bytes(n_steps, 4, stage_frags, d) <= 160 * 1024 ? 4 : 8;
 }
 
+// the kernel of an arithmetic: PREC 0 = f16x3, 1 = bf16x6 (the two have one function type; only the one asked for is instantiated)
+template <int KIND, int HT, int OT, int ACTA, int ACTB, int WV, int DEPTH, int PREC>
+constexpr auto bwd_kernel_of() {
+  if constexpr (PREC == 0) return &bwd_kernel_hx3<KIND, HT, OT, ACTA, ACTB, WV, DEPTH>;
+  else return &bwd_kernel_hx3_safe<KIND, HT, OT, ACTA, ACTB, WV, DEPTH>;
+}
+
 template <int KIND, int HT, int OT, int ACTA, int ACTB, int WV, int DEPTH, int PREC = 0>
 static hipError_t bwd_launch_wv(FlowLaunch p, hipStream_t s) {
   constexpr BwdLayout L(HT, OT, DEPTH, hx3_pieces(PREC));
+  constexpr auto kernel = bwd_kernel_of<KIND, HT, OT, ACTA, ACTB, WV, DEPTH, PREC>();
   const size_t lds = bwd_hx3_lds_bytes(p.n_steps, WV, L.STAGE_FRAGS, p.d);
   if (lds > 160 * 1024 || p.n_steps > LDS_TABLE_STEPS) return hipErrorInvalidValue;
   const long long tiles = p.np / 16;               // every padded row (np is a multiple of 32): wgrad_kernel sums over all of them
   const long long grid = (tiles + WV - 1) / WV;
-  static bool attr_set = false;
-  if constexpr (PREC == 0) {
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)bwd_kernel_hx3<KIND, HT, OT, ACTA, ACTB, WV, DEPTH>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((bwd_kernel_hx3<KIND, HT, OT, ACTA, ACTB, WV, DEPTH>), dim3((unsigned)grid), dim3(64 * WV), lds, s, p);
-  } else {
-    if (!attr_set) {
-      hipError_t e = hipFuncSetAttribute((const void*)bwd_kernel_hx3_safe<KIND, HT, OT, ACTA, ACTB, WV, DEPTH>,
-                                         hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-      if (e != hipSuccess) return e;
-      attr_set = true;
-    }
-    hipLaunchKernelGGL((bwd_kernel_hx3_safe<KIND, HT, OT, ACTA, ACTB, WV, DEPTH>), dim3((unsigned)grid), dim3(64 * WV), lds, s, p);
-  }
+  static DynamicLdsOptIn opt_in;
+  if (hipError_t e = opt_in({(const void*)kernel}); e != hipSuccess) return e;
+  hipLaunchKernelGGL(kernel, dim3((unsigned)grid), dim3(64 * WV), lds, s, p);
   return hipGetLastError();
 }
 
-// registry key: VariantKey{kind, ht, -3 (f16x3) | -6 (bf16x6), /*ks1*/ 2 (backward), ot, /*nt*/ 1, depth, act_a, act_b}
-#define GBNF_INSTANTIATE_HX3_BWD(KIND, HT, OT, ACTA, ACTB, DEPTH)                                           \
+// registry key: VariantKey{kind, ht, -3 (f16x3) | -6 (bf16x6: a `safe` line of variants.list), /*ks1*/ 2 (backward), ot, /*nt*/ 1, depth,
+// act_a, act_b}; PREC: 0 | 1
+#define GBNF_INSTANTIATE_HX3_BWD(PREC, KIND, HT, OT, ACTA, ACTB, DEPTH)                                     \
   namespace gbnf {                                                                                          \
   static hipError_t launch_hx3b_##KIND##_##HT##_##OT##_##ACTA##_##ACTB##_##DEPTH(const FlowLaunch& p0, unsigned, hipStream_t s) { \
-    constexpr BwdLayout L(HT, OT, DEPTH);                                                                   \
-    if (bwd_hx3_waves(p0.n_steps, L.STAGE_FRAGS, p0.d) == 4) return bwd_launch_wv<KIND, HT, OT, ACTA, ACTB, 4, DEPTH>(p0, s); \
-    return bwd_launch_wv<KIND, HT, OT, ACTA, ACTB, 8, DEPTH>(p0, s);                                        \
+    constexpr BwdLayout L(HT, OT, DEPTH, hx3_pieces(PREC));                                                 \
+    if (bwd_hx3_waves(p0.n_steps, L.STAGE_FRAGS, p0.d) == 4) return bwd_launch_wv<KIND, HT, OT, ACTA, ACTB, 4, DEPTH, PREC>(p0, s); \
+    return bwd_launch_wv<KIND, HT, OT, ACTA, ACTB, 8, DEPTH, PREC>(p0, s);                                  \
   }                                                                                                         \
   static const int reg_hx3b_##KIND##_##HT##_##OT##_##ACTA##_##ACTB##_##DEPTH =                              \
-      (register_variant(VariantKey{KIND, HT, -3, 2, OT, 1, DEPTH, ACTA, ACTB}, launch_hx3b_##KIND##_##HT##_##OT##_##ACTA##_##ACTB##_##DEPTH, \
-                        "bwd_kernel_hx3<" #KIND "," #HT "," #OT "," #ACTA "," #ACTB "," #DEPTH ">"),        \
-       0);                                                                                                  \
-  }
-
-// the bf16x6 form of the same geometry (a `safe` line of variants.list)
-#define GBNF_INSTANTIATE_HX3_BWD_SAFE(KIND, HT, OT, ACTA, ACTB, DEPTH)                                      \
-  namespace gbnf {                                                                                          \
-  static hipError_t launch_hx3bs_##KIND##_##HT##_##OT##_##ACTA##_##ACTB##_##DEPTH(const FlowLaunch& p0, unsigned, hipStream_t s) { \
-    constexpr BwdLayout L(HT, OT, DEPTH, 3);                                                                \
-    if (bwd_hx3_waves(p0.n_steps, L.STAGE_FRAGS, p0.d) == 4) return bwd_launch_wv<KIND, HT, OT, ACTA, ACTB, 4, DEPTH, 1>(p0, s); \
-    return bwd_launch_wv<KIND, HT, OT, ACTA, ACTB, 8, DEPTH, 1>(p0, s);                                     \
-  }                                                                                                         \
-  static const int reg_hx3bs_##KIND##_##HT##_##OT##_##ACTA##_##ACTB##_##DEPTH =                             \
-      (register_variant(VariantKey{KIND, HT, -6, 2, OT, 1, DEPTH, ACTA, ACTB}, launch_hx3bs_##KIND##_##HT##_##OT##_##ACTA##_##ACTB##_##DEPTH, \
-                        "bwd_kernel_hx3_safe<" #KIND "," #HT "," #OT "," #ACTA "," #ACTB "," #DEPTH ">"),   \
+      (register_variant(VariantKey{KIND, HT, PREC == 0 ? -3 : -6, 2, OT, 1, DEPTH, ACTA, ACTB},            \
+                        launch_hx3b_##KIND##_##HT##_##OT##_##ACTA##_##ACTB##_##DEPTH,                       \
+                        PREC == 0 ? "bwd_kernel_hx3<" #KIND "," #HT "," #OT "," #ACTA "," #ACTB "," #DEPTH ">"       \
+                                  : "bwd_kernel_hx3_safe<" #KIND "," #HT "," #OT "," #ACTA "," #ACTB "," #DEPTH ">"), \
        0);                                                                                                  \
   }
 

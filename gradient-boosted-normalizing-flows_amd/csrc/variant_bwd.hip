@@ -4,8 +4,9 @@
 #error "compile with -DGBNF_V_ARGS=KIND,HT,OT,ACTA,ACTB,DEPTH"
 #endif
 #ifdef GBNF_V_SAFE
-#define GBNF_INST2(...) GBNF_INSTANTIATE_HX3_BWD_SAFE(__VA_ARGS__)
+#define GBNF_V_PREC 1
 #else
-#define GBNF_INST2(...) GBNF_INSTANTIATE_HX3_BWD(__VA_ARGS__)
+#define GBNF_V_PREC 0
 #endif
-GBNF_INST2(GBNF_V_ARGS)
+#define GBNF_INST2(...) GBNF_INSTANTIATE_HX3_BWD(__VA_ARGS__)
+GBNF_INST2(GBNF_V_PREC, GBNF_V_ARGS)

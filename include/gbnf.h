@@ -395,8 +395,9 @@ int gbnf_trainer_repair_count(const gbnf_trainer* trainer, int64_t* calls, int32
  * Since round 3 the trace buffer of a flow that runs on the register-chained kernels (TanhNet / ReLUNet coupling nets of
  * coupling_network_depth 0, 1, 2 and RealNVP ResidualNets of one or two blocks -- all but depth 1 since round 5 -- of a compiled width)
  * is also the OPERAND WORKSPACE of the step: behind the states the forward call stores the coupling nets' inputs, hidden
- * activations and outputs (gbnf_trainer_trace_floats accounts for it: K * nets * (ip + 2 L hp + 2 op) rows of
- * n-rounded-up-to-32 floats, L = hidden layers per net -- 20 KB per sample for MINIBOONE, K = 5, depth 1), and
+ * activations and outputs.  gbnf_trainer_trace_floats returns the whole buffer, in rows of np = n-rounded-up-to-32 floats:
+ * (K + 1) * d rows of states (K normalised ones and the running state), and for such a flow K * nets * (ip + 2 L hp + 2 op)
+ * operand rows, L = hidden layers per net, + 320 slack rows -- 20 KB per sample for MINIBOONE, K = 5, depth 1.
  * gbnf_trainer_backward WRITES the gradient-side operands of the weight gradients into the same buffer (its `trace`
  * argument is const for the states only).  One trace buffer therefore serves one forward + one backward call. */
 int gbnf_trainer_trace_floats(const gbnf_trainer* trainer, int64_t n, int64_t* n_floats);
