@@ -829,6 +829,57 @@ class BoostedFlow(nn.Module):
             z, ldj, _ = self.native_flow(int(c)).forward(x)
         return z, ldj
 
+    def training_step(self, x, *, lr, weight_decay=0.0, max_grad_norm=0.0, optimizer="adamw", betas=(0.9, 0.999), eps=1e-8,
+                      resample=None, beta=1.0):
+        """The body of one iteration of the reference's training loop (density_experiment.py:340-384) for ``self.component``, in one
+        library call (gbnf_trainer_nll_step): compute_kl_pq_loss (:606-674) -- for a boosted component beyond the first on the batch
+        resampled with ``boosting_weights`` and the CALLER's RNG (``torch.multinomial``) --, ``nll.backward()``, ``clip_grad_norm_``
+        (``max_grad_norm`` > 0) and the step of ``optim.AdamW`` / ``optim.SGD`` ("adamw" | "sgd") on the component's parameters, in
+        place.  ``lr`` is per call (schedulers stay with the caller; a component that is not being trained gets 0).  ``resample``
+        defaults to ``self.component > 0 or self.all_trained``.  ActNorm's data-dependent initialisation and the BatchNorm mode follow
+        ``component_forward``; in train() mode the running statistics are updated on the device.  Returns 0-dim DEVICE tensors (nothing
+        is read back): ``nll``, ``grad_norm``, ``clip_coef`` and, when resampled, ``G_nll``.  The optimiser state is kept per component
+        (``self.opt_state(c)``: a ``native.OptState``).  No ``p.grad`` is written."""
+        self._check_ready(x)
+        c = int(self.component)
+        x = x.contiguous().float()
+        self._ensure_actnorm(x, c)
+        if resample is None:
+            resample = bool(self.component > 0 or self.all_trained)
+        out, rows = {}, None
+        if resample:
+            with torch.no_grad():
+                w, G = self.boosting_weights(x, beta)
+                rows = torch.multinomial(w, x.shape[0], replacement=True)
+                out["G_nll"] = -G.mean()
+        with torch.cuda.device(x.device):
+            trainer = self.native_trainer(c)
+            batch_stats = bool(self.training and trainer.has_batch_stats)
+            trainer.set_batch_stats(batch_stats)
+            trainer.forward_serial = getattr(trainer, "forward_serial", 0) + 1     # (the bound batch statistics are overwritten)
+            state = self.opt_state(c, optimizer)
+            momentum = -1.0
+            if batch_stats:
+                momentum = next(float(m[2].momentum) for m in self.flows[c].flow_param if len(m) > 2 and m[2] is not None)
+            stats, _ = trainer.nll_step(x, state, rows=rows, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                                        betas=betas, eps=eps, bn_momentum=momentum)
+        # the kernels wrote the parameters (and running statistics) behind autograd's back: move their version counters, on the host
+        # and without a launch, so that every packed evaluation copy keyed on them (_component_key) is rebuilt
+        params, buffers, _ = self._component_tensors(c)
+        torch.autograd.graph.increment_version(params + buffers if batch_stats else params)
+        out.update(nll=stats[0], grad_norm=stats[1], clip_coef=stats[2])
+        return out
+
+    def opt_state(self, c, optimizer="adamw"):
+        """The ``native.OptState`` ``training_step`` keeps for component c (created on first use; another ``optimizer`` kind or a
+        re-shaped component starts a new one)."""
+        trainer = self.native_trainer(int(c))
+        states = self.__dict__.setdefault("_opt_states", {})
+        st = states.get(int(c))
+        if st is None or st.kind != optimizer or st.grad_floats != trainer.grad_floats or st.exp_avg_device != trainer.device:
+            st = states[int(c)] = native.OptState(trainer, optimizer)
+        return st
+
     # The reference's evaluate loop asks for the components of ONE batch one call at a time
     # (density_experiment.py:561-573: ``for c in range(model.component + 1): model(x=x, components=c)``).  All of them read
     # the same x, so in eval() mode the first call of a batch launches EVERY component in use
@@ -939,7 +990,9 @@ class BoostedFlow(nn.Module):
         every ordinary update moves (optimiser steps, ``load_state_dict``, ``p.add_()`` / ``p.copy_()`` under ``no_grad``, ``.to()``);
         what they CANNOT see is an in-place write through ``.data`` (``p.data.clamp_()``, ``p.data.copy_(w)``: PyTorch bumps no
         counter for it) or through a raw pointer -- call this after such a write.  (The training handles read the live tensors
-        on every call and need nothing.)"""
+        on every call and need nothing.)  ``training_step`` updates the parameters through raw pointers too; it does not call this
+        but moves the version counters of the component it updated itself (``torch.autograd.graph.increment_version``: host only),
+        so only that component's packed copies are rebuilt."""
         self._handles = {}
         self._handles_exact = {}
         self._mixture = None

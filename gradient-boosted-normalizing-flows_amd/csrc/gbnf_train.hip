@@ -43,6 +43,7 @@
 
 #include "../../include/gbnf.h"
 #include "gbnf_internal.h"
+#include "gbnf_opt.h"
 
 
 namespace gbnf {
@@ -1649,6 +1650,12 @@ struct gbnf_trainer {
   std::vector<StepRange> ranges, single_steps;
   std::vector<char> stats_bound;       // per step: bmean / bvar bound by the caller
   std::vector<float*> bmean_ptr, bvar_ptr;   // per step: the caller's device buffers (host copies of TrStep::bmean / bvar)
+  // The on-device update (gbnf_opt.hip): every bound parameter tensor with its place in the flat gradient buffer, the trainer-owned
+  // partial sums of gbnf_trainer_apply_update's norm, and the running statistics a batch-statistics step moves
+  OptRegion* regions_dev = nullptr;
+  int n_regions = 0;
+  double* opt_partials_dev = nullptr;
+  std::vector<float*> rmean_ptr, rvar_ptr;   // per step: BatchNorm running_mean / running_var (null without a BatchNorm)
   LiveBlob* live = nullptr;            // the sweeps on flow_kernel_hx3<TRAIN> / bwd_kernel_hx3 (TanhNet / ReLUNet / ResidualNet of a compiled width), else null
   mutable int last_fwd_ranges = 0, last_bwd_ranges = 0;     // (tests) launches of the register-chained kernels by the last forward / backward call; 0 = the per-step kernels ran
   // GBNF_MATH_BF16X6 (gbnf_trainer_create_mode): `live` is the bf16x6 blob, every sweep and the weight gradients have the range of
@@ -1951,6 +1958,24 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
     blocks += ((P.M + P.bm - 1) / P.bm) * P.nb;
   }
   t->grad_floats = goff;
+  // the update kernel's region table, in the order of the flat buffer (a RealNVP step without BatchNorm: its two regions are reserved)
+  std::vector<OptRegion> regions;
+  for (const TrStep& st : steps) {
+    if (st.has_norm) {
+      regions.push_back(OptRegion{const_cast<float*>(st.na), st.g_na, d});
+      regions.push_back(OptRegion{const_cast<float*>(st.nb), st.g_nb, d});
+    }
+    for (int q = 0; q < t->nnets; ++q)
+      for (int l = 0; l < st.net[q].n_layers; ++l) {
+        const TrLayer& L = st.net[q].layer[l];
+        regions.push_back(OptRegion{const_cast<float*>(L.W), L.gW, (int64_t)L.rows * L.cols});
+        regions.push_back(OptRegion{const_cast<float*>(L.b), L.gb, L.rows});
+      }
+    const bool bn = !glow && st.has_norm;
+    t->rmean_ptr.push_back(bn ? const_cast<float*>(st.mean) : nullptr);
+    t->rvar_ptr.push_back(bn ? const_cast<float*>(st.var) : nullptr);
+  }
+  t->n_regions = (int)regions.size();
   t->n_probs = (int)probs.size();
   t->wg_blocks = blocks;
   t->n_prep = (int)preps.size();
@@ -1994,6 +2019,9 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
   if (e == hipSuccess) e = hipMemcpy(t->prep_dev, preps.data(), sizeof(PrepProblem) * preps.size(), hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMalloc((void**)&t->frag_dev, (size_t)frag_off * 16);
   if (e == hipSuccess) e = hipMalloc((void**)&t->gmax_dev, sizeof(unsigned));
+  if (e == hipSuccess) e = hipMalloc((void**)&t->regions_dev, sizeof(OptRegion) * regions.size());
+  if (e == hipSuccess) e = hipMemcpy(t->regions_dev, regions.data(), sizeof(OptRegion) * regions.size(), hipMemcpyHostToDevice);
+  if (e == hipSuccess) e = hipMalloc((void**)&t->opt_partials_dev, sizeof(double) * OPT_MAX_PARTIALS);
   if (e == hipSuccess) e = hipMalloc((void**)&t->bn_part_dev, sizeof(float) * 2 * 64 * BN_CHUNKS);
   if (e == hipSuccess) {
     const void* fns[8] = {(const void*)train_kernel<GBNF_KIND_GLOW, 0, 1>, (const void*)train_kernel<GBNF_KIND_GLOW, 1, 1>,
@@ -2046,6 +2074,8 @@ int gbnf_trainer_destroy(gbnf_trainer* t) {
   if (t->prep_dev) (void)hipFree(t->prep_dev);
   if (t->frag_dev) (void)hipFree(t->frag_dev);
   if (t->gmax_dev) (void)hipFree(t->gmax_dev);
+  if (t->regions_dev) (void)hipFree(t->regions_dev);
+  if (t->opt_partials_dev) (void)hipFree(t->opt_partials_dev);
   if (t->bn_part_dev) (void)hipFree(t->bn_part_dev);
   if (t->probs_safe_dev) (void)hipFree(t->probs_safe_dev);
   if (t->own_dev) (void)hipFree(t->own_dev);
@@ -2543,6 +2573,29 @@ int gbnf_trainer_repair_count(const gbnf_trainer* t, int64_t* calls, int32_t res
   *calls = (int64_t)v;
   return GBNF_OK;
 }
+
+}  // extern "C"
+
+// What gbnf_opt.hip needs of a trainer.  The two halves of a repairing trainer bind the same tensors: the f16x3 half speaks for both.
+int gbnf::trainer_opt_view(const gbnf_trainer* t, TrainerOptView* out) {
+  if (!t || !out) return fail(GBNF_ERR_INVALID, "trainer_opt_view: null argument");
+  const gbnf_trainer* b = t->rep.f ? t->rep.f : t;
+  std::memset(out, 0, sizeof(*out));
+  out->regions_dev = b->regions_dev; out->n_regions = b->n_regions;
+  out->grad_floats = b->grad_floats; out->d = b->d; out->K = b->K;
+  out->partials_dev = b->opt_partials_dev;
+  out->batch_stats = needs_step_launches(b) ? 1 : 0;
+  if (out->batch_stats && (int)b->bmean_ptr.size() == b->K)
+    for (int k = 0; k < b->K && out->bn.n < OPT_MAX_BN_STEPS; ++k)
+      if (b->rmean_ptr[k] != nullptr && b->stats_bound[k]) {
+        const int i = out->bn.n++;
+        out->bn.mean[i] = b->rmean_ptr[k]; out->bn.var[i] = b->rvar_ptr[k];
+        out->bn.bmean[i] = b->bmean_ptr[k]; out->bn.bvar[i] = b->bvar_ptr[k];
+      }
+  return GBNF_OK;
+}
+
+extern "C" {
 
 // (tests) how the last forward / backward call of a trainer ran: launches of the register-chained kernels (1 = the whole sweep in one
 // launch, > 1 = one per step range of a batch-statistics BatchNorm sweep), 0 = the per-step kernels

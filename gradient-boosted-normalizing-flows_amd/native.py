@@ -34,6 +34,7 @@ ABI_SYMBOLS = (
     "gbnf_flow_validate", "gbnf_trainer_create", "gbnf_trainer_destroy", "gbnf_trainer_forward",
     "gbnf_trainer_grad_floats", "gbnf_trainer_workspace_bytes", "gbnf_trainer_backward", "gbnf_trainer_trace_floats",
     "gbnf_trainer_bind_batch_stats", "gbnf_trainer_set_batch_stats", "gbnf_trainer_create_mode", "gbnf_trainer_repair_count",
+    "gbnf_trainer_apply_update", "gbnf_trainer_step_workspace_bytes", "gbnf_trainer_nll_step",
     "gbnf_image_flow_create", "gbnf_image_flow_destroy", "gbnf_image_flow_info", "gbnf_image_flow_workspace_bytes",
     "gbnf_image_flow_forward", "gbnf_image_flow_prior", "gbnf_image_flow_eps_floats", "gbnf_image_flow_inverse",
     "gbnf_image_flow_numerics", "gbnf_image_flow_repair_counts", "gbnf_image_flow_create_mode", "gbnf_image_flow_actnorm_stats",
@@ -109,6 +110,17 @@ class NumericsStatus(C.Structure):
                 ("worst_rel_err", C.c_float), ("tolerance", C.c_float)]
 
 
+OPT_KIND = {"sgd": 0, "adamw": 1}      # GBNF_OPT_SGD / _ADAMW
+
+
+class _OptHyper(C.Structure):
+    """gbnf_opt_hyper (48 bytes)."""
+    _fields_ = [("kind", C.c_int32), ("reserved0", C.c_int32), ("step", C.c_int64),
+                ("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float),
+                ("weight_decay", C.c_float), ("max_grad_norm", C.c_float), ("bn_momentum", C.c_float),
+                ("reserved1", C.c_float)]
+
+
 _lib = None
 
 
@@ -172,6 +184,9 @@ def lib():
     L.gbnf_trainer_grad_floats.argtypes = [vp, C.POINTER(i64)]
     L.gbnf_trainer_workspace_bytes.argtypes = [vp, i64, C.POINTER(i64)]
     L.gbnf_trainer_backward.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]
+    L.gbnf_trainer_apply_update.argtypes = [vp, vp, vp, vp, C.POINTER(_OptHyper), vp, vp]
+    L.gbnf_trainer_step_workspace_bytes.argtypes = [vp, i64, C.POINTER(i64)]
+    L.gbnf_trainer_nll_step.argtypes = [vp, vp, i64, vp, i64, vp, vp, vp, C.POINTER(_OptHyper), vp, vp, i64, vp]
     L.gbnf_image_flow_create.argtypes = [C.POINTER(_ImageFlowDesc), C.POINTER(vp)]
     L.gbnf_image_flow_create_mode.argtypes = [C.POINTER(_ImageFlowDesc), i32, C.POINTER(vp)]
     L.gbnf_image_flow_actnorm_stats.argtypes = [vp, vp, vp, i64, i32, vp, vp, C.POINTER(i32), vp, i64, vp]
@@ -657,9 +672,62 @@ class NativeTrainer:
         if self.grad_floats != sum(self._sizes):
             raise GbnfError("gradient-buffer layout mismatch between the library and the binding")
         self._ws = None
+        self._step_ws = None
+        self.device = self._tensors[0].device
 
     def key(self):
         return tuple(t.data_ptr() for t in self._tensors)
+
+    def _hyper(self, state, lr, weight_decay=0.0, max_grad_norm=0.0, betas=(0.9, 0.999), eps=1e-8, bn_momentum=-1.0):
+        """The gbnf_opt_hyper of the NEXT update of ``state`` (its ``step`` + 1)."""
+        return _OptHyper(kind=OPT_KIND[state.kind], step=state.step + 1, lr=lr, beta1=betas[0], beta2=betas[1], eps=eps,
+                         weight_decay=weight_decay, max_grad_norm=max_grad_norm, bn_momentum=bn_momentum)
+
+    def apply_update(self, flat_grads, state, **hyper):
+        """clip_grad_norm_ + one optimiser step on the bound parameter tensors, in place, from a flat gradient buffer in the layout of
+        ``backward`` (gbnf_trainer_apply_update).  ``state``: an ``OptState`` of this trainer, advanced by one step.  ``hyper``: lr,
+        weight_decay, max_grad_norm, betas, eps.  -> stats (4,) device tensor: [1] gradient norm, [2] clip coefficient.  The parameters
+        change behind autograd's back: no version counter moves (BoostedFlow.training_step takes care of that)."""
+        import torch
+        _require_device_f32(flat_grads, "flat_grads")
+        if flat_grads.numel() != self.grad_floats:
+            raise GbnfError(f"flat_grads has {flat_grads.numel()} elements, expected {self.grad_floats}")
+        state.check(self)
+        h = self._hyper(state, **hyper)
+        stats = torch.zeros(4, dtype=torch.float32, device=flat_grads.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_trainer_apply_update(self.handle, ptr(flat_grads), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h),
+                                               ptr(stats), _stream_ptr()))
+        state.step += 1
+        return stats
+
+    def nll_step(self, x, state, rows=None, **hyper):
+        """One whole training step of this component on the device (gbnf_trainer_nll_step): [x[rows]] -> forward on the live parameters ->
+        NLL and its seed -> backward -> clip -> optimiser update, no host read in between.  ``rows``: int64 device indices into x
+        (repeats allowed) or None.  ``hyper`` as for ``apply_update``, plus bn_momentum (>= 0: batch-statistics mode also moves the
+        bound running statistics).  -> (stats (4,) device tensor: nll, gradient norm, clip coefficient, 0; the flat unclipped gradient)."""
+        import torch
+        _require_device_f32(x, "x")
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise GbnfError(f"x must be (n,{self.d}), got {tuple(x.shape)}")
+        n_x = n = x.shape[0]
+        if rows is not None:
+            if not isinstance(rows, torch.Tensor) or not rows.is_cuda or rows.dtype != torch.int64 or not rows.is_contiguous() or rows.dim() != 1:
+                raise GbnfError("rows must be a contiguous 1-d int64 tensor on the device")
+            n = rows.shape[0]
+        state.check(self)
+        h = self._hyper(state, **hyper)
+        nb = C.c_int64()
+        _check(lib().gbnf_trainer_step_workspace_bytes(self.handle, n, C.byref(nb)))
+        if self._step_ws is None or self._step_ws.numel() * 4 < nb.value or self._step_ws.device != x.device:
+            self._step_ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        flat = torch.empty(self.grad_floats, dtype=torch.float32, device=x.device)
+        stats = torch.zeros(4, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_trainer_nll_step(self.handle, ptr(x), n_x, ptr(rows), n, ptr(flat), ptr(state.exp_avg), ptr(state.exp_avg_sq),
+                                           C.byref(h), ptr(stats), ptr(self._step_ws), self._step_ws.numel() * 4, _stream_ptr()))
+        state.step += 1
+        return stats, flat
 
     def set_batch_stats(self, on):
         """RealNVP BatchNorm on batch statistics (True = the reference's train() mode) or running statistics (False)."""
@@ -730,6 +798,80 @@ class NativeTrainer:
             self.close()
         except Exception:
             pass
+
+
+class OptState:
+    """Caller-owned optimiser state of one trainer's parameters for ``NativeTrainer.apply_update`` / ``nll_step``: ``exp_avg`` and
+    ``exp_avg_sq`` as flat device tensors in the layout of the flat gradient buffer (None for SGD), ``step`` = updates taken so far,
+    ``kind`` = "adamw" | "sgd".  It maps one to one onto the state of a ``torch.optim.AdamW`` (``load_from`` / ``store_to``)."""
+
+    def __init__(self, trainer, kind="adamw", device=None):
+        import torch
+        if kind not in OPT_KIND:
+            raise GbnfError(f"OptState: kind must be one of {sorted(OPT_KIND)}, got {kind!r}")
+        self.kind = kind
+        self.step = 0
+        self.grad_floats = trainer.grad_floats
+        self._shapes = [(None if t is None else tuple(t.shape), size) for t, size in zip(trainer.params, trainer._sizes)]
+        self.exp_avg_device = device = trainer.device if device is None else device
+        self.exp_avg = self.exp_avg_sq = None
+        if kind == "adamw":
+            self.exp_avg = torch.zeros(self.grad_floats, dtype=torch.float32, device=device)
+            self.exp_avg_sq = torch.zeros(self.grad_floats, dtype=torch.float32, device=device)
+
+    def check(self, trainer):
+        if self.grad_floats != trainer.grad_floats:
+            raise GbnfError("OptState belongs to a trainer of another geometry")
+
+    def _views(self, flat):
+        out, off = [], 0
+        for shape, size in self._shapes:
+            out.append(None if shape is None or flat is None else flat[off:off + size].view(shape))
+            off += size
+        return out
+
+    def views(self):
+        """-> (exp_avg views, exp_avg_sq views), one per entry of ``trainer.params`` (None for reserved regions and for SGD)."""
+        return self._views(self.exp_avg), self._views(self.exp_avg_sq)
+
+    def load_from(self, optimizer, params):
+        """Take exp_avg / exp_avg_sq / step of every tensor of ``params`` (``trainer.params``; matched by identity) from a
+        ``torch.optim.AdamW``; a parameter the optimiser has no state for yet keeps zeros.  Steps must agree across parameters."""
+        import torch
+        if self.kind != "adamw":
+            raise GbnfError("OptState.load_from: only AdamW has state")
+        steps = set()
+        with torch.no_grad():
+            for p, m, v in zip(params, *self.views()):
+                st = optimizer.state.get(p) if p is not None else None
+                if not st:
+                    continue
+                m.copy_(st["exp_avg"])
+                v.copy_(st["exp_avg_sq"])
+                steps.add(int(st["step"]))
+        if len(steps) > 1:
+            raise GbnfError(f"OptState.load_from: the parameters are at different steps {sorted(steps)}")
+        self.step = steps.pop() if steps else 0
+        return self
+
+    def store_to(self, optimizer, params):
+        """The other direction: write this state into the ``torch.optim.AdamW``'s per-parameter state (created where missing)."""
+        import torch
+        if self.kind != "adamw":
+            raise GbnfError("OptState.store_to: only AdamW has state")
+        with torch.no_grad():
+            for p, m, v in zip(params, *self.views()):
+                if p is None:
+                    continue
+                st = optimizer.state[p]
+                if "exp_avg" in st:
+                    st["exp_avg"].copy_(m)
+                    st["exp_avg_sq"].copy_(v)
+                else:
+                    st["exp_avg"], st["exp_avg_sq"] = m.clone(), v.clone()
+                old = st.get("step")
+                st["step"] = torch.full_like(old, float(self.step)) if isinstance(old, torch.Tensor) else torch.tensor(float(self.step))
+        return self
 
 
 def saturation_count(reset=False):

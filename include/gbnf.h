@@ -434,6 +434,63 @@ int gbnf_trainer_backward(const gbnf_trainer* trainer, const float* x, int64_t n
                           const float* g_ldj, float* g_x, float* grads, void* workspace, int64_t workspace_bytes,
                           void* stream);
 
+/* ---- the rest of the step: loss seed, gradient-norm clip and the optimiser, on the device -------------------------------
+ * Between and behind the two calls above the reference's driver runs eager PyTorch: the NLL and its autograd seed, clip_grad_norm_,
+ * optimizer.step() (density_experiment.py:340-374).  These calls do that on the trainer's stream, on the LIVE tensors the trainer
+ * binds: the next gbnf_trainer_forward sees the updated parameters with no host work.  No call reads the device or synchronises.
+ * The optimiser state is caller-owned like every buffer of this ABI: two flat DEVICE buffers of gbnf_trainer_grad_floats floats in the
+ * layout of the gradient buffer (they map one to one onto torch.optim.AdamW's exp_avg / exp_avg_sq), and the update's index `step`.
+ * It survives re-creating the trainer.  Replaces: optim.AdamW(lr, weight_decay) with default betas / eps or optim.SGD(lr,
+ * weight_decay) without momentum (optimization/optimizers.py:54-65); a component that is not being trained gets lr = 0
+ * (update_learning_rates, density_experiment.py:511-513): its parameters stay bit-identical while its moments move, as in torch. */
+enum { GBNF_OPT_SGD = 0, GBNF_OPT_ADAMW = 1 };
+typedef struct gbnf_opt_hyper {      /* 48 bytes; passed by pointer, read on the host at call time */
+  int32_t kind;                      /* GBNF_OPT_*                                                   */
+  int32_t reserved0;
+  int64_t step;                      /* 1-based index of THIS update (AdamW bias correction)         */
+  float lr, beta1, beta2, eps;       /* each taken as the shortest decimal that rounds to the float: 0.999f means 0.999, */
+                                     /* so that 1 - beta2 is torch's (computed from the Python float) to the last bit    */
+  float weight_decay;                /* AdamW: decoupled (p *= 1 - lr wd); SGD: g += wd p            */
+  float max_grad_norm;               /* <= 0: no clipping                                            */
+  float bn_momentum;                 /* < 0: running statistics untouched (see nll_step)             */
+  float reserved1;
+} gbnf_opt_hyper;
+/* stats_dev: 4 floats of DEVICE memory: [0] nll (nll_step only; apply_update leaves it alone), [1] total gradient 2-norm,
+ * [2] clip coefficient applied, [3] 0 */
+
+/* Replaces: torch.nn.utils.clip_grad_norm_(model.parameters(), max_grad_norm) + optimizer.step() (density_experiment.py:363-364,
+ * 374) for this component, from a flat gradient buffer in the gbnf_trainer_grad_floats layout (reserved RealNVP regions: zero, no
+ * tensor behind them, skipped):
+ *   norm = ||grads||_2 over all entries -> stats[1];  coef = min(1, max_grad_norm / (norm + 1e-6)) (1 without clipping) -> stats[2];
+ *   g = coef * grads[i], then in torch's order
+ *     AdamW  p *= 1 - lr wd;  m = b1 m + (1 - b1) g;  v = b2 v + (1 - b2) g^2;
+ *            p -= lr / (1 - b1^step) * m / (sqrt(v) / sqrt(1 - b2^step) + eps)      (bias corrections: host, double precision)
+ *     SGD    p -= lr (g + wd p)                                                      (exp_avg / exp_avg_sq may be NULL)
+ * `grads` is read only: it holds the unclipped gradient afterwards.  The norm is summed per workgroup and re-added in a fixed order in
+ * double precision: bit-identical from run to run for the same buffer.  GBNF_ERR_INVALID (nothing launched): unknown kind, AdamW with
+ * step <= 0 or without state.  Two calls on ONE trainer must not run concurrently (the partial sums live in the trainer). */
+int gbnf_trainer_apply_update(const gbnf_trainer* trainer, const float* grads, float* exp_avg, float* exp_avg_sq,
+                              const gbnf_opt_hyper* hyper, float* stats_dev, void* stream);
+/* Bytes of caller-owned DEVICE scratch one gbnf_trainer_nll_step over n rows needs: the gathered rows, z, ldj, the trace, g_z, g_ldj,
+ * the backward workspace and the reductions' partial sums. */
+int gbnf_trainer_step_workspace_bytes(const gbnf_trainer* trainer, int64_t n, int64_t* bytes);
+/* Replaces: one iteration of density_experiment.py:340-374 for this component -- compute_kl_pq_loss (:606-674), loss.backward(),
+ * clip_grad_norm_, optimizer.step() -- for a trainer of any math mode:
+ *   1. rows != NULL: the batch is x[rows] (:643-644; `rows`: n int64 DEVICE indices into the n_x rows of x, repeats allowed, an index
+ *      outside [0, n_x) is clamped); rows == NULL: x itself, n == n_x required;
+ *   2. gbnf_trainer_forward on the live parameters with the trace in `workspace`;
+ *   3. nll = mean_i(0.5 sum_j z_ij^2 + 0.5 d log 2 pi - ldj_i)  (:647-649, utils/distributions.py:44-60) and its seed g_z = z / n,
+ *      g_ldj = -1 / n;
+ *   4. `grads` is zeroed, then gbnf_trainer_backward with that trace (no g_x): it holds this step's unclipped gradient afterwards;
+ *   5. gbnf_trainer_apply_update;  6. stats_dev[0] = nll.
+ * Batch-statistics mode (gbnf_trainer_set_batch_stats(1), n >= 2) with bn_momentum >= 0: behind the forward every step with bound
+ * statistics gets  running = bn_momentum * running + (1 - bn_momentum) * batch  on its bound running mean and variance
+ * (models/layers.py:339-344).  GBNF_ERR_INVALID (nothing launched): the cases of apply_update, a workspace smaller than
+ * gbnf_trainer_step_workspace_bytes(n), rows == NULL with n != n_x, n < 1. */
+int gbnf_trainer_nll_step(const gbnf_trainer* trainer, const float* x, int64_t n_x, const int64_t* rows, int64_t n,
+                          float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper,
+                          float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---------------------------------------------------------------------------------------------------------------
  * Image components (BASELINE.json configs[3]): density evaluation of one multi-scale image
  * Glow, models/glow.py:92-110 with the image branches of FlowNet / FlowStep (:192-252, :317-342).  All arrays are HOST
