@@ -516,15 +516,20 @@ class BoostedFlow(nn.Module):
                 fixed_ll = full_ll
         return new_ll, fixed_ll, full_ll
 
-    def update_rho(self, data_loader):
+    def update_rho(self, data_loader, fused=False):
         """models/boosted_flow.py:141-207 (approximate branch).  The reference's log line references an
         undefined ``g_nll`` and so raises NameError whenever rho_iters > 0; the update rule
-        itself is reproduced, the broken log message is not."""
+        itself is reproduced, the broken log message is not.
+        ``fused=True``: every iteration is one library call (gbnf_mixture_rho_step: one flow launch for all components, the
+        recursion, the gradient and the clamped update of ``self.rho`` on the device); nothing is read back up to iteration
+        ``min_iters``, where the reference cannot stop, and the call's 4 statistics per iteration after that."""
         if self.component == 0 and not self.all_trained:
             return
         if getattr(self.args, "rho_iters", 0) == 0:
             return
         self.eval()
+        if fused and self.component > 0:
+            return self._update_rho_fused(data_loader)
         with torch.no_grad():
             tolerance, min_iters = 0.001, 10
             init_step, max_iters = self.args.rho_lr, self.args.rho_iters
@@ -546,6 +551,33 @@ class BoostedFlow(nn.Module):
                 prev_rho = rho
                 if batch_id > min_iters and (batch_id > max_iters or dif < tolerance):
                     break
+
+    @torch.no_grad()
+    def _update_rho_fused(self, data_loader):
+        """The loop of ``update_rho`` on gbnf_mixture_rho_step, for ``self.component`` >= 1."""
+        c = int(self.component)
+        tolerance, min_iters = 0.001, 10
+        init_step, max_iters = self.args.rho_lr, self.args.rho_iters
+        rho = self.rho
+        if rho.dtype != torch.float32 or not rho.is_contiguous():
+            raise ValueError("update_rho(fused=True) writes self.rho in place: it must be contiguous float32")
+        data_iter = iter(data_loader)
+        for batch_id in range(max_iters):
+            try:
+                (x, _) = next(data_iter)
+            except StopIteration:
+                data_iter = iter(data_loader)
+                (x, _) = next(data_iter)
+            x = x.detach().to(rho.device).contiguous().float()
+            self._check_ready(x)
+            for k in range(c + 1):
+                self._ensure_actnorm(x, k)
+            with torch.cuda.device(x.device):
+                stats = self.native_mixture(c + 1).rho_step(x, c, rho, init_step / (0.05 * batch_id + 1))
+            # the kernel wrote rho behind autograd's back: move its version counter as training_step does for parameters
+            torch.autograd.graph.increment_version([rho])
+            if batch_id > min_iters and (batch_id > max_iters or stats.tolist()[3] < tolerance):
+                break
 
     # ------------------------------------------------------------------ native handles
     def _component_tensors(self, c):
@@ -830,7 +862,7 @@ class BoostedFlow(nn.Module):
         return z, ldj
 
     def training_step(self, x, *, lr, weight_decay=0.0, max_grad_norm=0.0, optimizer="adamw", betas=(0.9, 0.999), eps=1e-8,
-                      resample=None, beta=1.0):
+                      resample=None, beta=1.0, uniforms=None):
         """The body of one iteration of the reference's training loop (density_experiment.py:340-384) for ``self.component``, in one
         library call (gbnf_trainer_nll_step): compute_kl_pq_loss (:606-674) -- for a boosted component beyond the first on the batch
         resampled with ``boosting_weights`` and the CALLER's RNG (``torch.multinomial``) --, ``nll.backward()``, ``clip_grad_norm_``
@@ -839,7 +871,12 @@ class BoostedFlow(nn.Module):
         defaults to ``self.component > 0 or self.all_trained``.  ActNorm's data-dependent initialisation and the BatchNorm mode follow
         ``component_forward``; in train() mode the running statistics are updated on the device.  Returns 0-dim DEVICE tensors (nothing
         is read back): ``nll``, ``grad_norm``, ``clip_coef`` and, when resampled, ``G_nll``.  The optimiser state is kept per component
-        (``self.opt_state(c)``: a ``native.OptState``).  No ``p.grad`` is written."""
+        (``self.opt_state(c)``: a ``native.OptState``).  No ``p.grad`` is written.
+        ``uniforms``: the draws of the resample.  None (the default) keeps ``torch.multinomial`` and three library calls.  A (n,) float32
+        device tensor of values in [0,1), or True for ``torch.rand(n, device=...)``, takes the boosted step in ONE library call
+        (gbnf_boosted_nll_step: mixture log-density, weights, inverse-CDF resample on these uniforms, the step); the result gains ``ess``,
+        the effective sample size of the weights, and all five entries are views of one stats tensor.  The first component has nothing
+        to resample from and ignores it."""
         self._check_ready(x)
         c = int(self.component)
         x = x.contiguous().float()
@@ -847,6 +884,9 @@ class BoostedFlow(nn.Module):
         if resample is None:
             resample = bool(self.component > 0 or self.all_trained)
         out, rows = {}, None
+        if resample and uniforms is not None and c > 0:
+            return self._boosted_training_step(x, c, uniforms, beta, optimizer,
+                                               dict(lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm, betas=betas, eps=eps))
         if resample:
             with torch.no_grad():
                 w, G = self.boosting_weights(x, beta)
@@ -869,6 +909,31 @@ class BoostedFlow(nn.Module):
         torch.autograd.graph.increment_version(params + buffers if batch_stats else params)
         out.update(nll=stats[0], grad_norm=stats[1], clip_coef=stats[2])
         return out
+
+    def _boosted_training_step(self, x, c, uniforms, beta, optimizer, hyper):
+        """``training_step`` of component c > 0 on given uniforms: one gbnf_boosted_nll_step."""
+        n = x.shape[0]
+        u = torch.rand(n, device=x.device) if uniforms is True else uniforms
+        if not isinstance(u, torch.Tensor) or u.shape != (n,) or u.dtype != torch.float32 or u.device != x.device:
+            raise ValueError(f"uniforms must be True or a ({n},) float32 tensor on {x.device}")
+        for k in range(c):
+            self._ensure_actnorm(x, k)
+        self._guard(x, range(c))
+        with torch.cuda.device(x.device):
+            mixture = self.native_mixture(c)
+            trainer = self.native_trainer(c)
+            batch_stats = bool(self.training and trainer.has_batch_stats)
+            trainer.set_batch_stats(batch_stats)
+            trainer.forward_serial = getattr(trainer, "forward_serial", 0) + 1     # (the bound batch statistics are overwritten)
+            state = self.opt_state(c, optimizer)
+            momentum = -1.0
+            if batch_stats:
+                momentum = next(float(m[2].momentum) for m in self.flows[c].flow_param if len(m) > 2 and m[2] is not None)
+            stats, _, _ = trainer.boosted_nll_step(mixture, c, self.rho.contiguous().float(), x, u.contiguous(), state, beta=beta,
+                                                   bn_momentum=momentum, **hyper)
+        params, buffers, _ = self._component_tensors(c)
+        torch.autograd.graph.increment_version(params + buffers if batch_stats else params)
+        return {"G_nll": stats[4], "ess": stats[5], "nll": stats[0], "grad_norm": stats[1], "clip_coef": stats[2]}
 
     def opt_state(self, c, optimizer="adamw"):
         """The ``native.OptState`` ``training_step`` keeps for component c (created on first use; another ``optimizer`` kind or a

@@ -178,6 +178,11 @@ def main(argv=None):
     objs.append(opt_o)
     if args.force or not newer(opt_o, [opt_src, opt_hdr, hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", opt_src, "-o", opt_o])
+    # what boosting adds to a training step (weighted resampling, the one-call boosted step, one update_rho iteration): gbnf_boost.hip
+    boost_o, boost_src = os.path.join(OBJ, "gbnf_boost.o"), os.path.join(HERE, "gbnf_boost.hip")
+    objs.append(boost_o)
+    if args.force or not newer(boost_o, [boost_src, opt_hdr, hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", boost_src, "-o", boost_o])
     for v in read_variants():
         o = os.path.join(OBJ, "v_" + "_".join(str(a) for a in v) + ".o")
         objs.append(o)

@@ -155,6 +155,13 @@ unsigned* training_saturation_counter() {
   return p ? p + 2 : nullptr;          // 64-bit word [1] (SAT_MARKS = 2: words [0] and [1] are counters, the launch marks follow)
 }
 
+int mixture_shape(const gbnf_mixture* mix, int* n_components, int* d) {
+  if (!mix || mix->flows.empty()) return fail(GBNF_ERR_INVALID, "mixture_shape: mix is null or empty");
+  *n_components = (int)mix->flows.size();
+  *d = mix->flows[0]->d;
+  return GBNF_OK;
+}
+
 // ---- launch-policy knobs (gbnf_tuning_set / _get; initialised from the environment at first use)
 struct Tuning {
   std::atomic<int> force_nt{0}, wg_pairs{-1}, repair{1}, nt2_min_waves{1024}, check_every{256}, check_tolerance_e9{2500};

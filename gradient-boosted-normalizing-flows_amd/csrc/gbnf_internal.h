@@ -20,6 +20,9 @@ unsigned* saturation_counter();
 // reports their sum, gbnf_training_saturation_count() this word alone.
 unsigned* training_saturation_counter();
 
+// How many components a mixture holds and their feature count, for the translation units that do not see the handle (gbnf_boost.hip)
+int mixture_shape(const gbnf_mixture* mix, int* n_components, int* d);
+
 // Kernel-variant key only (not a descriptor value): the activation differs between the steps / nets of a component
 // (`--coupling_network random` in the reference); the kernel reads it per step and net from the step header.
 constexpr int GBNF_ACT_PER_STEP = 3;

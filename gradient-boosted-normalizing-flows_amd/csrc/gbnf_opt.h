@@ -31,5 +31,8 @@ struct TrainerOptView {
   OptBnTable bn;
 };
 int trainer_opt_view(const gbnf_trainer* t, TrainerOptView* out);
+// What every call that ends in an update refuses before it launches anything (GBNF_ERR_INVALID: null hyper, unknown kind, AdamW with
+// step <= 0 or without state); `fn` names the entry point in the message.  gbnf_opt.hip
+int check_hyper(const char* fn, const gbnf_opt_hyper* h, const float* m, const float* v);
 
 }  // namespace gbnf

@@ -197,7 +197,7 @@ static double decimal_meant(float f) {
   return (double)f;
 }
 
-static int check_hyper(const char* fn, const gbnf_opt_hyper* h, const float* m, const float* v) {
+int check_hyper(const char* fn, const gbnf_opt_hyper* h, const float* m, const float* v) {
   if (h == nullptr) return fail(GBNF_ERR_INVALID, "%s: hyper is null", fn);
   if (h->kind != GBNF_OPT_SGD && h->kind != GBNF_OPT_ADAMW) return fail(GBNF_ERR_INVALID, "%s: unknown optimiser kind %d", fn, h->kind);
   if (h->kind == GBNF_OPT_ADAMW) {

@@ -41,6 +41,8 @@ ABI_SYMBOLS = (
     "gbnf_comm_unique_id", "gbnf_comm_create", "gbnf_comm_destroy", "gbnf_comm_info", "gbnf_mixture_group_log_prob",
     "gbnf_group_graph_create", "gbnf_group_graph_launch", "gbnf_group_graph_destroy",
     "gbnf_flow_numerics", "gbnf_mixture_numerics", "gbnf_tuning_set", "gbnf_tuning_get",
+    "gbnf_resample_workspace_bytes", "gbnf_resample_rows", "gbnf_boosted_step_workspace_bytes", "gbnf_boosted_nll_step",
+    "gbnf_mixture_rho_step",
 )
 
 
@@ -168,6 +170,11 @@ def lib():
     L.gbnf_mixture_log_prob.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
     L.gbnf_actnorm_init.argtypes = [vp, i64, i32, C.c_float, vp, vp, vp]
     L.gbnf_boosting_weights.argtypes = [vp, i64, C.c_float, vp, vp]
+    L.gbnf_resample_workspace_bytes.argtypes = [i64, C.POINTER(i64)]
+    L.gbnf_resample_rows.argtypes = [vp, i64, vp, i64, vp, vp, i64, vp]
+    L.gbnf_boosted_step_workspace_bytes.argtypes = [vp, i32, vp, i64, C.POINTER(i64)]
+    L.gbnf_boosted_nll_step.argtypes = [vp, i32, vp, C.c_float, vp, vp, i64, vp, vp, vp, vp, C.POINTER(_OptHyper), vp, vp, vp, i64, vp]
+    L.gbnf_mixture_rho_step.argtypes = [vp, vp, i64, i32, vp, C.c_float, vp, vp, vp]
     L.gbnf_flow_validate.argtypes = [C.POINTER(_FlowDesc)]
     L.gbnf_flow_numerics.argtypes = [vp, C.POINTER(NumericsStatus)]
     L.gbnf_mixture_numerics.argtypes = [vp, C.POINTER(NumericsStatus)]
@@ -673,6 +680,7 @@ class NativeTrainer:
             raise GbnfError("gradient-buffer layout mismatch between the library and the binding")
         self._ws = None
         self._step_ws = None
+        self._boost_ws = None
         self.device = self._tensors[0].device
 
     def key(self):
@@ -728,6 +736,40 @@ class NativeTrainer:
                                            C.byref(h), ptr(stats), ptr(self._step_ws), self._step_ws.numel() * 4, _stream_ptr()))
         state.step += 1
         return stats, flat
+
+    def boosted_nll_step(self, mixture, n_fixed, rho, x, u, state, beta=1.0, want_rows=False, **hyper):
+        """One whole BOOSTED training step of this component on the device (gbnf_boosted_nll_step): the mixture log-density of the
+        ``n_fixed`` fixed components of ``mixture`` (a ``NativeMixture``) under ``rho`` -> boosting weights -> the weighted resample on the
+        caller's uniforms ``u`` ((n,) float32 in [0,1), on the device) -> ``nll_step`` on the drawn rows, no host read in between.
+        ``hyper`` as for ``nll_step``.  -> (stats (8,) device tensor: nll, gradient norm, clip coefficient, 0, G_nll, effective sample
+        size, bad-weight count, 0; the flat unclipped gradient; the drawn rows (n,) int64 when ``want_rows``, else None)."""
+        import torch
+        _require_device_f32(x, "x")
+        _require_device_f32(u, "u")
+        _require_device_f32(rho, "rho")
+        if x.dim() != 2 or x.shape[1] != self.d or x.shape[0] < 1:
+            raise GbnfError(f"x must be (n,{self.d}) with n >= 1, got {tuple(x.shape)}")
+        n = x.shape[0]
+        if u.dim() != 1 or u.shape[0] != n:
+            raise GbnfError(f"u must be ({n},), one uniform per draw, got {tuple(u.shape)}")
+        n_fixed = int(n_fixed)
+        if rho.dim() != 1 or rho.numel() < n_fixed:
+            raise GbnfError("rho shorter than n_fixed")
+        state.check(self)
+        h = self._hyper(state, **hyper)
+        nb = C.c_int64()
+        _check(lib().gbnf_boosted_step_workspace_bytes(mixture.handle, n_fixed, self.handle, n, C.byref(nb)))
+        if self._boost_ws is None or self._boost_ws.numel() * 8 < nb.value or self._boost_ws.device != x.device:
+            self._boost_ws = torch.empty((nb.value + 7) // 8, dtype=torch.float64, device=x.device)
+        flat = torch.empty(self.grad_floats, dtype=torch.float32, device=x.device)
+        stats = torch.zeros(8, dtype=torch.float32, device=x.device)
+        rows = torch.empty(n, dtype=torch.int64, device=x.device) if want_rows else None
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_boosted_nll_step(mixture.handle, n_fixed, ptr(rho), float(beta), self.handle, ptr(x), n, ptr(u), ptr(flat),
+                                           ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(rows),
+                                           ptr(self._boost_ws), self._boost_ws.numel() * 8, _stream_ptr()))
+        state.step += 1
+        return stats, flat, rows
 
     def set_batch_stats(self, on):
         """RealNVP BatchNorm on batch statistics (True = the reference's train() mode) or running statistics (False)."""
@@ -1055,6 +1097,28 @@ class NativeMixture:
             C.c_void_p(out.data_ptr() if n else 0), _stream_ptr()))
         return out, ll_out
 
+    def rho_step(self, x, component, rho, step_size):
+        """One iteration of ``update_rho`` for ``component`` >= 1 on the device (gbnf_mixture_rho_step): the log-densities of components
+        [0, component], the reference's un-normalised recursion, grad = mean(fixed_ll - new_ll) and
+        ``rho[component] = clamp(rho[component] - step_size * grad, 0.01, 100)`` written IN PLACE into ``rho`` (a contiguous float32
+        device tensor; no version counter moves).  -> stats (4,) device tensor: grad, rho before, rho after, |after - before|.  The
+        (component + 1, n) log-likelihood table of the call stays in ``self.rho_ll``."""
+        import torch
+        _require_device_f32(x, "x")
+        _require_device_f32(rho, "rho")
+        component = int(component)
+        if x.dim() != 2 or x.shape[1] != self.d or x.shape[0] < 1:
+            raise GbnfError(f"x must be (n,{self.d}) with n >= 1, got {tuple(x.shape)}")
+        if rho.dim() != 1 or rho.numel() <= component:
+            raise GbnfError("rho has no entry for this component")
+        n = x.shape[0]
+        self.rho_ll = torch.empty((component + 1, n), dtype=torch.float32, device=x.device)
+        stats = torch.zeros(4, dtype=torch.float32, device=x.device)
+        _check(lib().gbnf_mixture_rho_step(self.handle, C.c_void_p(x.data_ptr()), n, component, C.c_void_p(rho.data_ptr()),
+                                           float(step_size), C.c_void_p(self.rho_ll.data_ptr()), C.c_void_p(stats.data_ptr()),
+                                           _stream_ptr()))
+        return stats
+
     def close(self):
         if getattr(self, "handle", None):
             lib().gbnf_mixture_destroy(self.handle)
@@ -1253,3 +1317,20 @@ def boosting_weights(G, beta=1.0):
     _check(lib().gbnf_boosting_weights(C.c_void_p(G.data_ptr()), G.numel(), float(beta), C.c_void_p(w.data_ptr()),
                                        _stream_ptr()))
     return w
+
+
+def resample_rows(w, u):
+    """Multinomial resampling with replacement by inverse CDF (gbnf_resample_rows): ``w`` (n,) weights and ``u`` (m,) uniforms in [0,1),
+    both float32 on the device -> rows (m,) int64, rows[i] = the smallest j with u[i] * sum(w) < cumsum(max(w, 0))[j] in float64."""
+    import torch
+    _require_device_f32(w, "w")
+    _require_device_f32(u, "u")
+    if w.dim() != 1 or w.numel() < 1 or u.dim() != 1 or u.numel() < 1:
+        raise GbnfError("w must be (n,) and u (m,) with n, m >= 1")
+    nb = C.c_int64()
+    _check(lib().gbnf_resample_workspace_bytes(w.numel(), C.byref(nb)))
+    cdf = torch.empty(nb.value // 8, dtype=torch.float64, device=w.device)
+    rows = torch.empty(u.numel(), dtype=torch.int64, device=w.device)
+    _check(lib().gbnf_resample_rows(C.c_void_p(w.data_ptr()), w.numel(), C.c_void_p(u.data_ptr()), u.numel(),
+                                    C.c_void_p(rows.data_ptr()), C.c_void_p(cdf.data_ptr()), nb.value, _stream_ptr()))
+    return rows

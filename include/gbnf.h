@@ -333,8 +333,23 @@ int gbnf_actnorm_init(const float* z, int64_t n, int32_t d, float scale, float* 
  * mixture log-density G (n,) of the fixed components:
  *   w = softmax(-G) (utils/utilities.py:12-14);  w = w^beta;  if max(w) > 0.1: w = clamp(w, 0.01, 0.1);
  *   if sum(w) != 1: w /= sum(w).
- * G and w_out are DEVICE buffers of n floats.  (The multinomial resampling that follows stays with the caller's RNG.) */
+ * G and w_out are DEVICE buffers of n floats.  (The multinomial resampling that follows: gbnf_resample_rows, on the caller's
+ * uniforms.) */
 int gbnf_boosting_weights(const float* G, int64_t n, float beta, float* w_out, void* stream);
+
+/* Replaces: reweighted_idx = torch.multinomial(weights, N, replacement=True) of compute_kl_pq_loss (density_experiment.py:643) --
+ * m draws with replacement from n rows in proportion to w, by inverse CDF on the CALLER's uniforms u (m values in [0,1): the RNG
+ * stays outside the library like `eps` of gbnf_image_flow_inverse, so a draw is reproducible and testable):
+ *   cdf_j = sum_{k <= j} max(w_k, 0)  (a non-finite w_k counts 0), summed in double precision in a fixed order -- no atomics,
+ *   bit-identical from run to run --;  T = cdf_{n-1};  rows[i] = the smallest j with (double)u[i] * T < cdf_j.
+ * A row of zero weight is never drawn, and every index written lies in [0, n) whatever u and w hold: out of contract (u[i] >= 1 or
+ * NaN) a draw takes the last row of positive weight, and row i % n when no row has any (T == 0).  w (n), u (m): DEVICE floats; rows (m):
+ * DEVICE int64, what gbnf_trainer_nll_step takes; workspace: gbnf_resample_workspace_bytes(n) of DEVICE memory (the n-entry double
+ * cdf, 8 n rounded up to 256), 8-byte aligned.  Two launches: a one-workgroup scan, a binary search per draw.
+ * GBNF_ERR_INVALID (nothing launched): a null pointer, n < 1, m < 1, a workspace that is too small. */
+int gbnf_resample_workspace_bytes(int64_t n, int64_t* bytes);
+int gbnf_resample_rows(const float* w, int64_t n, const float* u, int64_t m, int64_t* rows, void* workspace, int64_t workspace_bytes,
+                       void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Training path: what loss.backward() / optimizer.step() of density_experiment.py:366-374 do
@@ -490,6 +505,40 @@ int gbnf_trainer_step_workspace_bytes(const gbnf_trainer* trainer, int64_t n, in
 int gbnf_trainer_nll_step(const gbnf_trainer* trainer, const float* x, int64_t n_x, const int64_t* rows, int64_t n,
                           float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper,
                           float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- boosting: the step of a component beyond the first, and the mixture weight behind it --------------------------------------
+ * Replaces: compute_kl_pq_loss for a boosted component (density_experiment.py:609-653) followed by loss.backward(), clip_grad_norm_
+ * and optimizer.step() (:361-374) for the component being trained, in ONE call on `stream`, with no host read and no synchronisation:
+ *   1. gbnf_mixture_log_prob over components [0, n_fixed) of `fixed` (:612-622; numerics guard and repair pass included) -> G;
+ *   2. the gbnf_boosting_weights arithmetic on G (:624-640) -> w;
+ *   3. gbnf_resample_rows of w on the caller's uniforms u (n DEVICE floats in [0,1)) (:643) -> rows;
+ *   4. gbnf_trainer_nll_step on x (n rows) with those rows (:644-653, :361-374).
+ * stats_dev: 8 floats of DEVICE memory: [0..3] as gbnf_trainer_nll_step writes them; [4] G_nll = -mean(G) and [5] the effective sample
+ * size (sum w)^2 / sum w^2, both summed in double precision in a fixed order; [6] how many weights were negative or non-finite (0 on
+ * healthy input); [7] 0.  rows_out: n DEVICE int64 that receive the drawn rows, or NULL.  workspace: caller-owned DEVICE scratch of
+ * gbnf_boosted_step_workspace_bytes bytes -- the nll_step workspace, the (n_fixed, n) log-likelihood table, G, w, the cdf and the rows,
+ * each 256-byte aligned.  GBNF_ERR_INVALID (nothing launched): everything gbnf_trainer_nll_step refuses, n_fixed < 1 or more than
+ * `fixed` holds, a mixture whose d differs from the trainer's, a null u, x or rho_dev, a short workspace.  The FIRST component has no
+ * fixed mixture (:655-661): it keeps gbnf_trainer_nll_step. */
+int gbnf_boosted_step_workspace_bytes(const gbnf_mixture* fixed, int32_t n_fixed, const gbnf_trainer* trainer, int64_t n,
+                                      int64_t* bytes);
+int gbnf_boosted_nll_step(const gbnf_mixture* fixed, int32_t n_fixed, const float* rho_dev, float beta, const gbnf_trainer* trainer,
+                          const float* x, int64_t n, const float* u, float* grads, float* exp_avg, float* exp_avg_sq,
+                          const gbnf_opt_hyper* hyper, float* stats_dev, int64_t* rows_out, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
+/* Replaces: ONE iteration of BoostedFlow.update_rho (models/boosted_flow.py:119-207, the approximate branch) for `component` >= 1 of a
+ * mixture that holds at least components [0, component]: one gbnf_mixture_component_log_prob launch for all of them into
+ * ll_workspace ((component + 1, n) DEVICE floats, also an output), then per row
+ *   fixed_ll = ll_0;  for c = 1 .. component - 1:  fixed_ll = LSE(log(1 - rho[c]) + fixed_ll, log(rho[c]) + ll_c)
+ * -- the reference's UN-normalised recursion (:124-137), NaN for rho[c] > 1 included --, new_ll = ll_component,
+ *   grad = mean(fixed_ll - new_ll)                                        (summed per workgroup, re-added in a fixed order in double)
+ *   rho[component] = min(max(rho[component] - step_size * grad, 0.01), 100)   (:193-199), written in place on the DEVICE buffer.
+ * Only entry `component` of rho_dev is written, and the recursion never reads it.  stats_dev: 4 DEVICE floats [grad, rho before,
+ * rho after, |after - before|].  No host read, no synchronisation; the step-size schedule and the stopping rule (:193, :200-204) stay with
+ * the caller.  The partial sums live in a per-device buffer of the library: two calls on one device must not run concurrently. */
+int gbnf_mixture_rho_step(const gbnf_mixture* mix, const float* x, int64_t n, int32_t component, float* rho_dev, float step_size,
+                          float* ll_workspace, float* stats_dev, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Image components (BASELINE.json configs[3]): density evaluation of one multi-scale image

@@ -1,14 +1,16 @@
 #!/usr/bin/env python3
-"""One boosted training step of density_experiment.py:340-384 two ways, in the same process on the same model (MINIBOONE Glow, the model,
+"""One boosted training step of density_experiment.py:340-384 three ways, in the same process on the same model (MINIBOONE Glow, the model,
 batch sizes and warm-up of tools/bench_boosted_step.py):
 
   (a) module   the drop-in module as the reference's loop drives it: boosting_weights, torch.multinomial, the row gather, the recorded
                forward, the NLL in torch ops, loss.backward(), clip_grad_norm_, torch.optim.AdamW
   (b) fused    BoostedFlow.training_step: boosting_weights + torch.multinomial, then ONE library call (gather, forward, loss seed,
                backward, gradient norm, clip, AdamW on the live tensors: gbnf_trainer_nll_step)
+  (c) onecall  BoostedFlow.training_step(uniforms=True): torch.rand, then ONE library call for all of it (mixture log-density, weights,
+               inverse-CDF resample, and the step of (b): gbnf_boosted_nll_step)
 
 Wall time per step (host clock around a window that ends in a synchronise) and GPU time between two events around the same window,
-in alternating rounds of the two paths; one JSON line.
+in alternating rounds of the paths; one JSON line.
 
     python tools/bench_fused_step.py [--batch 512] [--steps 200] [--rounds 5] [--components 4]
 """
@@ -75,7 +77,10 @@ def main():
         torch.cuda.synchronize()
         return (time.perf_counter() - t0) / a.steps * 1e3, ev[0].elapsed_time(ev[1]) / a.steps
 
-    paths = {"module": module_step, "fused": fused_step}
+    def onecall_step():
+        m.training_step(x, lr=LR, weight_decay=WEIGHT_DECAY, max_grad_norm=MAX_GRAD_NORM, uniforms=True)
+
+    paths = {"module": module_step, "fused": fused_step, "onecall": onecall_step}
     for fn in paths.values():
         for _ in range(20):
             fn()
@@ -83,7 +88,8 @@ def main():
     for _ in range(a.rounds):                    # alternating: a drift of the machine hits both paths alike
         for k, fn in paths.items():
             res[k].append(window(fn))
-    out = {"metric": "boosted training step, MINIBOONE Glow: module path (clip_grad_norm_ + torch.optim.AdamW) vs BoostedFlow.training_step",
+    out = {"metric": "boosted training step, MINIBOONE Glow: module path (clip_grad_norm_ + torch.optim.AdamW) vs BoostedFlow.training_step "
+                     "(value) vs training_step(uniforms=True), the one-call boosted step",
            "unit": "ms/step", "batch": a.batch, "components": C, "steps_per_window": a.steps, "rounds": a.rounds,
            "data": "synthetic", "dtype": "f16x3", "lr": LR, "weight_decay": WEIGHT_DECAY, "max_grad_norm": MAX_GRAD_NORM}
     for k, r in res.items():
@@ -93,6 +99,7 @@ def main():
         out[f"{k}_ms_per_step_gpu_events"] = statistics.median(gpu)
     out["value"] = out["fused_ms_per_step_wall"]
     out["speedup_wall"] = out["module_ms_per_step_wall"] / out["fused_ms_per_step_wall"]
+    out["onecall_speedup_wall_vs_fused"] = out["fused_ms_per_step_wall"] / out["onecall_ms_per_step_wall"]
     out["note"] = ("wall: host clock around a window that ends in a synchronise, median over alternating rounds; gpu_events: device time "
                    "between two events around the same window (host gaps included while the stream runs dry)")
     print(json.dumps(out))
