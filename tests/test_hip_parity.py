@@ -25,6 +25,15 @@ def _mixture(specs, math="default"):
     return native.mixture_from_specs(specs, math=math)    # (per-step activation kernels when the components need them)
 
 
+def _assert_inverse_matches_oracle(spec, z, x, ild, tag=None):
+    """x, ild = the device inverse of the device's own z: against the float64 oracle inverse of that z, at the bars of
+    test_inverse_matches_oracle_and_round_trips (x 2e-5 of its scale, the log-determinant 1e-5 of its scale)."""
+    from oracle import gbnf_oracle as oracle
+    x64, ild64 = oracle.component_inverse(spec, z.cpu().numpy(), backend="numpy64")
+    assert np.abs(x.cpu().numpy() - x64).max() <= 2e-5 * max(1.0, float(np.abs(x64).max())), tag
+    assert np.abs(ild.cpu().numpy() - ild64).max() <= 1e-5 * max(1.0, float(np.abs(ild64).max())), tag
+
+
 @pytest.mark.parametrize("math", ["f32", "f16x3", "bf16x6", "default"])
 @pytest.mark.parametrize("name", golden_names())
 def test_hip_matches_reference_golden(name, math, golden_case, dev):
@@ -167,9 +176,11 @@ def test_activation_drawn_per_step(kind, d, h, K, math, dev):
     if True:                     # the inverse direction: every math mode since round 3
         x = synth.synth_batch(200, d, seed=3)
         xd = torch.from_numpy(x).to(dev)
-        z, _, _ = flows[1].forward(xd)
-        xr, _ = flows[1].inverse(z)
+        z, ldj, _ = flows[1].forward(xd)
+        xr, ldj_inv = flows[1].inverse(z)
         assert np.abs(xr.cpu().numpy() - x).max() < 5e-4
+        assert np.abs((ldj + ldj_inv).cpu().numpy()).max() < 1e-3
+        _assert_inverse_matches_oracle(specs[1], z, xr, ldj_inv)
     if kind == "realnvp":      # a pair nobody compiled (tanh shift net, relu scale net, every step) runs on the per-step kernels
         odd = synth.synth_realnvp_spec(d, h, 3, seed=5, coupling_network="tanh")
         for st in odd["steps"]:
@@ -206,6 +217,7 @@ def test_residual_coupling_networks(blocks, dev):
     xr, ldj_inv = flows[2].inverse(z)
     assert np.abs(xr.cpu().numpy() - x).max() < 5e-4
     assert np.abs((ldj + ldj_inv).cpu().numpy()).max() < 1e-3
+    _assert_inverse_matches_oracle(specs[2], z, xr, ldj_inv)
     if True:                                    # every math mode against the oracle, 16- and 32-sample waves
         xs = synth.synth_batch(700, d, seed=5)
         z64, ldj64 = oracle.component_forward(specs[1], xs, backend="numpy64")
@@ -251,6 +263,7 @@ def test_wide_residual_networks_run_on_the_split_kernels(h, blocks, dev):
         xr, ldj_inv = f.inverse(zz)
         assert np.abs(xr.cpu().numpy() - xs).max() < 5e-4
         assert np.abs((ll_ + ldj_inv).cpu().numpy()).max() < 1e-3
+        _assert_inverse_matches_oracle(specs[1], zz, xr, ldj_inv, math)
 
 
 def test_out_of_range_samples_are_repaired(dev):
