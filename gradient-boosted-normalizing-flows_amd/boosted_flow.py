@@ -746,9 +746,17 @@ class BoostedFlow(nn.Module):
     #              callers only; `verify_numerics` remains as the explicit, synchronous form.
     NUMERICS_TOL = 2.5e-6
 
-    def numerics_status(self, n_used=None):
+    def numerics_status(self, n_used=None, direction="forward"):
         """State of the library's numerics guard for the mixture of the first n_used components (no synchronisation):
-        dict(math_mode, demoted, checks, worst_rel_err, tolerance)."""
+        dict(math_mode, demoted, checks, worst_rel_err, tolerance).  ``direction="inverse"``: the same keys for the z -> x
+        direction, which runs per component (``component_inverse``): the worst over the first n_used components' own guards
+        (gbnf_flow_numerics_inverse) -- demoted if any is, checks summed, the largest worst_rel_err (max(e_l, e_x / 2), against the
+        log|det| tolerance)."""
+        if native.check_direction(direction) == "inverse":
+            sts = [self.native_flow(c).numerics("inverse") for c in range(self._n_used(n_used))]
+            return {"math_mode": native.MATH_NAME[max(int(st.math_mode) for st in sts)], "demoted": any(bool(st.demoted) for st in sts),
+                    "checks": sum(int(st.checks) for st in sts), "worst_rel_err": max(float(st.worst_rel_err) for st in sts),
+                    "tolerance": float(sts[0].tolerance)}
         st = self.native_mixture(self._n_used(n_used)).numerics()
         return {"math_mode": native.MATH_NAME[int(st.math_mode)], "demoted": bool(st.demoted), "checks": int(st.checks),
                 "worst_rel_err": float(st.worst_rel_err), "tolerance": float(st.tolerance)}

@@ -8,6 +8,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <string.h>
+#include <algorithm>
 #include <atomic>
 #include <mutex>
 #include <string>
@@ -62,15 +63,21 @@ constexpr int GUARD_ROWS = 256;
 struct GuardStatus {             // pinned host memory, written by guard_compare_kernel through its device alias
   unsigned long long checks;
   float worst_rel_err;
-  unsigned demoted;
+  unsigned demoted;                // the verdict belongs to the handle: a failed check of either direction raises it
+  float worst_rel_err_inv;         // the z -> x checks (guard_compare_inverse_kernel): max(e_l, e_x / 2), comparable with the tolerance
+  unsigned long long checks_inv;
 };
 struct Guard {
   unsigned* flag_dev = nullptr;          // [0] != 0: the check failed (read by every repair launch of the handle)
-  float* scratch_dev = nullptr;          // [2][n_comp][GUARD_ROWS] log-likelihoods of the check rows: f16x3 | bf16x6
+  // [2][n_comp][GUARD_ROWS] log-likelihoods of the check rows: f16x3 | bf16x6.  A flow handle's guard (inv_d > 0) also checks the
+  // z -> x direction: [2] x ([GUARD_ROWS][d] x | [GUARD_ROWS] log|det|) in the same memory (one check in flight per guard)
+  float* scratch_dev = nullptr;
   GuardStatus* status_host = nullptr;    // hipHostMalloc, mapped
   GuardStatus* status_dev = nullptr;     // the device's address of the same memory
   int n_comp = 0;
+  int inv_d = 0;                         // features the scratch holds for a z -> x check (0: a mixture's guard, forward only)
   std::atomic<long long> launches{0};
+  std::atomic<long long> launches_inv{0};      // the z -> x direction keeps a schedule of its own
   // the check rows of a launch live in scratch_dev until guard_compare_kernel has read them: a check on ANOTHER stream while one
   // is still in flight would race on them -- such a check is skipped (the next launch checks instead)
   hipEvent_t check_done = nullptr;       // recorded behind the last check's compare launch
@@ -216,17 +223,23 @@ static void free_guard(Guard* g) {
   if (ok && g_guard_pool.size() < 64) g_guard_pool.push_back(g);
   else destroy_guard(g);
 }
-static hipError_t make_guard(int n_comp, Guard** out) {
+static void reset_guard_status(GuardStatus* st) {
+  st->checks = 0; st->worst_rel_err = 0.0f; st->demoted = 0;
+  st->checks_inv = 0; st->worst_rel_err_inv = 0.0f;
+}
+// inv_d: features of a flow handle whose z -> x direction is checked too (0: a mixture's guard)
+static hipError_t make_guard(int n_comp, int inv_d, Guard** out) {
   int dev = 0;
   (void)hipGetDevice(&dev);
   {
     std::lock_guard<std::mutex> lk(g_guard_pool_mutex);
     for (size_t k = 0; k < g_guard_pool.size(); ++k) {
       Guard* g = g_guard_pool[k];
-      if (g->n_comp == n_comp && g->device == dev) {
+      if (g->n_comp == n_comp && g->inv_d == inv_d && g->device == dev) {
         g_guard_pool.erase(g_guard_pool.begin() + (long)k);
-        g->status_host->checks = 0; g->status_host->worst_rel_err = 0.0f; g->status_host->demoted = 0;
+        reset_guard_status(g->status_host);
         g->launches.store(0);
+        g->launches_inv.store(0);
         g->check_pending = false;
         *out = g;
         return hipSuccess;
@@ -235,13 +248,15 @@ static hipError_t make_guard(int n_comp, Guard** out) {
   }
   Guard* g = new Guard();
   g->n_comp = n_comp;
+  g->inv_d = inv_d;
   g->device = dev;
   hipError_t e = hipMalloc((void**)&g->flag_dev, 16);
   if (e == hipSuccess) e = hipMemset(g->flag_dev, 0, 16);
-  if (e == hipSuccess) e = hipMalloc((void**)&g->scratch_dev, sizeof(float) * 2 * n_comp * GUARD_ROWS);
+  const size_t scratch_floats = (size_t)2 * GUARD_ROWS * (size_t)std::max(n_comp, inv_d > 0 ? inv_d + 1 : 0);
+  if (e == hipSuccess) e = hipMalloc((void**)&g->scratch_dev, sizeof(float) * scratch_floats);
   if (e == hipSuccess) e = hipHostMalloc((void**)&g->status_host, sizeof(GuardStatus), hipHostMallocMapped);
   if (e == hipSuccess) {
-    g->status_host->checks = 0; g->status_host->worst_rel_err = 0.0f; g->status_host->demoted = 0;
+    reset_guard_status(g->status_host);
     e = hipHostGetDevicePointer((void**)&g->status_dev, g->status_host, 0);
   }
   if (e == hipSuccess) e = hipEventCreateWithFlags(&g->check_done, hipEventDisableTiming);
@@ -1017,7 +1032,7 @@ int gbnf_flow_create_ex(const gbnf_flow_desc* desc, int32_t math_mode, int32_t f
   }
   // ---- a DEFAULT handle that stays on f16x3 keeps being checked against its bf16x6 packing on the caller's data
   if (math_mode == GBNF_MATH_DEFAULT && f->math_mode == GBNF_MATH_F16X3 && f->blob2_dev != nullptr) {
-    e = make_guard(1, &f->guard);
+    e = make_guard(1, f->d, &f->guard);
     if (e != hipSuccess) {
       free_flow(f);
       return fail(GBNF_ERR_HIP, "allocating the numerics guard failed: %s", hipGetErrorString(e));
@@ -1114,6 +1129,56 @@ __global__ void __launch_bounds__(256) guard_compare_kernel(const float* __restr
     }
     st->worst_rel_err = fmaxf(st->worst_rel_err, worst);
     st->checks = st->checks + 1ull;
+    __threadfence_system();
+  }
+}
+
+// The same for the z -> x direction of one flow: x (rows, d) and log|det| (rows) of the check rows, f16x3 (xa, la) against bf16x6
+// (xb, lb).  Per row e_x = max_j |xa - xb| / max(1, max_j |xb|) and e_l = |la - lb| / max(1, |lb|); the check fails when e_l > tol or
+// e_x > 2 tol (a quarter of the direction's 1e-5 / 2e-5 bars); worst = max(e_l, e_x / 2) compares directly with tol.  One workgroup,
+// thread r owns row r (rows <= GUARD_ROWS = the block), features in order, a fixed reduction order.
+__global__ void __launch_bounds__(GUARD_ROWS) guard_compare_inverse_kernel(const float* __restrict__ xa, const float* __restrict__ la,
+                                                                           const float* __restrict__ xb, const float* __restrict__ lb,
+                                                                           int d, int rows, float tol, unsigned* __restrict__ flag,
+                                                                           GuardStatus* __restrict__ st) {
+  __shared__ float red[2][4];
+  float e_l = 0.0f, e_x = 0.0f;
+  const int r = threadIdx.x;
+  if (r < rows) {
+    const float va = la[r], vb = lb[r];
+    bool marked = va != va;                                   // marked by the f16x3 launch: the repair pass owns the row
+    float diff = 0.0f, mag = 0.0f;
+    bool lone = false;                                        // only one of the two results is finite
+    for (int j = 0; j < d; ++j) {
+      const float a = xa[r * d + j], b = xb[r * d + j];
+      marked = marked || a != a;
+      if (a == b) { mag = fmaxf(mag, fabsf(b)); continue; }   // equal (infinities included)
+      if (b != b || isinf(a) || isinf(b)) { lone = true; continue; }
+      diff = fmaxf(diff, fabsf(a - b));
+      mag = fmaxf(mag, fabsf(b));
+    }
+    if (!marked) {
+      e_x = lone ? INFINITY : diff / fmaxf(mag, 1.0f);
+      if (va == vb) e_l = 0.0f;
+      else if (vb != vb || isinf(va) || isinf(vb)) e_l = INFINITY;
+      else e_l = fabsf(va - vb) / fmaxf(fabsf(vb), 1.0f);
+    }
+  }
+  for (int off = 32; off > 0; off >>= 1) {
+    e_l = fmaxf(e_l, __shfl_xor(e_l, off));
+    e_x = fmaxf(e_x, __shfl_xor(e_x, off));
+  }
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = e_l; red[1][threadIdx.x >> 6] = e_x; }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    e_l = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+    e_x = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+    if (!(e_l <= tol) || !(e_x <= 2.0f * tol)) {
+      flag[0] = 1u;
+      st->demoted = 1u;
+    }
+    st->worst_rel_err_inv = fmaxf(st->worst_rel_err_inv, fmaxf(e_l, 0.5f * e_x));
+    st->checks_inv = st->checks_inv + 1ull;
     __threadfence_system();
   }
 }
@@ -1226,6 +1291,63 @@ static int launch_flow(const gbnf_flow* f, const uint32_t* const* table, const u
       r.guard = guard->flag_dev;
       e = f->launch2_nt[nt](r, (unsigned)grid, stream);
       if (e != hipSuccess) return fail(GBNF_ERR_HIP, "numerics-guard re-evaluation launch failed: %s", hipGetErrorString(e));
+    }
+  }
+  // ---- the same guard for z -> x (one flow, gbnf_flow_inverse): a schedule of its own (the forward cadence is untouched), the same
+  //      one-check-in-flight rule; x and log|det| of the leading rows on both packings, compared on the device.  A call that writes x
+  //      over its own z leaves nothing to re-evaluate behind the launch: it is not checked and does not advance the schedule.
+  if (split_pair && guard != nullptr && inverse && n_comp == 1 && n_batches == 1 && guard->inv_d >= f->d && z != nullptr &&
+      (const float*)z != p.xs[0] && f->launch_nt[1] != nullptr && f->launch2_nt[1] != nullptr) {
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    if (stream != nullptr && hipStreamIsCapturing(stream, &cap) != hipSuccess) cap = hipStreamCaptureStatusNone;
+    const long long k = cap == hipStreamCaptureStatusNone ? guard->launches_inv.fetch_add(1, std::memory_order_relaxed) : -1;
+    const int every = tuning().check_every.load(std::memory_order_relaxed);
+    bool check_now = k >= 0 && every >= 0 && (k == 0 || (every > 0 && k % every == 0));
+    if (check_now) {
+      std::lock_guard<std::mutex> lk(guard->check_mutex);
+      if (guard->check_pending && guard->check_stream != stream && hipEventQuery(guard->check_done) == hipErrorNotReady) {
+        check_now = false;
+        guard->launches_inv.store(0, std::memory_order_relaxed);      // (the next z -> x launch takes the check)
+      } else {
+        guard->check_pending = true;
+        guard->check_stream = stream;
+      }
+    }
+    if (check_now) {
+      const int rows = (int)(n < GUARD_ROWS ? n : GUARD_ROWS);
+      const size_t half = (size_t)GUARD_ROWS * (size_t)(f->d + 1);
+      float* xa = guard->scratch_dev;
+      float* la = xa + (size_t)GUARD_ROWS * f->d;
+      float* xb = guard->scratch_dev + half;
+      float* lb = xb + (size_t)GUARD_ROWS * f->d;
+      FlowLaunch q = p;
+      q.n = rows; q.out_stride = GUARD_ROWS; q.n_tiles = (rows + 15) / 16;
+      q.ll_out = nullptr; q.repair = 0; q.guard = nullptr;
+      q.sat = nullptr;                 // the check rows were counted (and marked) by the launch itself: not twice
+      const unsigned mini_grid = (unsigned)q.n_tiles;
+      q.z_out = xa; q.ldj_out = la;
+      q.seq = next_serial();
+      e = f->launch_nt[1](q, mini_grid, stream);
+      if (e == hipSuccess) {
+        q.blobs = table2;
+        q.z_out = xb; q.ldj_out = lb;
+        q.seq = next_serial();
+        e = f->launch2_nt[1](q, mini_grid, stream);
+      }
+      if (e != hipSuccess) return fail(GBNF_ERR_HIP, "numerics-guard launch (z -> x) failed: %s", hipGetErrorString(e));
+      hipLaunchKernelGGL(guard_compare_inverse_kernel, dim3(1), dim3(GUARD_ROWS), 0, stream, (const float*)xa, (const float*)la,
+                         (const float*)xb, (const float*)lb, f->d, rows,
+                         1e-9f * (float)tuning().check_tolerance_e9.load(std::memory_order_relaxed), guard->flag_dev, guard->status_dev);
+      e = hipGetLastError();
+      if (e != hipSuccess) return fail(GBNF_ERR_HIP, "numerics-guard compare launch (z -> x) failed: %s", hipGetErrorString(e));
+      (void)hipEventRecord(guard->check_done, stream);
+      // the launch that was just checked: x and log|det| of ALL its rows again on bf16x6 if (and only if) the check failed
+      FlowLaunch r = p;
+      r.blobs = table2;
+      r.repair = 2;
+      r.guard = guard->flag_dev;
+      e = f->launch2_nt[nt](r, (unsigned)grid, stream);
+      if (e != hipSuccess) return fail(GBNF_ERR_HIP, "numerics-guard re-evaluation launch (z -> x) failed: %s", hipGetErrorString(e));
     }
   }
   return GBNF_OK;
@@ -1426,7 +1548,7 @@ int gbnf_flow_inverse(const gbnf_flow* flow, const float* z, int64_t n, float* x
   if (n < 0) return fail(GBNF_ERR_INVALID, "gbnf_flow_inverse: n < 0");
   if (n > 0 && (!z || !x)) return fail(GBNF_ERR_INVALID, "gbnf_flow_inverse: z / x is null");
   // every math mode (round 3: the split kernels run backwards too; an f16x3 launch is followed by its bf16x6 repair pass
-  // like a forward one; the numerics guard of a DEFAULT handle keeps its verdict from the forward direction)
+  // like a forward one; the numerics guard of a DEFAULT handle checks this direction on a schedule of its own, launch_flow)
   return launch_flow(flow, flow->self_table_dev, flow->self_table2_dev, false, 0, 1, z, n, x, ldj, nullptr, nullptr, (hipStream_t)stream, -1,
                      nullptr, 1, 1, flow->guard);
 }
@@ -1489,7 +1611,7 @@ int gbnf_mixture_create(gbnf_flow* const* flows, int32_t n_flows, gbnf_mixture**
   if (e == hipSuccess && have2 && m->math_mode == GBNF_MATH_F16X3) {
     bool all_default = true;
     for (int c = 0; c < n_flows; ++c) all_default = all_default && flows[c]->requested_mode == GBNF_MATH_DEFAULT;
-    if (all_default) e = make_guard(n_flows, &m->guard);
+    if (all_default) e = make_guard(n_flows, 0, &m->guard);
   }
   if (e != hipSuccess) {
     if (m->table_dev) (void)hipFree(m->table_dev);
@@ -1597,20 +1719,26 @@ int gbnf_mixture_log_prob(const gbnf_mixture* mix, const float* x, int64_t n, in
   return gbnf_mixture_lse(ll_workspace, n, rho_dev, n_used, n, out, stream);
 }
 
-static void fill_numerics(const Guard* g, int mode, gbnf_numerics_status* out) {
+static void fill_numerics(const Guard* g, int mode, gbnf_numerics_status* out, bool inverse = false) {
   out->math_mode = mode; out->demoted = 0; out->checks = 0; out->worst_rel_err = 0.0f;
   out->tolerance = 1e-9f * (float)tuning().check_tolerance_e9.load(std::memory_order_relaxed);
   if (g == nullptr) return;
   const volatile GuardStatus* st = g->status_host;
   out->demoted = st->demoted != 0u ? 1 : 0;
-  out->checks = (int64_t)st->checks;
-  out->worst_rel_err = st->worst_rel_err;
+  out->checks = (int64_t)(inverse ? st->checks_inv : st->checks);
+  out->worst_rel_err = inverse ? st->worst_rel_err_inv : st->worst_rel_err;
   if (out->demoted && mode == GBNF_MATH_F16X3) out->math_mode = GBNF_MATH_BF16X6;
 }
 
 int gbnf_flow_numerics(const gbnf_flow* flow, gbnf_numerics_status* out) {
   if (!flow || !out) return fail(GBNF_ERR_INVALID, "gbnf_flow_numerics: null argument");
   fill_numerics(flow->guard, flow->math_mode, out);
+  return GBNF_OK;
+}
+
+int gbnf_flow_numerics_inverse(const gbnf_flow* flow, gbnf_numerics_status* out) {
+  if (!flow || !out) return fail(GBNF_ERR_INVALID, "gbnf_flow_numerics_inverse: null argument");
+  fill_numerics(flow->guard, flow->math_mode, out, true);
   return GBNF_OK;
 }
 

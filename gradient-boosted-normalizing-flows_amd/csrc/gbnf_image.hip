@@ -525,15 +525,42 @@ __global__ void __launch_bounds__(256) img_embed_kernel(const float* __restrict_
 }
 
 // the last unsqueeze + to_logits(reverse=True) (models/glow.py:151-158): (n, 4C, H/2, W/2) logits -> x (n, C, H, W)
+__device__ __forceinline__ float img_post_value(const float* __restrict__ xi, int e, int H, int W, int Hi, int Wi, float bounds) {
+  const int c = e / (Hi * Wi), rem = e % (Hi * Wi), y = rem / Wi, xx = rem % Wi;
+  const int ic = c * 4 + (y & 1) * 2 + (xx & 1);
+  const float v = xi[((int64_t)ic * (H / 2) + (y >> 1)) * (W / 2) + (xx >> 1)];
+  const float sg = 1.0f / (__expf(-v) + 1.0f);
+  return ((sg * 2.0f - 1.0f) / bounds + 1.0f) * 0.5f;
+}
 __device__ __forceinline__ void img_post_body(const float* __restrict__ xi, float* __restrict__ oi, int C, int H, int W, int Hi, int Wi, float bounds) {
   const int xchw = C * Hi * Wi;                              // storage H x W, x (C, Hi, Wi)
+  for (int e = threadIdx.x; e < xchw; e += 256) oi[e] = img_post_value(xi, e, H, W, Hi, Wi, bounds);
+}
+// The on-data check of the z -> x direction: the same values, COMPARED with what the split-f16 pass left in `got` instead of stored.
+// Returns max |got - x| / max(1, max |x|) over the image in every thread (infinite when only one of the two is finite); a workgroup
+// reduction in a fixed order, no atomics.
+__device__ __forceinline__ float img_post_check_body(const float* __restrict__ xi, const float* __restrict__ got, int C, int H, int W, int Hi,
+                                                     int Wi, float bounds) {
+  const int xchw = C * Hi * Wi;
+  float diff = 0.0f, mag = 0.0f;
   for (int e = threadIdx.x; e < xchw; e += 256) {
-    const int c = e / (Hi * Wi), rem = e % (Hi * Wi), y = rem / Wi, xx = rem % Wi;
-    const int ic = c * 4 + (y & 1) * 2 + (xx & 1);
-    const float v = xi[((int64_t)ic * (H / 2) + (y >> 1)) * (W / 2) + (xx >> 1)];
-    const float sg = 1.0f / (__expf(-v) + 1.0f);
-    oi[e] = ((sg * 2.0f - 1.0f) / bounds + 1.0f) * 0.5f;
+    const float want = img_post_value(xi, e, H, W, Hi, Wi, bounds), g = got[e];
+    if (g == want) { mag = fmaxf(mag, fabsf(want)); continue; }
+    if (g != g || want != want || isinf(g) || isinf(want)) { diff = INFINITY; continue; }
+    diff = fmaxf(diff, fabsf(g - want));
+    mag = fmaxf(mag, fabsf(want));
   }
+  for (int off = 32; off > 0; off >>= 1) {
+    diff = fmaxf(diff, __shfl_xor(diff, off));
+    mag = fmaxf(mag, __shfl_xor(mag, off));
+  }
+  __shared__ float red[2][4];
+  if ((threadIdx.x & 63) == 0) { red[0][threadIdx.x >> 6] = diff; red[1][threadIdx.x >> 6] = mag; }
+  __syncthreads();
+  diff = fmaxf(fmaxf(red[0][0], red[0][1]), fmaxf(red[0][2], red[0][3]));
+  mag = fmaxf(fmaxf(red[1][0], red[1][1]), fmaxf(red[1][2], red[1][3]));
+  __syncthreads();
+  return diff / fmaxf(mag, 1.0f);
 }
 __global__ void __launch_bounds__(256) img_post_kernel(const float* __restrict__ in, float* __restrict__ x, int C, int H, int W, int Hi, int Wi,
                                                        float bounds) {
@@ -658,12 +685,14 @@ struct RepairArgs {
   const float* zin; const float* eps; float* xout; float temperature;      // z -> x
   int64_t xchw, zsz;
   float tol;
-  unsigned* host_words;       // pinned: [2] checks completed, [3] checks failed, [4] worst relative difference (float bits)
+  unsigned* host_words;       // pinned: [2] checks completed, [3] checks failed, [4] worst relative difference (float bits);
+                              // [5] [6] [7]: the same of the z -> x direction
 };
 
 __global__ void __launch_bounds__(256) img_compact_kernel(const unsigned* __restrict__ mark, int n, unsigned* __restrict__ list,
                                                           unsigned* __restrict__ count /* [0] marked, [1] check entries */,
-                                                          unsigned* __restrict__ check_list, unsigned* __restrict__ dev_state /* [0] launches */,
+                                                          unsigned* __restrict__ check_list,
+                                                          unsigned* __restrict__ launches /* this direction's word of dev_state */,
                                                           unsigned* host_words, int check_every) {
   // in order: one wave scans (n is a batch size: a few thousand at most)
   if (threadIdx.x >= 64) return;
@@ -671,7 +700,7 @@ __global__ void __launch_bounds__(256) img_compact_kernel(const unsigned* __rest
   bool check = false;
   if (check_list != nullptr) {
     unsigned serial = 0;
-    if (threadIdx.x == 0) { serial = dev_state[0]; dev_state[0] = serial + 1u; }
+    if (threadIdx.x == 0) { serial = launches[0]; launches[0] = serial + 1u; }
     serial = __shfl(serial, 0);
     check = check_every >= 0 && (serial == 0u || (check_every > 0 && serial % (unsigned)check_every == 0u));
   }
@@ -782,7 +811,21 @@ __global__ void __launch_bounds__(64 * IMG_WAVES) img_repair_kernel(const Repair
                                op.eps_img ? a.eps + op.eps_lvl * a.n + img * op.eps_img : nullptr, op.i[3], op.i[4], op.i[5], op.i[6], op.i[7]);
           break;
         case ROP_POST:
-          if constexpr (INV) img_post_body(wsb + op.a, a.xout + img * a.xchw, op.i[0], op.i[1], op.i[2], op.i[3], op.i[4], op.f[0]);
+          if constexpr (INV) {
+            if (!a.check) {
+              img_post_body(wsb + op.a, a.xout + img * a.xchw, op.i[0], op.i[1], op.i[2], op.i[3], op.i[4], op.f[0]);
+            } else if (a.mark[img] == 0u) {                   // (a marked image is repaired anyway; a check never writes x)
+              const float err = img_post_check_body(wsb + op.a, a.xout + img * a.xchw, op.i[0], op.i[1], op.i[2], op.i[3], op.i[4], op.f[0]);
+              if (threadIdx.x == 0) {
+                atomicAdd_system(a.host_words + 5, 1u);
+                atomicMax_system(a.host_words + 7, __float_as_uint(err == err ? err : INFINITY));
+                if (!(err <= 2.0f * a.tol)) {                 // x is held to twice the log-likelihood's bar: a quarter of each
+                  atomicExch(a.force_all, 1u);
+                  atomicAdd_system(a.host_words + 6, 1u);
+                }
+              }
+            }
+          }
           break;
         default: break;
       }
@@ -835,13 +878,17 @@ struct gbnf_image_flow {
   bool probed = false;
   // pinned, device-visible: [0] calls that marked an image, [1] images re-evaluated on exact f32, [2] on-data checks completed,
   // [3] on-data checks failed (non-zero: the handle runs on the exact-f32 kernels from the next call on), [4] worst relative
-  // difference a check has seen (float bits)
+  // difference a check has seen (float bits); [5] [6] [7] the same three of the z -> x direction's checks ([6] demotes like [3])
   unsigned* host_words = nullptr;
-  unsigned* dev_state = nullptr;             // device: [0] launches so far (the check schedule), [1] force_all (a check failed)
+  // device: [0] forward launches so far (the check schedule), [1] force_all (a check failed), [2] z -> x launches so far
+  unsigned* dev_state = nullptr;
   RepairOp* ops_dev = nullptr;               // the exact-f32 sequence of ONE image as recorded ops: forward [0, n_ops_fwd), then z -> x
   int n_ops_fwd = 0, n_ops_inv = 0;
   size_t repair_lds_fwd = 0, repair_lds_inv = 0;
-  bool on_data_demoted() const { return host_words != nullptr && ((volatile unsigned*)host_words)[3] != 0u; }
+  bool on_data_demoted() const {
+    volatile unsigned* w = (volatile unsigned*)host_words;
+    return w != nullptr && (w[3] != 0u || w[6] != 0u);
+  }
 };
 
 namespace {
@@ -1321,8 +1368,8 @@ int gbnf_image_flow_create_mode(const gbnf_image_flow_desc* d, int32_t math_mode
     if (e == hipSuccess && f->math_mode == GBNF_MATH_F16X3) {
       e = hipHostMalloc((void**)&f->host_words, 8 * sizeof(unsigned), hipHostMallocMapped);
       if (e == hipSuccess) std::memset(f->host_words, 0, 8 * sizeof(unsigned));
-      if (e == hipSuccess) e = hipMalloc((void**)&f->dev_state, 2 * sizeof(unsigned));
-      if (e == hipSuccess) e = hipMemset(f->dev_state, 0, 2 * sizeof(unsigned));
+      if (e == hipSuccess) e = hipMalloc((void**)&f->dev_state, 4 * sizeof(unsigned));
+      if (e == hipSuccess) e = hipMemset(f->dev_state, 0, 4 * sizeof(unsigned));
     }
     if (e != hipSuccess) rc = fail(GBNF_ERR_HIP, "gbnf_image_flow_create: %s", hipGetErrorString(e));
     if (rc == GBNF_OK && f->math_mode == GBNF_MATH_F16X3) rc = image_record_repair_ops(f);
@@ -1710,6 +1757,18 @@ int gbnf_image_flow_repair_counts(const gbnf_image_flow* f, int64_t* marked_call
   return GBNF_OK;
 }
 
+int gbnf_image_flow_inverse_check_counts(const gbnf_image_flow* f, int64_t* data_checks, int64_t* failed_checks, float* worst_rel_err) {
+  if (!f) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_inverse_check_counts: flow is null");
+  volatile unsigned* w = (volatile unsigned*)f->host_words;
+  if (data_checks) *data_checks = w ? w[5] : 0;
+  if (failed_checks) *failed_checks = w ? w[6] : 0;
+  if (worst_rel_err) {
+    const unsigned bits = w ? w[7] : 0u;
+    std::memcpy(worst_rel_err, &bits, 4);
+  }
+  return GBNF_OK;
+}
+
 int gbnf_image_flow_eps_floats(const gbnf_image_flow* f, int64_t* per_image) {
   if (!f || !per_image) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_eps_floats: null argument");
   *per_image = (int64_t)f->C * f->Hi * f->Wi - (int64_t)f->zC * f->zH * f->zW;
@@ -1891,20 +1950,27 @@ int gbnf_image_flow_inverse(const gbnf_image_flow* f, const float* z, const floa
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   // split-f16 coupling nets (the fused kernel, as the forward) unless the handle runs on exact f32 (its mode, or a failed on-data
-  // check of the forward direction).  An image whose hidden activation leaves the fp16 range is re-evaluated on exact f32 by the
-  // repair launch behind the pass, in this call.
+  // check of either direction).  An image whose hidden activation leaves the fp16 range is re-evaluated on exact f32 by the
+  // repair launch behind the pass, in this call; on this direction's first launch and every check_every-th after it (counted on the
+  // device) up to IMG_CHECK_MAX unmarked images are walked through the exact-f32 sequence too and their x compared in place.
   const bool fast = f->math_mode == GBNF_MATH_F16X3 && !f->on_data_demoted();
   if (!fast || image_repair_mode() == 0) return image_inverse_impl(f, z, eps, temperature, n, x, ws, s, fast, nullptr, nullptr);
   const RepairSpace r = repair_space(f, ws, n);
   if (hipMemsetAsync(r.mark, 0, (size_t)n * 4, s) != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_image_flow_inverse: memset failed");
   const int rc = image_inverse_impl(f, z, eps, temperature, n, x, ws, s, true, r.mark, nullptr);
   if (rc) return rc;
-  hipLaunchKernelGGL(img_compact_kernel, dim3(1), dim3(256), 0, s, (const unsigned*)r.mark, (int)n, r.list, r.count, (unsigned*)nullptr,
-                     f->dev_state, f->host_words, -1);
+  int32_t every = 256, tol_e9 = 2500;
+  (void)gbnf_tuning_get("check_every", &every);
+  (void)gbnf_tuning_get("check_tolerance_e9", &tol_e9);
+  hipLaunchKernelGGL(img_compact_kernel, dim3(1), dim3(256), 0, s, (const unsigned*)r.mark, (int)n, r.list, r.count, r.check_list,
+                     f->dev_state + 2, f->host_words, (int)every);
   RepairArgs a{};
   a.mark = r.mark; a.ws = r.wsr;
   a.zin = z; a.eps = eps; a.xout = x; a.temperature = temperature;
   a.xchw = (int64_t)f->C * f->Hi * f->Wi; a.zsz = (int64_t)f->zC * f->zH * f->zW;
+  a.tol = 1e-9f * (float)tol_e9;
+  a.check = 1; a.list = r.check_list; a.count = r.count + 1;
+  launch_repair(f, true, a, n, s);
   a.check = 0; a.list = r.list; a.count = r.count;
   launch_repair(f, true, a, n, s);
   const hipError_t e = hipGetLastError();

@@ -384,6 +384,30 @@ class BoostedImageFlow(nn.Module):
         with torch.cuda.device(x.device):
             return self.native_flow(int(c)).forward(x, noise.contiguous().float(), want_z=want_z)
 
+    def numerics_status(self, n_used=None, direction="forward"):
+        """State of the image path's numerics protocol over the first n_used components (no synchronisation), with the keys of
+        BoostedFlow.numerics_status: dict(math_mode, demoted, checks, worst_rel_err, tolerance).  ``checks`` / ``worst_rel_err`` are
+        the on-data checks of the direction asked for (gbnf_image_flow_repair_counts, gbnf_image_flow_inverse_check_counts), summed /
+        the largest over the components; math_mode and demoted belong to the handles (a failed check of either direction sends a
+        handle to exact f32): "f32" as soon as one component runs there."""
+        inverse = native.check_direction(direction) == "inverse"
+        n_used = self.num_components if n_used is None else int(n_used)
+        checks, worst, demoted, mode, tol = 0, 0.0, False, None, 0.0
+        for c in range(n_used):
+            h = self.native_flow(c)
+            st = h.numerics()
+            if inverse:
+                k = h.inverse_check_counts()
+                checks, worst = checks + k["data_checks"], max(worst, k["worst_rel_err"])
+            else:
+                k = h.repair_counts()
+                checks, worst = checks + k["data_checks"], max(worst, k["worst_check_rel_err"])
+            demoted = demoted or bool(st.demoted)
+            mode = int(st.math_mode) if mode is None else min(mode, int(st.math_mode))
+            tol = float(st.tolerance)
+        return {"math_mode": native.MATH_NAME[mode], "demoted": demoted, "checks": int(checks), "worst_rel_err": float(worst),
+                "tolerance": tol}
+
     def _prior_on(self, handle, device):
         prior = handle.__dict__.get("_prior_dev")            # (mean, logvar) of the top prior on the device, per handle
         if prior is None or prior[0].device != device:

@@ -43,6 +43,7 @@ ABI_SYMBOLS = (
     "gbnf_flow_numerics", "gbnf_mixture_numerics", "gbnf_tuning_set", "gbnf_tuning_get",
     "gbnf_resample_workspace_bytes", "gbnf_resample_rows", "gbnf_boosted_step_workspace_bytes", "gbnf_boosted_nll_step",
     "gbnf_mixture_rho_step",
+    "gbnf_flow_numerics_inverse", "gbnf_image_flow_inverse_check_counts",
 )
 
 
@@ -178,6 +179,7 @@ def lib():
     L.gbnf_flow_validate.argtypes = [C.POINTER(_FlowDesc)]
     L.gbnf_flow_numerics.argtypes = [vp, C.POINTER(NumericsStatus)]
     L.gbnf_mixture_numerics.argtypes = [vp, C.POINTER(NumericsStatus)]
+    L.gbnf_flow_numerics_inverse.argtypes = [vp, C.POINTER(NumericsStatus)]
     L.gbnf_tuning_set.argtypes = [C.c_char_p, i32]
     L.gbnf_tuning_get.argtypes = [C.c_char_p, C.POINTER(i32)]
     L.gbnf_trainer_create.argtypes = [C.POINTER(_FlowDesc), C.POINTER(vp)]
@@ -204,6 +206,7 @@ def lib():
     L.gbnf_image_flow_prior.argtypes = [vp, C.POINTER(C.c_float)]
     L.gbnf_image_flow_numerics.argtypes = [vp, C.POINTER(NumericsStatus)]
     L.gbnf_image_flow_repair_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_float)]
+    L.gbnf_image_flow_inverse_check_counts.argtypes = [vp, C.POINTER(i64), C.POINTER(i64), C.POINTER(C.c_float)]
     L.gbnf_comm_unique_id.argtypes = [C.POINTER(C.c_uint8)]
     L.gbnf_comm_create.argtypes = [C.POINTER(C.c_uint8), i32, i32, C.POINTER(vp)]
     L.gbnf_comm_destroy.argtypes = [vp]
@@ -310,6 +313,13 @@ def _stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+def check_direction(direction):
+    """``"forward"`` or ``"inverse"`` (which direction's on-data checks a numerics status reports); anything else: ValueError."""
+    if direction not in ("forward", "inverse"):
+        raise ValueError(f"direction must be 'forward' or 'inverse', got {direction!r}")
+    return direction
+
+
 class NativeFlow:
     """One packed component on the device (gbnf_flow)."""
 
@@ -329,10 +339,13 @@ class NativeFlow:
         _check(lib().gbnf_flow_info(self.handle, C.byref(ki)))
         return ki
 
-    def numerics(self):
-        """gbnf_flow_numerics: (math mode of the next launch, demoted?, completed checks, worst relative error); no sync."""
+    def numerics(self, direction="forward"):
+        """gbnf_flow_numerics: (math mode of the next launch, demoted?, completed checks, worst relative error); no sync.
+        ``direction="inverse"``: gbnf_flow_numerics_inverse, the checks of the z -> x direction (math mode and demoted are the
+        handle's, shared by both directions)."""
+        fn = lib().gbnf_flow_numerics_inverse if check_direction(direction) == "inverse" else lib().gbnf_flow_numerics
         st = NumericsStatus()
-        _check(lib().gbnf_flow_numerics(self.handle, C.byref(st)))
+        _check(fn(self.handle, C.byref(st)))
         return st
 
     def forward(self, x, want_z=True, want_ldj=True, want_ll=False):
@@ -459,6 +472,13 @@ class NativeImageFlow:
         _check(lib().gbnf_image_flow_repair_counts(self.handle, C.byref(a), C.byref(b), C.byref(c), C.byref(d), C.byref(w)))
         return {"marked_calls": a.value, "repaired_images": b.value, "data_checks": c.value, "failed_checks": d.value,
                 "worst_check_rel_err": w.value}
+
+    def inverse_check_counts(self):
+        """gbnf_image_flow_inverse_check_counts: the on-data checks of the z -> x direction (pinned words, no synchronisation):
+        images checked / failed, the worst relative difference of x a check has seen."""
+        c, d, w = C.c_int64(), C.c_int64(), C.c_float()
+        _check(lib().gbnf_image_flow_inverse_check_counts(self.handle, C.byref(c), C.byref(d), C.byref(w)))
+        return {"data_checks": c.value, "failed_checks": d.value, "worst_rel_err": w.value}
 
     def actnorm_stats(self, x, noise, index):
         """gbnf_image_flow_actnorm_stats: (mean (C,), var (C,)) device tensors of the tensor that reaches ActNorm2d number

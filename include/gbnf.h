@@ -169,7 +169,16 @@ int gbnf_training_saturation_count(int64_t* count, int32_t reset);
  * Every entry point that evaluates a flow (gbnf_flow_forward, gbnf_mixture_component_log_prob*, gbnf_mixture_log_prob)
  * is covered, so C-ABI callers, sharded.GroupPipeline and bench.py get it like BoostedFlow does.  Handles created with
  * an explicit GBNF_MATH_F16X3 keep the caller's choice (range repair only).  These calls never synchronise: `checks`
- * and `worst_rel_err` are those of the checks that have COMPLETED on the device. */
+ * and `worst_rel_err` are those of the checks that have COMPLETED on the device.
+ * The z -> x direction (gbnf_flow_inverse) is checked the same way on a schedule of its OWN: the first inverse launch of a handle
+ * and every `check_every`-th after it evaluate up to 256 leading rows of the launch's z on both packings and compare x and
+ * log|det| on the device, per row  e_x = max_j |x16 - x6| / max(1, max_j |x6|)  and  e_l = |l16 - l6| / max(1, |l6|).  The check
+ * fails when e_l > tolerance or e_x > 2 tolerance: a quarter of the direction's parity bars (1e-5 for log|det|, 2e-5 for x), as
+ * the forward tolerance is a quarter of the log-likelihood's.  The verdict belongs to the handle: a failed check of either
+ * direction re-evaluates ALL rows of the failing call on bf16x6 (x and log|det|) and sends both directions to bf16x6.
+ * gbnf_flow_numerics reports the forward checks, gbnf_flow_numerics_inverse the z -> x ones: `math_mode` and `demoted` are shared,
+ * `checks` and `worst_rel_err` (= max(e_l, e_x / 2), so that it compares with `tolerance`, the log|det| one) are that direction's.
+ * A call that writes x over its own z buffer is not checked (and does not advance the schedule). */
 typedef struct gbnf_numerics_status {
   int32_t math_mode;       /* GBNF_MATH_* the NEXT launch of this handle will run in                       */
   int32_t demoted;         /* 1 = a check failed: the handle left f16x3 for bf16x6                          */
@@ -178,6 +187,7 @@ typedef struct gbnf_numerics_status {
   float tolerance;
 } gbnf_numerics_status;
 int gbnf_flow_numerics(const gbnf_flow* flow, gbnf_numerics_status* out);
+int gbnf_flow_numerics_inverse(const gbnf_flow* flow, gbnf_numerics_status* out);
 int gbnf_mixture_numerics(const gbnf_mixture* mix, gbnf_numerics_status* out);
 
 /* Launch-policy knobs (process-wide; tests, soak runs and tuning -- the defaults are what is measured and shipped):
@@ -239,7 +249,10 @@ int gbnf_flow_forward(const gbnf_flow* flow, const float* x, int64_t n,
  * BoostedFlow.decode / Glow.decode / FlowStep.decode (models/boosted_flow.py:209-218, models/glow.py:112-123, 344-366)
  * and RealNVPFlow.decode (models/realnvp.py:97-113) are meant to do.  In the reference this direction is dead or wrong
  * on tabular data, so parity is defined by inverse(forward(x)) == x (and the one case the reference can
- * decode, additive Glow, fixture g9).  Any math mode (the split kernels run backwards since round 3; ResidualNets: f32). */
+ * decode, additive Glow, fixture g9).  Any math mode (the split kernels run backwards since round 3; ResidualNets: f32).
+ * An f16x3 launch is followed by its bf16x6 range-repair pass like a forward one, and a GBNF_MATH_DEFAULT handle re-checks the
+ * f16x3 choice on the caller's z on this direction's own schedule (gbnf_numerics_status, gbnf_flow_numerics_inverse): a call whose
+ * check fails returns the bf16x6 x and log|det| for every row. */
 int gbnf_flow_inverse(const gbnf_flow* flow, const float* z, int64_t n, float* x, float* ldj, void* stream);
 
 /* Replaces: the nn.ModuleList of components (models/boosted_flow.py:42).  All flows must
@@ -623,7 +636,11 @@ int gbnf_image_flow_prior(const gbnf_image_flow* flow, float* mean_logvar_host);
  *     counted on the device, so HIP-graph replays are covered) up to 2 unmarked images are evaluated on exact f32 as well and
  *     compared with the split-f16 result on the device (`check_tolerance_e9`).  A failed check makes the repair launch of that
  *     very call -- and of every later one -- re-evaluate ALL images, and raises a pinned word: later (non-captured) calls run
- *     the exact-f32 kernels directly (math_mode reads GBNF_MATH_F32, demoted = 1).
+ *     the exact-f32 kernels directly (math_mode reads GBNF_MATH_F32, demoted = 1).  gbnf_image_flow_inverse does the same on a
+ *     device-side launch count of its own: up to 2 unmarked images are walked through the exact-f32 z -> x sequence and their x
+ *     compared in place,  err = max |x16 - x32| / max(1, max |x32|)  over the image, failing when err > 2 `check_tolerance_e9`
+ *     (x is held to twice the log-likelihood's bar, as on the tabular path).  A failure of either direction demotes both;
+ *     its counters: gbnf_image_flow_inverse_check_counts.
  * Environment GBNF_IMAGE_REPAIR=0: nothing behind the split-f16 pass (timing only: out-of-range images keep clamped values).
  * `checks` = calls that marked an image so far; gbnf_image_flow_repair_counts has the rest.  Never synchronises. */
 int gbnf_image_flow_numerics(const gbnf_image_flow* flow, gbnf_numerics_status* out);
@@ -632,6 +649,11 @@ int gbnf_image_flow_numerics(const gbnf_image_flow* flow, gbnf_numerics_status* 
  * difference a check has seen. */
 int gbnf_image_flow_repair_counts(const gbnf_image_flow* flow, int64_t* marked_calls, int64_t* repaired_images,
                                   int64_t* data_checks, int64_t* failed_checks, float* worst_check_rel_err);
+/* The on-data checks of the z -> x direction (gbnf_image_flow_inverse): images checked / failed and the worst relative difference of
+ * x a check has seen.  data_checks / failed_checks of gbnf_image_flow_repair_counts count the forward direction only.  Pinned
+ * host words, no synchronisation; any pointer may be NULL. */
+int gbnf_image_flow_inverse_check_counts(const gbnf_image_flow* flow, int64_t* data_checks, int64_t* failed_checks,
+                                         float* worst_rel_err);
 /* Replaces (one layer at a time): _ActNorm.initialize_parameters for ActNorm2d (models/layers.py:473-486, 548-557), the
  * data-dependent initialisation the first training-mode forward of an image Glow performs layer by layer.  ActNorm2d number
  * `index` of the component in module order -- per FlowStep its own ActNorm2d, then the one behind each Conv2d of its coupling
@@ -654,8 +676,10 @@ int gbnf_image_flow_actnorm_stats(const gbnf_image_flow* flow, const float* x, c
  * gbnf_image_flow_eps_floats() floats per image in all (= C*H*W - Cz*Hz*Wz); may be NULL for a one-level flow.
  * The coupling networks run on the fused split-f16 kernel like the forward where the handle does; an image whose hidden
  * activation leaves the fp16 range is re-evaluated on the exact-f32 sequence by the repair launch behind the pass, in this
- * call (see gbnf_image_flow_numerics).  A handle created with GBNF_MATH_F32, demoted by the probe or by an on-data check of
- * the forward direction runs the exact-f32 convolution kernels.  workspace as for gbnf_image_flow_forward. */
+ * call, and the on-data precision check runs on this direction's first launch and every `check_every`-th after it: a call whose
+ * check fails returns the exact-f32 x for every image (see gbnf_image_flow_numerics).  A handle created with GBNF_MATH_F32, demoted
+ * by the probe or by an on-data check of either direction runs the exact-f32 convolution kernels.  workspace as for
+ * gbnf_image_flow_forward. */
 int gbnf_image_flow_eps_floats(const gbnf_image_flow* flow, int64_t* per_image);
 int gbnf_image_flow_inverse(const gbnf_image_flow* flow, const float* z, const float* eps, float temperature, int64_t n,
                             float* x, void* workspace, int64_t workspace_bytes, void* stream);
