@@ -211,6 +211,11 @@ def main(argv=None):
     objs.append(net_o)
     if args.force or not newer(net_o, [net_src, os.path.join(HERE, "gbnf_image_net.h")]):
         jobs.append([HIPCC] + FLAGS + VGPR_FORM + ["-c", net_src, "-o", net_o])
+    # the image training path (pack / weight-gradient / unfold kernels; the convolutions themselves are gbnf_image.hip's)
+    imgt_o, imgt_src = os.path.join(OBJ, "gbnf_image_train.o"), os.path.join(HERE, "gbnf_image_train.hip")
+    objs.append(imgt_o)
+    if args.force or not newer(imgt_o, [imgt_src, os.path.join(HERE, "gbnf_image_net.h"), hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", imgt_src, "-o", imgt_o])
     comm_o, comm_src = os.path.join(OBJ, "gbnf_comm.o"), os.path.join(HERE, "gbnf_comm.hip")
     objs.append(comm_o)
     if args.force or not newer(comm_o, [comm_src, hdr[2], hdr[3]]):

@@ -45,31 +45,7 @@ constexpr int IMG_MAX_PT = 4;     // pixel tiles of 16 per strip (IMG_R * W / 16
 
 // (the epilogue kinds EPI_* live in gbnf_image_net.h: shared with the fused coupling-net kernel's translation unit)
 
-struct ConvLaunch {
-  const float* in;        // (n, *, H, W): first input channel of image 0
-  int64_t in_img;         // floats between images
-  const float* wp;        // packed weights [OT][taps][KC][64][4]
-  const float* bias;      // [OT*16]
-  float* out;             // EPI_RELU / EPI_STORE: (n, *, H, W) first output channel of image 0
-  int64_t out_img;
-  float* st;              // EPI_COUPLE_* / EPI_SPLIT: the coupled half z2 (n, *, H, W), first channel of image 0
-  int64_t st_img;
-  float* ldj;             // (n,) accumulated with atomics (EPI_COUPLE_AFFINE / EPI_SPLIT)
-  int cin, cout, H, W, ks, n_strips;
-  int Hv, Wv;             // the map proper: rows < Hv, columns < Wv of the H x W storage (a 14 x 14 map lives in 16 x 16 storage;
-                          // everything outside is ZERO in every tensor in HBM -- the 'same' padding of the map -- and stays so)
-  float temperature;      // EPI_SPLIT_INV: z2 = mean + exp(log-var) * temperature * eps (models/layers.py:697)
-  int c_chunk;            // input channels staged per pass (a multiple of 16; 0 = all: 3 x 3 convolutions from > 256 channels do not
-                          // fit the LDS at once and stage their input in two halves; split-contraction form only)
-  int o_split;            // workgroups sharing one strip, each with 1/o_split of the output tiles (fills the chip at small batch)
-  // fused producer (1x1 convolutions only): the input of this convolution is relu(conv3x3(pre_in) + pre_bias), computed
-  // for the strip straight into LDS instead of being read from `in` (the ConvNet's first layer never touches HBM)
-  const float* pre_in;    // (n, *, H, W) first input channel of image 0, or null
-  int64_t pre_in_img;
-  const float* pre_wp;    // packed 3x3 weights [cin/16 tiles][9][pre_kc][64][4]
-  const float* pre_bias;
-  int pre_cin;
-};
+// (struct ConvLaunch lives in gbnf_image_net.h: the training path, gbnf_image_train.hip, fills the same launches)
 
 __device__ __forceinline__ f32x4 img_mfma(float a, float b, f32x4 c) {
   return __builtin_amdgcn_mfma_f32_16x16x4f32(a, b, c, 0, 0, 0);
@@ -1979,3 +1955,46 @@ int gbnf_image_flow_inverse(const gbnf_image_flow* f, const float* z, const floa
 }
 
 }  // extern "C"
+
+// ---- the launch interface of the training path (gbnf_image_train.hip; declared in gbnf_image_net.h): the kernels above, as they are
+namespace gbnf {
+
+hipError_t img_allow_lds() {
+  hipError_t e = allow_lds<EPI_RELU>();
+  if (e == hipSuccess) e = allow_lds<EPI_STORE>();
+  if (e == hipSuccess) e = allow_lds<EPI_COUPLE_AFFINE>();
+  if (e == hipSuccess) e = allow_lds<EPI_COUPLE_ADD>();
+  if (e == hipSuccess) e = allow_lds<EPI_SPLIT>();
+  return e;
+}
+
+bool img_launch_conv(int epi, const ConvLaunch& p, int n, hipStream_t s) {
+  switch (epi) {
+    case EPI_RELU: launch_conv<EPI_RELU>(p, n, s); return true;
+    case EPI_STORE: launch_conv<EPI_STORE>(p, n, s); return true;
+    case EPI_COUPLE_AFFINE: launch_conv<EPI_COUPLE_AFFINE>(p, n, s); return true;
+    case EPI_COUPLE_ADD: launch_conv<EPI_COUPLE_ADD>(p, n, s); return true;
+    case EPI_SPLIT: launch_conv<EPI_SPLIT>(p, n, s); return true;
+    default: return false;
+  }
+}
+
+void img_launch_pre(const float* x, const float* noise, float* out, float* ldj, int C, int H, int W, int Hi, int Wi, float bounds,
+                    float ld_const, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(img_pre_kernel, dim3((unsigned)n), dim3(256), 0, s, x, noise, out, ldj, C, H, W, Hi, Wi, bounds, ld_const);
+}
+void img_launch_squeeze(const float* in, int64_t in_img, float* out, int C, int H, int W, int Ho, int Wo, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(img_squeeze_kernel, dim3((unsigned)n), dim3(256), 0, s, in, in_img, out, C, H, W, Ho, Wo);
+}
+void img_launch_unsqueeze(const float* in, float* out, int64_t out_img, int C, int H, int W, int Hs, int Ws, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(img_unsqueeze_kernel, dim3((unsigned)n), dim3(256), 0, s, in, out, out_img, C, H, W, (const float*)nullptr, 0, 0, 0, Hs, Ws);
+}
+void img_launch_embed(const float* z, float* out, int C, int H, int W, int Hv, int Wv, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(img_embed_kernel, dim3((unsigned)n), dim3(256), 0, s, z, out, C, H, W, Hv, Wv);
+}
+void img_launch_final(const float* state, int64_t state_img, const float* prior, const float* ldj, float* ll, float* z, int C, int H, int W,
+                      int Hv, int Wv, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(img_final_kernel, dim3((unsigned)n), dim3(256), 0, s, state, state_img, prior, ldj, ll, z, C, H, W, Hv, Wv);
+}
+
+}  // namespace gbnf

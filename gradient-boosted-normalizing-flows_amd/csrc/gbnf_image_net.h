@@ -45,4 +45,44 @@ size_t img_net_hx3_lds(int W, int chp, int cin, int pre_kc, int cout);
 // workgroups on 16-wide maps).
 hipError_t img_net_hx3_launch(const NetLaunch& q, int W, bool additive, int64_t n, hipStream_t s);
 
+// One launch of img_conv_kernel (gbnf_image.hip): an implicit-GEMM convolution of n images, strip by strip.
+struct ConvLaunch {
+  const float* in;        // (n, *, H, W): first input channel of image 0
+  int64_t in_img;         // floats between images
+  const float* wp;        // packed weights [OT][taps][KC][64][4]
+  const float* bias;      // [OT*16]
+  float* out;             // EPI_RELU / EPI_STORE: (n, *, H, W) first output channel of image 0
+  int64_t out_img;
+  float* st;              // EPI_COUPLE_* / EPI_SPLIT: the coupled half z2 (n, *, H, W), first channel of image 0
+  int64_t st_img;
+  float* ldj;             // (n,) accumulated with atomics (EPI_COUPLE_AFFINE / EPI_SPLIT)
+  int cin, cout, H, W, ks, n_strips;
+  int Hv, Wv;             // the map proper: rows < Hv, columns < Wv of the H x W storage (a 14 x 14 map lives in 16 x 16 storage;
+                          // everything outside is ZERO in every tensor in HBM -- the 'same' padding of the map -- and stays so)
+  float temperature;      // EPI_SPLIT_INV: z2 = mean + exp(log-var) * temperature * eps (models/layers.py:697)
+  int c_chunk;            // input channels staged per pass (a multiple of 16; 0 = all: 3 x 3 convolutions from > 256 channels do not
+                          // fit the LDS at once and stage their input in two halves; split-contraction form only)
+  int o_split;            // workgroups sharing one strip, each with 1/o_split of the output tiles (fills the chip at small batch)
+  // fused producer (1x1 convolutions only): the input of this convolution is relu(conv3x3(pre_in) + pre_bias), computed
+  // for the strip straight into LDS instead of being read from `in` (the ConvNet's first layer never touches HBM)
+  const float* pre_in;    // (n, *, H, W) first input channel of image 0, or null
+  int64_t pre_in_img;
+  const float* pre_wp;    // packed 3x3 weights [cin/16 tiles][9][pre_kc][64][4]
+  const float* pre_bias;
+  int pre_cin;
+};
+
+// ---- the evaluation path's kernels as the training path (gbnf_image_train.hip) launches them; defined in gbnf_image.hip.
+// img_allow_lds: the convolution kernels' opt-in to 160 KB of dynamic LDS on the CURRENT device.  img_launch_conv: epi = EPI_RELU,
+// EPI_STORE, EPI_COUPLE_AFFINE, EPI_COUPLE_ADD or EPI_SPLIT (false: another value); c_chunk and o_split are chosen here.
+hipError_t img_allow_lds();
+bool img_launch_conv(int epi, const ConvLaunch& p, int n, hipStream_t s);
+void img_launch_pre(const float* x, const float* noise, float* out, float* ldj, int C, int H, int W, int Hi, int Wi, float bounds,
+                    float ld_const, int64_t n, hipStream_t s);
+void img_launch_squeeze(const float* in, int64_t in_img, float* out, int C, int H, int W, int Ho, int Wo, int64_t n, hipStream_t s);
+void img_launch_unsqueeze(const float* in, float* out, int64_t out_img, int C, int H, int W, int Hs, int Ws, int64_t n, hipStream_t s);
+void img_launch_embed(const float* z, float* out, int C, int H, int W, int Hv, int Wv, int64_t n, hipStream_t s);
+void img_launch_final(const float* state, int64_t state_img, const float* prior, const float* ldj, float* ll, float* z, int C, int H, int W,
+                      int Hv, int Wv, int64_t n, hipStream_t s);
+
 }  // namespace gbnf

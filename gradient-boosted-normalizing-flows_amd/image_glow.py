@@ -8,7 +8,9 @@ reference checkpoint loads with ``load_state_dict``; every call that computes go
 Reference anchors: Glow (models/glow.py:12-110), FlowNet image branch (:192-252), FlowStep (:264-342), ActNorm2d /
 Conv2d / Conv2dZeros / Permute2d / Split2d / SqueezeLayer / InvertibleConv1x1 (models/layers.py:548-796), BoostedFlow
 (models/boosted_flow.py), the image likelihood ll = log_normal_diag(z, z_mu, z_var) + logdet (image_experiment.py:227).
-Not on the path: y_condition, learned dequantisation flows, training.  An un-initialised model (fresh from the constructor)
+Not on the path: y_condition, learned dequantisation flows.  In train mode with gradients enabled a component's forward runs on the
+live parameters and is differentiable (``native.NativeImageTrainer``: HIP forward and backward, exact f32; ``torch.optim`` on the
+resulting ``.grad`` is the supported step).  An un-initialised model (fresh from the constructor)
 is initialised from data with ``BoostedImageFlow.initialize_actnorms(x)`` -- what the reference's first training-mode forward
 does (models/layers.py:473-486) -- or by loading a trained checkpoint / ``set_actnorm_init``.
 """
@@ -123,6 +125,24 @@ class InvertibleConv1x1(nn.Module):
         u = self.upper.detach().double().cpu() * l_mask.t() + torch.diag(
             self.sign_s.double().cpu() * torch.exp(self.log_s.detach().double().cpu()))
         return (self.p.double().cpu() @ (lower @ u)).numpy()
+
+    def composed_weight_tensor(self):
+        """The same matrix as a differentiable float32 tensor on the parameters' device (the training path's 1x1 weight): the chain
+        from its gradient to lower / upper / log_s is torch autograd on C x C."""
+        if not self.LU_decomposed:
+            return self.weight
+        n = self.w_shape[0]
+        l_mask = torch.tril(torch.ones(n, n, dtype=self.lower.dtype, device=self.lower.device), -1)
+        lower = self.lower * l_mask + torch.eye(n, dtype=self.lower.dtype, device=self.lower.device)
+        u = self.upper * l_mask.t() + torch.diag(self.sign_s * torch.exp(self.log_s))
+        return self.p @ (lower @ u)
+
+    def composed_log_det(self):
+        """log|det| of that matrix, differentiable: sum(log_s) for the LU form, slogdet otherwise (models/layers.py:756, 790; C x C in
+        float64 on the parameters' device)."""
+        if self.LU_decomposed:
+            return self.log_s.sum()
+        return torch.linalg.slogdet(self.weight.double())[1].to(self.weight.dtype)
 
 
 class FlowStep(nn.Module):
@@ -294,8 +314,28 @@ def load_image_spec(glow, spec):
         _load_conv(glow.learn_top_fn, spec["learn_top"])
 
 
+class _ImageFlowFunction(torch.autograd.Function):
+    """(z, ldj) of one component on its live parameters (native.NativeImageTrainer); the backward calls the library.  ``tensors``: the
+    bound parameters in the order of ``paths`` (for an LU step the composed 1x1 matrix: autograd carries its gradient on to lower /
+    upper / log_s), saved for autograd's in-place-modification check only."""
+
+    @staticmethod
+    def forward(ctx, trainer, x, noise, paths, *tensors):
+        z, ldj, trace = trainer.forward(x, noise)
+        ctx.trainer, ctx.trace, ctx.paths = trainer, trace, paths
+        ctx.save_for_backward(*tensors)
+        return z, ldj
+
+    @staticmethod
+    def backward(ctx, g_z, g_ldj):
+        tensors = ctx.saved_tensors              # (raises if an optimiser stepped between forward and backward)
+        _, views = ctx.trainer.backward(ctx.trace, g_z.contiguous().float(), g_ldj.contiguous().float())
+        return (None, None, None, None) + tuple(views[p].view_as(t) for p, t in zip(ctx.paths, tensors))
+
+
 class BoostedImageFlow(nn.Module):
-    """models/boosted_flow.py:BoostedFlow for image components, density-evaluation path."""
+    """models/boosted_flow.py:BoostedFlow for image components: density evaluation, z -> x, and (train mode, gradients enabled) the
+    differentiable forward of one component."""
 
     def __init__(self, args):
         super().__init__()
@@ -315,6 +355,7 @@ class BoostedImageFlow(nn.Module):
         self.register_buffer("rho", rho.float())
         self.flows = nn.ModuleList([ImageGlow(args) for _ in range(self.num_components)])
         self._handles = {}
+        self._trainers = {}
         dev = getattr(args, "device", None)
         if dev is not None:
             self.to(dev)
@@ -371,13 +412,116 @@ class BoostedImageFlow(nn.Module):
     def _check(self, x):
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise native.GbnfError("x must live on the MI355X (cuda) device: this module has no CPU path")
-        if self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
-            raise RuntimeError("the image path is density evaluation only: call .eval() or use torch.no_grad()")
+
+    def _recording(self, c):
+        """Train mode with gradients enabled: the component's forward is recorded for autograd."""
+        return self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self._component_tensors(c)[0])
+
+    def native_trainer(self, c):
+        """(native.NativeImageTrainer bound to component c's live parameter storage, bindings), cached like ``native_flow`` and keyed
+        on the tensors' addresses (not their versions: an optimiser's in-place update needs no new trainer).  bindings: one
+        (path, parameter | InvertibleConv1x1 module, persistent composed matrix | None, pixels of the level) per bound tensor."""
+        flow = self.flows[c]
+        params, buffers, perms, actnorms = self._component_tensors(c)
+        if not all(bool(m.inited) for m in actnorms):
+            raise ValueError("ActNorm not initialised: call initialize_actnorms(x) (or load a checkpoint) before training")
+        key = tuple(t.data_ptr() for t in params) + tuple(t.data_ptr() for t in buffers) + \
+            tuple((m.indices_serial, int(m.indices._version)) for m in perms)
+        cached = self._trainers.get(c)
+        if cached is not None and cached[0] == key:
+            return cached[1], cached[2]
+        bind = []
+
+        def conv(m, path):
+            zeros = isinstance(m, Conv2dZeros)
+            out = {"w": m.conv.weight, "b": m.conv.bias, "an_bias": None if zeros else m.actnorm.bias,
+                   "an_logs": None if zeros else m.actnorm.logs, "logs": m.logs if zeros else None}
+            for k in native.NativeImageTrainer.CONV_KEYS:
+                if out[k] is not None:
+                    bind.append((path + (k,), out[k], None))
+                    out[k] = out[k].detach()
+            return out
+
+        levels, steps, coupling = [], [], None
+        for layer in flow.flow.layers:
+            l, k = len(levels), len(steps)
+            if isinstance(layer, FlowStep):
+                path = ("levels", l, "steps", k)
+                st = {"an_bias": layer.actnorm.bias.detach(), "an_logs": layer.actnorm.logs.detach(), "perm_w": None, "perm": None}
+                bind.append((path + ("an_bias",), layer.actnorm.bias, None))
+                bind.append((path + ("an_logs",), layer.actnorm.logs, None))
+                if hasattr(layer, "invconv"):
+                    inv = layer.invconv
+                    # LU: one persistent (C, C) tensor per step, the composed matrix is copied in before each forward.  So is a plain
+                    # weight that is not row-major in memory (the constructor's QR factor is column-major): the library binds rows.
+                    if inv.LU_decomposed or not inv.weight.is_contiguous():
+                        st["perm_w"] = torch.empty(tuple(inv.w_shape), dtype=torch.float32, device=actnorms[0].bias.device)
+                        bind.append((path + ("perm_w",), inv, st["perm_w"]))
+                    else:
+                        st["perm_w"] = inv.weight.detach()
+                        bind.append((path + ("perm_w",), inv, None))
+                else:
+                    pm = layer.shuffle if hasattr(layer, "shuffle") else layer.reverse
+                    st["perm"] = np.asarray(pm.indices.cpu().numpy(), dtype=np.int64)
+                st["convs"] = [conv(m, path + ("convs", q))
+                               for q, m in enumerate(mm for mm in layer.block.network if not isinstance(mm, nn.ReLU))]
+                coupling = layer.flow_coupling
+                steps.append(st)
+            elif isinstance(layer, Split2d):
+                levels.append({"steps": steps, "split": conv(layer.conv, ("levels", l, "split"))})
+                steps = []
+        levels.append({"steps": steps, "split": None})
+        dev_spec = {"kind": "glow_image", "input_size": list(flow.input_size), "hidden": flow.hidden, "coupling": coupling,
+                    "bounds": float(flow.bounds.item()), "levels": levels, "learn_top": None}
+        with torch.cuda.device(params[0].device):
+            trainer = native.NativeImageTrainer(dev_spec)
+        self._trainers[c] = (key, trainer, bind)
+        return trainer, bind
+
+    def _component_forward_train(self, x, c, noise):
+        """Differentiable (z, z_mu, z_var, ldj, None) of component c on its live parameters (models/glow.py:92-110)."""
+        if x.requires_grad:
+            raise NotImplementedError("the image training path has no gradient with respect to x")
+        flow = self.flows[c]
+        trainer, bind = self.native_trainer(c)
+        paths, tensors, log_dets, plain = [], [], [], {}
+        for path, obj, persistent in bind:
+            if isinstance(obj, InvertibleConv1x1):
+                w = obj.composed_weight_tensor()
+                if persistent is not None:
+                    with torch.no_grad():
+                        persistent.copy_(w)
+                if obj.LU_decomposed:
+                    log_dets.append(trainer.level_pixels[path[1]] * obj.composed_log_det())
+                else:                                    # plain matrices: ONE batched float64 slogdet per level, on the device
+                    plain.setdefault(path[1], []).append(w)
+                obj = w
+            paths.append(path)
+            tensors.append(obj)
+        with torch.cuda.device(x.device):
+            z, ldj = _ImageFlowFunction.apply(trainer, x, noise, tuple(paths), *tensors)
+        for l, ws in plain.items():
+            log_dets.append(trainer.level_pixels[l] * torch.linalg.slogdet(torch.stack(ws).double())[1].sum().to(z.dtype))
+        if log_dets:                                     # the 1x1 matrices' own log-determinants: closed form on C x C
+            ldj = ldj + torch.stack(log_dets).sum()
+        Cz = z.shape[1]
+        if flow.learn_top:                               # Conv2dZeros of a zero input: bias * exp(3 logs); its weight gets a zero gradient
+            top = flow.learn_top_fn
+            h = top.conv.bias * torch.exp(top.logs.view(-1) * top.logscale_factor) + 0.0 * top.conv.weight.sum()
+            z_mu, z_var = h[:Cz].view(1, -1, 1, 1).expand(z.shape), h[Cz:].view(1, -1, 1, 1).expand(z.shape)
+        else:
+            z_mu = z_var = torch.zeros((), dtype=z.dtype, device=z.device).expand(z.shape)
+        return z, z_mu, z_var, ldj, None
 
     def component_forward(self, x, c, noise=None, want_z=True):
         """x (N,C,H,W) in [0,1] -> z, ldj, ll of component c.  ``noise``: the U(0,1) dequantisation noise
-        (models/glow.py:135); drawn on the device when None."""
+        (models/glow.py:135); drawn on the device when None.  In train mode with gradients enabled: the differentiable
+        (z, z_mu, z_var, ldj, None) of ``forward`` on the live parameters instead."""
         self._check(x)
+        if self._recording(int(c)):
+            xx = x if x.requires_grad else x.contiguous().float()
+            nn_ = torch.rand_like(xx) if noise is None else noise.contiguous().float()
+            return self._component_forward_train(xx, int(c), nn_)
         x = x.contiguous().float()
         if noise is None:
             noise = torch.rand_like(x)
@@ -438,6 +582,9 @@ class BoostedImageFlow(nn.Module):
         if reverse:
             return self.decode(z, y_onehot, temperature, components)
         c = self._sample_component(components) if isinstance(components, str) else int(components)
+        self._check(x)
+        if self._recording(c):
+            return self.component_forward(x, c)
         zz, ldj, _ = self.component_forward(x, c)
         handle = self.native_flow(c)
         prior = self._prior_on(handle, x.device)

@@ -44,6 +44,8 @@ ABI_SYMBOLS = (
     "gbnf_resample_workspace_bytes", "gbnf_resample_rows", "gbnf_boosted_step_workspace_bytes", "gbnf_boosted_nll_step",
     "gbnf_mixture_rho_step",
     "gbnf_flow_numerics_inverse", "gbnf_image_flow_inverse_check_counts",
+    "gbnf_image_trainer_create", "gbnf_image_trainer_destroy", "gbnf_image_trainer_trace_floats", "gbnf_image_trainer_workspace_bytes",
+    "gbnf_image_trainer_forward", "gbnf_image_trainer_grad_floats", "gbnf_image_trainer_backward",
 )
 
 
@@ -216,6 +218,13 @@ def lib():
     L.gbnf_group_graph_launch.argtypes = [vp, vp]
     L.gbnf_group_graph_destroy.argtypes = [vp]
     L.gbnf_image_flow_eps_floats.argtypes = [vp, C.POINTER(i64)]
+    L.gbnf_image_trainer_create.argtypes = [C.POINTER(_ImageFlowDesc), C.POINTER(vp)]
+    L.gbnf_image_trainer_destroy.argtypes = [vp]
+    L.gbnf_image_trainer_trace_floats.argtypes = [vp, i64, C.POINTER(i64)]
+    L.gbnf_image_trainer_workspace_bytes.argtypes = [vp, i64, C.POINTER(i64)]
+    L.gbnf_image_trainer_forward.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
+    L.gbnf_image_trainer_grad_floats.argtypes = [vp, C.POINTER(i64)]
+    L.gbnf_image_trainer_backward.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.gbnf_image_flow_inverse.argtypes = [vp, vp, vp, C.c_float, i64, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
@@ -582,6 +591,179 @@ class NativeImageFlow:
     def close(self):
         if getattr(self, "handle", None):
             lib().gbnf_image_flow_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+class NativeImageTrainer:
+    """Training path of one image Glow component (gbnf_image_trainer): forward on the LIVE device parameters and the backward pass,
+    exact f32.
+
+    ``dev_spec`` has the shape of an image flow spec (synth.synth_image_glow_spec) but every float array is a contiguous float32
+    CUDA tensor -- the caller's parameter storage itself (``perm`` stays a host int64 array; ``perm_w`` is the composed C x C matrix
+    of an InvertibleConv1x1).  Nothing is copied: the library keeps the addresses, this object keeps the tensors alive.  ``learn_top``
+    is ignored (the top prior is the caller's).  ``ldj`` of ``forward`` EXCLUDES the log-determinants of the ``perm_w`` matrices."""
+
+    CONV_KEYS = ("w", "b", "an_bias", "an_logs", "logs")          # order of a convolution's arrays in the flat gradient buffer
+
+    def __init__(self, dev_spec):
+        self._tensors = []
+        self._regions = []          # (path, offset, shape) in the order of the flat gradient buffer
+        self._off = 0
+        fp = C.POINTER(C.c_float)
+        keep = _Keep()
+
+        def dptr(t):
+            _require_device_f32(t, "parameter")
+            self._tensors.append(t)
+            return C.cast(C.c_void_p(t.data_ptr()), fp)
+
+        def region(path, t):
+            self._regions.append((path, self._off, tuple(t.shape)))
+            self._off += t.numel()
+
+        def conv(c, path):
+            w = c["w"]
+            cc = _Conv()
+            cc.out_channels, cc.in_channels, cc.kernel_size = int(w.shape[0]), int(w.shape[1]), int(w.shape[2])
+            for field, key in (("weight", "w"), ("bias", "b"), ("actnorm_bias", "an_bias"), ("actnorm_logs", "an_logs"), ("logs", "logs")):
+                if c.get(key) is not None:
+                    if key != "w" and c[key].numel() != cc.out_channels:
+                        raise GbnfError(f"{path + (key,)}: {c[key].numel()} elements, expected {cc.out_channels}")
+                    setattr(cc, field, dptr(c[key]))
+                    region(path + (key,), c[key])
+            return cc
+
+        desc = _ImageFlowDesc()
+        desc.channels, desc.height, desc.width = (int(v) for v in dev_spec["input_size"])
+        desc.n_levels = len(dev_spec["levels"])
+        desc.coupling = COUPLING[dev_spec.get("coupling") or "affine"]
+        desc.hidden = int(dev_spec["hidden"])
+        desc.bounds = float(dev_spec.get("bounds", 0.9))
+        levels = (_ImageLevel * desc.n_levels)()
+        ch, hh, ww = desc.channels, desc.height, desc.width
+        self.level_pixels = []
+        for l, lv in enumerate(dev_spec["levels"]):
+            ch, hh, ww = ch * 4, hh // 2, ww // 2
+            self.level_pixels.append(hh * ww)
+            steps = (_ImageStep * len(lv["steps"]))()
+            for k, st in enumerate(lv["steps"]):
+                path = ("levels", l, "steps", k)
+                s_ = _ImageStep()
+                for key in ("an_bias", "an_logs"):
+                    if st[key].numel() != ch:
+                        raise GbnfError(f"{path + (key,)}: {st[key].numel()} elements, expected {ch}")
+                s_.actnorm_bias = dptr(st["an_bias"])
+                region(path + ("an_bias",), st["an_bias"])
+                s_.actnorm_logs = dptr(st["an_logs"])
+                region(path + ("an_logs",), st["an_logs"])
+                if st.get("perm_w") is not None:
+                    if tuple(st["perm_w"].shape) != (ch, ch):
+                        raise GbnfError(f"{path + ('perm_w',)}: shape {tuple(st['perm_w'].shape)}, expected {(ch, ch)}")
+                    s_.perm_weight = dptr(st["perm_w"])
+                    region(path + ("perm_w",), st["perm_w"])
+                else:
+                    s_.perm_indices = keep.i64(st["perm"])
+                arr = (_Conv * len(st["convs"]))(*[conv(c, path + ("convs", q)) for q, c in enumerate(st["convs"])])
+                keep.refs.append(arr)
+                s_.n_convs, s_.convs = len(st["convs"]), arr
+                steps[k] = s_
+            keep.refs.append(steps)
+            levels[l].n_steps, levels[l].steps = len(lv["steps"]), steps
+            if lv["split"] is not None:
+                sp = conv(lv["split"], ("levels", l, "split"))
+                keep.refs.append(sp)
+                levels[l].split_prior = C.pointer(sp)
+                ch //= 2
+        desc.levels = levels
+        self.input_size = (desc.channels, desc.height, desc.width)
+        self.z_shape = (ch, hh, ww)
+        h = C.c_void_p()
+        _check(lib().gbnf_image_trainer_create(C.byref(desc), C.byref(h)))
+        del keep
+        self.handle = h
+        nf = C.c_int64()
+        _check(lib().gbnf_image_trainer_grad_floats(h, C.byref(nf)))
+        self.grad_floats = int(nf.value)
+        if self.grad_floats != self._off:
+            raise GbnfError("gradient-buffer layout mismatch between the library and the binding")
+        self.device = self._tensors[0].device
+        self._ws = None
+
+    def key(self):
+        return tuple(t.data_ptr() for t in self._tensors)
+
+    def _workspace(self, n):
+        import torch
+        nb = C.c_int64()
+        _check(lib().gbnf_image_trainer_workspace_bytes(self.handle, n, C.byref(nb)))
+        if self._ws is None or self._ws.numel() * 4 < nb.value:
+            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=self.device)
+        return self._ws
+
+    def forward(self, x, noise=None, want_trace=True):
+        """x (n,C,H,W) in [0,1] (+ dequantisation noise) -> (z, ldj (n,), trace | None) on the live parameters; current stream."""
+        import torch
+        _require_device_f32(x, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
+            raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        n = x.shape[0]
+        z = torch.empty((n,) + self.z_shape, dtype=torch.float32, device=x.device)
+        ldj = torch.empty(n, dtype=torch.float32, device=x.device)
+        nt = C.c_int64()
+        _check(lib().gbnf_image_trainer_trace_floats(self.handle, n, C.byref(nt)))
+        trace = torch.empty(nt.value, dtype=torch.float32, device=x.device)      # (the state storage of the pass: always needed)
+        if n:
+            ws = self._workspace(n)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+            _check(lib().gbnf_image_trainer_forward(self.handle, ptr(x), ptr(noise), n, ptr(z), ptr(ldj), ptr(trace), ptr(ws),
+                                                    ws.numel() * 4, _stream_ptr()))
+        return z, ldj, (trace if want_trace else None)
+
+    def backward(self, trace, g_z=None, g_ldj=None, out=None):
+        """-> (flat gradient buffer, {path: view}) with path = ("levels", l, "steps", k, "an_bias" | "an_logs" | "perm_w") |
+        ("levels", l, "steps", k, "convs", q, key) | ("levels", l, "split", key), key in CONV_KEYS.  ``out``: a flat buffer to
+        ACCUMULATE into (None: a zeroed one)."""
+        import torch
+        _require_device_f32(trace, "trace")
+        nt = C.c_int64()
+        _check(lib().gbnf_image_trainer_trace_floats(self.handle, 1, C.byref(nt)))
+        if nt.value == 0 or trace.numel() % nt.value:
+            raise GbnfError("trace is not one of this trainer's")
+        n = trace.numel() // nt.value
+        if g_z is not None:
+            _require_device_f32(g_z, "g_z")
+            if tuple(g_z.shape) != (n,) + self.z_shape:
+                raise GbnfError(f"g_z must be {(n,) + self.z_shape}, got {tuple(g_z.shape)}")
+        if g_ldj is not None:
+            _require_device_f32(g_ldj, "g_ldj")
+            if tuple(g_ldj.shape) != (n,):
+                raise GbnfError(f"g_ldj must be ({n},), got {tuple(g_ldj.shape)}")
+        if out is None:
+            out = torch.zeros(self.grad_floats, dtype=torch.float32, device=trace.device)
+        else:
+            _require_device_f32(out, "out")
+            if out.numel() != self.grad_floats:
+                raise GbnfError(f"out has {out.numel()} elements, expected {self.grad_floats}")
+        if n:
+            ws = self._workspace(n)
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+            _check(lib().gbnf_image_trainer_backward(self.handle, ptr(trace), n, ptr(g_z), ptr(g_ldj), ptr(out), ptr(ws),
+                                                     ws.numel() * 4, _stream_ptr()))
+        return out, {path: out[off: off + int(np.prod(shape))].view(shape) for path, off, shape in self._regions}
+
+    def close(self):
+        if getattr(self, "handle", None):
+            lib().gbnf_image_trainer_destroy(self.handle)
             self.handle = None
 
     def __del__(self):

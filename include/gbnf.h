@@ -605,7 +605,7 @@ typedef struct gbnf_image_flow gbnf_image_flow;
  * <= 64 channels per level; coupling ConvNets of hidden width <= 512 with 2 .. 5 convolutions (coupling_network_depth 0 .. 3);
  * the split-f16 kernels serve depth 1 at every hidden width (above 256 the fused kernel works in two halves of the hidden
  * channels), depth 0 and 2 to hidden width 256 (round 6), and <= 24 input channels of the first 3 x 3 (the 48-channel third level of a
- * 3 x 32 x 32 input); everything else runs on the exact-f32 convolution kernels.  Not built: y-conditioning, learned dequantisation flows, image training. */
+ * 3 x 32 x 32 input); everything else runs on the exact-f32 convolution kernels.  Not built: y-conditioning, learned dequantisation flows. */
 int gbnf_image_flow_create(const gbnf_image_flow_desc* desc, gbnf_image_flow** out);
 /* ... with an explicit GBNF_MATH_* mode: DEFAULT (what gbnf_image_flow_create does: split-f16 coupling nets if the create-time
  * probe passes), F32 (exact-f32 convolutions everywhere, no probe), F16X3. */
@@ -683,6 +683,44 @@ int gbnf_image_flow_actnorm_stats(const gbnf_image_flow* flow, const float* x, c
 int gbnf_image_flow_eps_floats(const gbnf_image_flow* flow, int64_t* per_image);
 int gbnf_image_flow_inverse(const gbnf_image_flow* flow, const float* z, const float* eps, float temperature, int64_t n,
                             float* x, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------------------
+ * Training path of ONE image Glow component: the forward on the LIVE parameters and its backward pass, exact f32
+ * (the image counterpart of gbnf_trainer_*).  The descriptor is the evaluation one, but every float pointer is a DEVICE
+ * pointer to the caller's live tensor in its reference layout (perm_indices stay HOST pointers, read at creation).
+ * Nothing is copied: every forward call re-derives the kernels' weight tiles from the tensors on the device (one launch),
+ * so parameters an optimiser updates in place are seen by the next call; re-create the trainer only when a tensor is
+ * re-allocated.  `learn_top` is ignored: the top prior is the caller's (a Conv2dZeros of a zero input is
+ * bias * exp(3 logs), differentiable in closed form).  The limits are those of gbnf_image_flow_create with 1 to 3 levels
+ * and the same depth and width in every coupling net; anything else answers GBNF_ERR_UNSUPPORTED with the reason.
+ * Calls on one trainer must not run concurrently (the weight tiles are the trainer's).
+ * --------------------------------------------------------------------------------------------------------------- */
+typedef struct gbnf_image_trainer gbnf_image_trainer;
+int gbnf_image_trainer_create(const gbnf_image_flow_desc* desc_device_params, gbnf_image_trainer** out);
+int gbnf_image_trainer_destroy(gbnf_image_trainer* trainer);
+/* Floats of the trace buffer / bytes of the workspace (forward and backward share one size) at a batch of n images. */
+int gbnf_image_trainer_trace_floats(const gbnf_image_trainer* trainer, int64_t n, int64_t* floats);
+int gbnf_image_trainer_workspace_bytes(const gbnf_image_trainer* trainer, int64_t n, int64_t* bytes);
+/* x, noise, z as gbnf_image_flow_forward (z may be NULL); the same values as a GBNF_MATH_F32 evaluation handle with ONE
+ * difference: ldj (n,) EXCLUDES the log-determinants of the 1 x 1 `perm_weight` matrices.  The caller adds
+ * sum over the steps of H_l * W_l * log|det W| (H_l x W_l: the map of the step's level): a per-component scalar,
+ * differentiable in closed form on C x C matrices.  trace (required) receives what the backward needs: per level the
+ * level's input and, per FlowStep, the state behind its ActNorm2d + 1 x 1 (the coupling's input) and the step's output
+ * (the last one is the Split2d's input).  Hidden activations are not kept: the backward recomputes them. */
+int gbnf_image_trainer_forward(gbnf_image_trainer* trainer, const float* x, const float* noise, int64_t n, float* z,
+                               float* ldj, float* trace, void* workspace, int64_t workspace_bytes, void* stream);
+/* Floats of the flat gradient buffer.  Layout, in descriptor order:  per level, per step:
+ *   [actnorm bias (C)] [actnorm logs (C)] [perm_weight (C*C), when not NULL]
+ *   then per convolution of the step, those arrays that are present: [weight] [bias] [actnorm_bias] [actnorm_logs] [logs];
+ * behind a level's steps, the level's split_prior convolution in the same form. */
+int gbnf_image_trainer_grad_floats(const gbnf_image_trainer* trainer, int64_t* floats);
+/* trace: what gbnf_image_trainer_forward left at the same n, parameters unchanged since.  g_z (n,Cz,Hz,Wz) and g_ldj (n,)
+ * may each be NULL, meaning zero.  ACCUMULATES into grads (the caller zeroes it).  The ActNorm2d `logs` gradients include
+ * the H*W * sum_n g_ldj[n] term of their own log-determinant; the `perm_weight` gradient is the data path only, consistent
+ * with the forward.  There is no gradient with respect to x.  Weight gradients are summed with float atomics: the last
+ * bits depend on the order. */
+int gbnf_image_trainer_backward(gbnf_image_trainer* trainer, const float* trace, int64_t n, const float* g_z,
+                                const float* g_ldj, float* grads, void* workspace, int64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
