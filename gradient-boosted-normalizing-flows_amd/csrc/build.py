@@ -214,8 +214,14 @@ def main(argv=None):
     # the image training path (pack / weight-gradient / unfold kernels; the convolutions themselves are gbnf_image.hip's)
     imgt_o, imgt_src = os.path.join(OBJ, "gbnf_image_train.o"), os.path.join(HERE, "gbnf_image_train.hip")
     objs.append(imgt_o)
-    if args.force or not newer(imgt_o, [imgt_src, os.path.join(HERE, "gbnf_image_net.h"), hdr[2], hdr[3]]):
+    imgt_hdr = os.path.join(HERE, "gbnf_image_train.h")
+    if args.force or not newer(imgt_o, [imgt_src, imgt_hdr, os.path.join(HERE, "gbnf_image_net.h"), hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", imgt_src, "-o", imgt_o])
+    # one image training step in one call (1x1 log-dets and LU chain, loss seed, top prior; the update is gbnf_opt.hip's): gbnf_image_opt.hip
+    imgo_o, imgo_src = os.path.join(OBJ, "gbnf_image_opt.o"), os.path.join(HERE, "gbnf_image_opt.hip")
+    objs.append(imgo_o)
+    if args.force or not newer(imgo_o, [imgo_src, imgt_hdr, opt_hdr, hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", imgo_src, "-o", imgo_o])
     comm_o, comm_src = os.path.join(OBJ, "gbnf_comm.o"), os.path.join(HERE, "gbnf_comm.hip")
     objs.append(comm_o)
     if args.force or not newer(comm_o, [comm_src, hdr[2], hdr[3]]):

@@ -1,0 +1,54 @@
+// gbnf_image_train.h -- the image trainer (gbnf_image_train.hip) as the one-call training step (gbnf_image_opt.hip) sees it; not part
+// of the C ABI.
+#pragma once
+#include <cstdint>
+#include <vector>
+#include "../../include/gbnf.h"
+
+namespace gbnf {
+
+// One convolution of the component -- or the 1x1 "mix" of a FlowStep (ActNorm2d then invconv / permutation) -- as the pack, weight
+// gradient and unfold kernels see it.  Parameter pointers are the caller's live device arrays.
+struct TConv {
+  const float* w;          // (cout, cin, ks, ks); mix: the C x C matrix (perm_weight, or the 0/1 matrix of a permutation)
+  const float* bias;       // Conv2dZeros bias or null
+  const float* an_bias;    // ActNorm2d behind a Conv2d, or null; mix: the step's ActNorm2d bias
+  const float* an_logs;    //   ... logs
+  const float* logs;       // Conv2dZeros logs or null
+  int cout, cin, ks, mix;
+  int64_t fwd_off, bwd_off, b_off;                            // floats into the pack blob: forward tiles, adjoint tiles, folded bias
+  int64_t gw_off, gb_off;                                     // floats into the (dW', db') scratch
+  int64_t g_w, g_bias, g_an_bias, g_an_logs, g_logs;          // floats into the flat gradient buffer, -1 = absent
+  float hw;                // mix: pixels of the level's map (its ActNorm2d log-det is hw * sum(logs))
+};
+
+// The state of gbnf_image_trainer_nll_step / _apply_update: the LU and top-prior bindings, the region table of the update kernel, the
+// trainer-owned partial sums.  Built at the end of gbnf_image_trainer_create and rebuilt by every bind call (so that a step allocates
+// and copies nothing); freed by gbnf_image_trainer_destroy.  gbnf_image_opt.hip
+struct ImageStepState;
+int image_step_state_create(gbnf_image_trainer* t);
+void image_step_state_destroy(ImageStepState* s);
+
+}  // namespace gbnf
+
+struct gbnf_image_trainer {
+  int C = 0, H = 32, W = 32, Hi = 0, Wi = 0, L = 0, hidden = 0, additive = 0;
+  float bounds = 0.9f;
+  double ld_const = 0;                         // dequantisation only: everything else is read from the live parameters
+  struct Level { int C, H, W, Hv, Wv, K; };
+  std::vector<Level> levels;
+  std::vector<gbnf::TConv> table;                    // per level: per step [mix, convs ...], then the split prior
+  std::vector<std::vector<int>> step_first;    // [level][step] -> index of the step's mix entry (its convs follow)
+  std::vector<int> step_convs;                 // convolutions of a step's net
+  std::vector<int> split_entry;                // [level] -> entry or -1
+  gbnf::TConv* table_dev = nullptr;
+  float* blob_dev = nullptr;                   // packs; [zero_off, zero_off + 1024): zeros (bias of the adjoint launches, the prior)
+  float* perm_dev = nullptr;                   // the 0/1 matrices of Permute2d steps
+  int64_t blob_floats = 0, zero_off = 0, scratch_floats = 0, grad_floats = 0;
+  int zC = 0, zH = 0, zW = 0;
+  int n_net = 0;                               // convolutions per coupling net
+  int64_t state_img = 0;                       // floats of the largest state tensor of one image
+  int64_t trace_img = 0;                       // trace floats per image
+  gbnf::ImageStepState* step = nullptr;        // what the one-call training step adds (gbnf_image_opt.hip): bindings, region table, partial sums
+};
+

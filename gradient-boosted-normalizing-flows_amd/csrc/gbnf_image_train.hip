@@ -36,6 +36,7 @@
 #include "../../include/gbnf.h"
 #include "gbnf_internal.h"
 #include "gbnf_image_net.h"
+#include "gbnf_image_train.h"
 
 namespace gbnf {
 
@@ -43,21 +44,6 @@ using f32x4 = __attribute__((ext_vector_type(4))) float;
 
 constexpr int TR_R = 4;            // rows of a strip (IMG_R of gbnf_image.hip)
 constexpr int WGRAD_ITEMS[3] = {6, 4, 2};     // least (image, strip) items per weight-gradient workgroup: first 3x3, last 3x3, 1x1 (launch_wgrad)
-
-// One convolution of the component -- or the 1x1 "mix" of a FlowStep (ActNorm2d then invconv / permutation) -- as the pack, weight
-// gradient and unfold kernels see it.  Parameter pointers are the caller's live device arrays.
-struct TConv {
-  const float* w;          // (cout, cin, ks, ks); mix: the C x C matrix (perm_weight, or the 0/1 matrix of a permutation)
-  const float* bias;       // Conv2dZeros bias or null
-  const float* an_bias;    // ActNorm2d behind a Conv2d, or null; mix: the step's ActNorm2d bias
-  const float* an_logs;    //   ... logs
-  const float* logs;       // Conv2dZeros logs or null
-  int cout, cin, ks, mix;
-  int64_t fwd_off, bwd_off, b_off;                            // floats into the pack blob: forward tiles, adjoint tiles, folded bias
-  int64_t gw_off, gb_off;                                     // floats into the (dW', db') scratch
-  int64_t g_w, g_bias, g_an_bias, g_an_logs, g_logs;          // floats into the flat gradient buffer, -1 = absent
-  float hw;                // mix: pixels of the level's map (its ActNorm2d log-det is hw * sum(logs))
-};
 
 __device__ __forceinline__ float tconv_value(const TConv& e, int co, int ci, int tap) {
   const int taps = e.ks * e.ks;
@@ -353,26 +339,6 @@ using namespace gbnf;
 // ---------------------------------------------------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------------------------------------------------
-struct gbnf_image_trainer {
-  int C = 0, H = 32, W = 32, Hi = 0, Wi = 0, L = 0, hidden = 0, additive = 0;
-  float bounds = 0.9f;
-  double ld_const = 0;                         // dequantisation only: everything else is read from the live parameters
-  struct Level { int C, H, W, Hv, Wv, K; };
-  std::vector<Level> levels;
-  std::vector<TConv> table;                    // per level: per step [mix, convs ...], then the split prior
-  std::vector<std::vector<int>> step_first;    // [level][step] -> index of the step's mix entry (its convs follow)
-  std::vector<int> step_convs;                 // convolutions of a step's net
-  std::vector<int> split_entry;                // [level] -> entry or -1
-  TConv* table_dev = nullptr;
-  float* blob_dev = nullptr;                   // packs; [zero_off, zero_off + 1024): zeros (bias of the adjoint launches, the prior)
-  float* perm_dev = nullptr;                   // the 0/1 matrices of Permute2d steps
-  int64_t blob_floats = 0, zero_off = 0, scratch_floats = 0, grad_floats = 0;
-  int zC = 0, zH = 0, zW = 0;
-  int n_net = 0;                               // convolutions per coupling net
-  int64_t state_img = 0;                       // floats of the largest state tensor of one image
-  int64_t trace_img = 0;                       // trace floats per image
-};
-
 namespace {
 
 int64_t tile_floats(int cout, int cin, int ks) { return (int64_t)((cout + 15) / 16) * ((cin + 15) / 16) * ks * ks * 256; }
@@ -479,6 +445,7 @@ int gbnf_image_trainer_destroy(gbnf_image_trainer* t) {
   if (t->table_dev) (void)hipFree(t->table_dev);
   if (t->blob_dev) (void)hipFree(t->blob_dev);
   if (t->perm_dev) (void)hipFree(t->perm_dev);
+  image_step_state_destroy(t->step);
   delete t;
   return GBNF_OK;
 }
@@ -585,6 +552,7 @@ int gbnf_image_trainer_create(const gbnf_image_flow_desc* d, gbnf_image_trainer*
     if (e == hipSuccess) e = hipMemset(t->blob_dev, 0, (size_t)t->blob_floats * 4);
     if (e == hipSuccess) e = img_allow_lds();
     if (e != hipSuccess) rc = fail(GBNF_ERR_HIP, "gbnf_image_trainer_create: %s", hipGetErrorString(e));
+    if (rc == GBNF_OK) rc = image_step_state_create(t);
   }
   if (rc != GBNF_OK) {
     gbnf_image_trainer_destroy(t);

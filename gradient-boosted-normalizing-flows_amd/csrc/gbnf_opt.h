@@ -31,6 +31,19 @@ struct TrainerOptView {
   OptBnTable bn;
 };
 int trainer_opt_view(const gbnf_trainer* t, TrainerOptView* out);
+// What the norm + update launches need, for an owner that is not a gbnf_trainer (the image trainer, gbnf_image_opt.hip): the region
+// table on the device (sorted by offset, reserved regions not listed) and the floats of the flat gradient buffer.
+struct OptUpdateView {
+  const OptRegion* regions_dev;
+  int n_regions;
+  int64_t grad_floats;
+};
+// grad_sqsum_kernel into `partials` (OPT_MAX_PARTIALS doubles), then opt_update_kernel: the clip coefficient, the update of every
+// region's tensor in place, stats[1..3]; with nll_partial, stats[0] = sum(nll_partial) * nll_scale + nll_const.  Two launches on
+// `stream` (a hipStream_t), no host read.  `fn` names the entry point in a launch error.  gbnf_opt.hip
+int opt_launch_update(const char* fn, const OptUpdateView& view, const float* grads, float* m, float* v, const gbnf_opt_hyper* h,
+                      float* stats, double* partials, const double* nll_partial, int n_nll_partial, double nll_scale, double nll_const,
+                      void* stream);
 // What every call that ends in an update refuses before it launches anything (GBNF_ERR_INVALID: null hyper, unknown kind, AdamW with
 // step <= 0 or without state); `fn` names the entry point in the message.  gbnf_opt.hip
 int check_hyper(const char* fn, const gbnf_opt_hyper* h, const float* m, const float* v);

@@ -208,8 +208,9 @@ int check_hyper(const char* fn, const gbnf_opt_hyper* h, const float* m, const f
 }
 
 // norm partials -> clip coefficient + update (+ the loss of nll_step) -- two launches
-static int launch_update(const TrainerOptView& tv, const float* grads, float* m, float* v, const gbnf_opt_hyper* h, float* stats,
-                         double* partials, const double* nll_partial, int n_nll_partial, int64_t n, hipStream_t s) {
+int opt_launch_update(const char* fn, const OptUpdateView& tv, const float* grads, float* m, float* v, const gbnf_opt_hyper* h, float* stats,
+                      double* partials, const double* nll_partial, int n_nll_partial, double nll_scale, double nll_const, void* stream) {
+  hipStream_t s = (hipStream_t)stream;
   const unsigned gb = partial_blocks(tv.grad_floats);
   hipLaunchKernelGGL(grad_sqsum_kernel, dim3(gb), dim3(OPT_THREADS), 0, s, grads, tv.grad_floats, partials);
   OptLaunch p{};
@@ -218,8 +219,8 @@ static int launch_update(const TrainerOptView& tv, const float* grads, float* m,
   p.grad_partial = partials; p.n_grad_partial = (int)gb;
   p.nll_partial = nll_partial; p.n_nll_partial = n_nll_partial;
   if (nll_partial != nullptr) {
-    p.nll_scale = 1.0 / (double)n;
-    p.nll_const = 0.5 * (double)tv.d * std::log(2.0 * M_PI);
+    p.nll_scale = nll_scale;
+    p.nll_const = nll_const;
   }
   p.max_norm = h->max_grad_norm;
   p.lr = h->lr; p.wd = h->weight_decay; p.b1 = h->beta1; p.b2 = h->beta2; p.eps = h->eps;
@@ -235,8 +236,17 @@ static int launch_update(const TrainerOptView& tv, const float* grads, float* m,
   const int64_t per = OPT_THREADS * OPT_ITEMS;
   hipLaunchKernelGGL(opt_update_kernel, dim3((unsigned)((tv.grad_floats + per - 1) / per)), dim3(OPT_THREADS), 0, s, p);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_apply_update launch: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s launch: %s", fn, hipGetErrorString(e));
   return GBNF_OK;
+}
+
+// ... for a gbnf_trainer: the tabular loss is nll = sum / n + 0.5 d log 2 pi
+static int launch_update(const TrainerOptView& tv, const float* grads, float* m, float* v, const gbnf_opt_hyper* h, float* stats,
+                         double* partials, const double* nll_partial, int n_nll_partial, int64_t n, hipStream_t s) {
+  const OptUpdateView view{tv.regions_dev, tv.n_regions, tv.grad_floats};
+  const bool loss = nll_partial != nullptr;
+  return opt_launch_update("gbnf_trainer_apply_update", view, grads, m, v, h, stats, partials, nll_partial, n_nll_partial,
+                           loss ? 1.0 / (double)n : 0.0, loss ? 0.5 * (double)tv.d * std::log(2.0 * M_PI) : 0.0, (void*)s);
 }
 
 // the caller's workspace of one whole step, in 256-byte aligned pieces

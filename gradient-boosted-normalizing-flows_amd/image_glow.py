@@ -478,6 +478,103 @@ class BoostedImageFlow(nn.Module):
         self._trainers[c] = (key, trainer, bind)
         return trainer, bind
 
+    def _step_trainer(self, c):
+        """``native_trainer(c)`` for the fused step, which updates the bound tensors themselves: (trainer, bindings) with the live LU
+        factors and ``learn_top_fn`` bound on top (once per trainer object).  A 1x1 tensor or buffer that is not row-major in memory
+        (the constructor's QR / LU factors are column-major) gets contiguous storage first.  Only ``.data`` is re-set: the Parameter
+        object, and so any torch optimiser holding it, is unchanged, and the library binds the module's own storage, never a copy."""
+        flow = self.flows[c]
+        for layer in flow.flow.layers:
+            inv = getattr(layer, "invconv", None)
+            for p in ([] if inv is None else ([inv.lower, inv.upper, inv.log_s, inv.p, inv.sign_s] if inv.LU_decomposed else [inv.weight])):
+                if not p.is_contiguous() or p.dtype != torch.float32:
+                    p.data = p.data.float().contiguous()
+        trainer, bind = self.native_trainer(c)
+        if not getattr(trainer, "step_bound", False):
+            with torch.cuda.device(trainer.device):
+                for path, obj, _ in bind:
+                    if isinstance(obj, InvertibleConv1x1) and obj.LU_decomposed:
+                        trainer.bind_lu(path[1], path[3], obj.p.detach(), obj.sign_s.detach(), obj.lower.detach(), obj.upper.detach(),
+                                        obj.log_s.detach())
+                if flow.learn_top:
+                    top = flow.learn_top_fn
+                    trainer.bind_top(top.conv.weight.detach(), top.conv.bias.detach(), top.logs.detach())
+            trainer.step_bound = True
+        return trainer, bind
+
+    def _step_names(self, c, bind=None):
+        """{path in the trainer's step layout: parameter name within flows[c]} of every tensor the fused step updates."""
+        flow = self.flows[c]
+        if bind is None:
+            _, bind = self._step_trainer(c)
+        ids = {id(p): name for name, p in flow.named_parameters()}
+        names = {}
+        for path, obj, _ in bind:
+            if not isinstance(obj, InvertibleConv1x1):
+                names[path] = ids[id(obj)]
+            elif obj.LU_decomposed:
+                for key in ("lower", "upper", "log_s"):
+                    names[path[:-1] + (key,)] = ids[id(getattr(obj, key))]
+            else:
+                names[path] = ids[id(obj.weight)]
+        if flow.learn_top:
+            top = flow.learn_top_fn
+            names.update({("learn_top", "w"): ids[id(top.conv.weight)], ("learn_top", "b"): ids[id(top.conv.bias)],
+                          ("learn_top", "logs"): ids[id(top.logs)]})
+        return names
+
+    def step_parameters(self, c):
+        """The component's ``nn.Parameter`` objects in the order of the trainer's step layout (None for a reserved region): the
+        ``params`` argument of ``native.OptState.load_from`` / ``store_to`` against a ``torch.optim`` optimiser on them."""
+        trainer, bind = self._step_trainer(int(c))
+        names, by_name = self._step_names(int(c), bind), dict(self.flows[int(c)].named_parameters())
+        return [None if t is None else by_name[names[path]] for (path, _, _), t in zip(trainer._step_regions, trainer.params)]
+
+    def opt_state(self, c, optimizer="adamw", trainer=None):
+        """The ``native.OptState`` ``training_step`` keeps for component c (created on first use; another ``optimizer`` kind or a
+        re-bound component starts a new one)."""
+        if trainer is None:
+            trainer, _ = self._step_trainer(int(c))
+        states = self.__dict__.setdefault("_opt_states", {})
+        st = states.get(int(c))
+        if st is None or st.kind != optimizer or st.grad_floats != trainer.step_grad_floats or st.exp_avg_device != trainer.device:
+            st = states[int(c)] = native.OptState(trainer, optimizer)
+        return st
+
+    def training_step(self, x, *, lr, weight_decay=0.0, max_grad_norm=0.0, optimizer="adamw", betas=(0.9, 0.999), eps=1e-8,
+                      noise=None, bits_per_dim=True, want_grads=False):
+        """The body of one iteration of the reference's image training loop (image_experiment.py:378-419) for ``self.component`` in one
+        library call (gbnf_image_trainer_nll_step): the loss ``mean(-(log_normal_diag(z, z_mu, z_var) + logdet))`` -- divided by
+        ``ln 2 * C*H*W`` with ``bits_per_dim`` (:227-229) --, ``loss.backward()``, ``clip_grad_norm_`` (``max_grad_norm`` > 0) and the
+        step of ``optim.AdamW`` / ``optim.SGD`` ("adamw" | "sgd") on the component's parameters, in place: the LU factors of the 1x1
+        convolutions and ``learn_top_fn`` included.  ``lr`` is per call (schedulers stay with the caller).  The boosted image loss
+        (:247-261) has the same gradient; its ``G_nll`` term is ``component_forward`` in ``eval()``.  ``noise``: the U(0,1) dequantisation
+        noise (drawn when None).  Returns 0-dim DEVICE tensors (nothing is read back): ``nll`` (nats), ``bpd``, ``grad_norm`` (of the
+        scaled loss: what the reference clips), ``clip_coef``; with ``want_grads`` also ``grads``: {parameter name within
+        ``flows[c]``: view of the unclipped gradient}.  The optimiser state is kept per component (``self.opt_state(c)``).  No
+        ``p.grad`` is written."""
+        self._check(x)
+        if x.requires_grad:
+            raise NotImplementedError("the image training path has no gradient with respect to x")
+        c = int(self.component)
+        flow = self.flows[c]
+        x = x.contiguous().float()
+        noise = torch.rand_like(x) if noise is None else noise.contiguous().float()
+        with torch.cuda.device(x.device):
+            trainer, bind = self._step_trainer(c)
+            state = self.opt_state(c, optimizer, trainer)
+            per_dim = 1.0 / (float(np.log(2.0)) * float(np.prod(flow.input_size)))
+            stats, flat = trainer.nll_step(x, noise, state, loss_scale=per_dim if bits_per_dim else 1.0, lr=lr, weight_decay=weight_decay,
+                                           max_grad_norm=max_grad_norm, betas=betas, eps=eps)
+        # the kernels wrote the parameters behind autograd's back: move their version counters (host only, no launch) so that the
+        # packed evaluation copy keyed on them (native_flow) is rebuilt
+        torch.autograd.graph.increment_version(self._component_tensors(c)[0])
+        out = {"nll": stats[0], "bpd": stats[0] * per_dim, "grad_norm": stats[1], "clip_coef": stats[2]}
+        if want_grads:
+            views = trainer.step_views(flat)
+            out["grads"] = {name: views[path] for path, name in self._step_names(c, bind).items()}
+        return out
+
     def _component_forward_train(self, x, c, noise):
         """Differentiable (z, z_mu, z_var, ldj, None) of component c on its live parameters (models/glow.py:92-110)."""
         if x.requires_grad:

@@ -46,6 +46,8 @@ ABI_SYMBOLS = (
     "gbnf_flow_numerics_inverse", "gbnf_image_flow_inverse_check_counts",
     "gbnf_image_trainer_create", "gbnf_image_trainer_destroy", "gbnf_image_trainer_trace_floats", "gbnf_image_trainer_workspace_bytes",
     "gbnf_image_trainer_forward", "gbnf_image_trainer_grad_floats", "gbnf_image_trainer_backward",
+    "gbnf_image_trainer_bind_lu", "gbnf_image_trainer_bind_top", "gbnf_image_trainer_step_grad_floats",
+    "gbnf_image_trainer_step_workspace_bytes", "gbnf_image_trainer_apply_update", "gbnf_image_trainer_nll_step",
 )
 
 
@@ -225,6 +227,12 @@ def lib():
     L.gbnf_image_trainer_forward.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.gbnf_image_trainer_grad_floats.argtypes = [vp, C.POINTER(i64)]
     L.gbnf_image_trainer_backward.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp]
+    L.gbnf_image_trainer_bind_lu.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
+    L.gbnf_image_trainer_bind_top.argtypes = [vp, vp, vp, vp]
+    L.gbnf_image_trainer_step_grad_floats.argtypes = [vp, C.POINTER(i64)]
+    L.gbnf_image_trainer_step_workspace_bytes.argtypes = [vp, i64, C.POINTER(i64)]
+    L.gbnf_image_trainer_apply_update.argtypes = [vp, vp, vp, vp, C.POINTER(_OptHyper), vp, vp]
+    L.gbnf_image_trainer_nll_step.argtypes = [vp, vp, vp, i64, C.c_float, vp, vp, vp, C.POINTER(_OptHyper), vp, vp, i64, vp]
     L.gbnf_image_flow_inverse.argtypes = [vp, vp, vp, C.c_float, i64, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
@@ -614,6 +622,9 @@ class NativeImageTrainer:
     def __init__(self, dev_spec):
         self._tensors = []
         self._regions = []          # (path, offset, shape) in the order of the flat gradient buffer
+        self._region_tensors = []   # the bound tensor of each
+        self._lu = {}               # (level, step) -> the LU factors bound there (bind_lu), in bind order
+        self._top = None            # (weight | None, bias, logs) of learn_top_fn (bind_top)
         self._off = 0
         fp = C.POINTER(C.c_float)
         keep = _Keep()
@@ -625,6 +636,7 @@ class NativeImageTrainer:
 
         def region(path, t):
             self._regions.append((path, self._off, tuple(t.shape)))
+            self._region_tensors.append(t)
             self._off += t.numel()
 
         def conv(c, path):
@@ -694,9 +706,129 @@ class NativeImageTrainer:
             raise GbnfError("gradient-buffer layout mismatch between the library and the binding")
         self.device = self._tensors[0].device
         self._ws = None
+        self._step_ws = None
+        self._layout_step()
 
     def key(self):
         return tuple(t.data_ptr() for t in self._tensors)
+
+    # ---- the one-call training step (gbnf_image_trainer_nll_step / _apply_update)
+    def _layout_step(self):
+        """The STEP layout (include/gbnf.h): the regions of ``backward`` -- the composed matrix of an LU step reserved --, then per bound
+        LU step lower / upper / log_s, then the top prior.  ``params`` / ``_sizes``: tensor | None and size per region, what
+        ``OptState`` walks."""
+        regions, tensors = [], []
+        for (path, off, shape), t in zip(self._regions, self._region_tensors):
+            reserved = path[-1] == "perm_w" and (path[1], path[3]) in self._lu
+            regions.append((path, off, shape))
+            tensors.append(None if reserved else t)
+        off = self._off
+        for (l, k), (lower, upper, log_s) in self._lu.items():
+            for name, t in (("lower", lower), ("upper", upper), ("log_s", log_s)):
+                regions.append((("levels", l, "steps", k, name), off, tuple(t.shape)))
+                tensors.append(t)
+                off += t.numel()
+        if self._top is not None:
+            for name, t in zip(("w", "b", "logs"), self._top):
+                if t is not None:
+                    regions.append((("learn_top", name), off, tuple(t.shape)))
+                    tensors.append(t)
+                    off += t.numel()
+        nf = C.c_int64()
+        _check(lib().gbnf_image_trainer_step_grad_floats(self.handle, C.byref(nf)))
+        if nf.value != off:
+            raise GbnfError("step gradient-buffer layout mismatch between the library and the binding")
+        self.step_grad_floats = int(nf.value)
+        self._step_regions = regions
+        self.params = tensors
+        self._sizes = [int(np.prod(shape)) for _, _, shape in regions]
+
+    def bind_lu(self, level, step, p, sign_s, lower, upper, log_s):
+        """The live LU factors of one 1x1 step (gbnf_image_trainer_bind_lu; contiguous float32 device tensors): ``nll_step`` composes
+        the step's bound ``perm_w`` from them and returns their gradients; the ``perm_w`` region of the step layout becomes reserved."""
+        c = self._region_shape(("levels", int(level), "steps", int(step), "perm_w"))
+        for name, t, shape in (("p", p, c), ("sign_s", sign_s, c and c[:1]), ("lower", lower, c), ("upper", upper, c), ("log_s", log_s, c and c[:1])):
+            _require_device_f32(t, name)
+            if c is not None and tuple(t.shape) != shape:
+                raise GbnfError(f"bind_lu: {name} has shape {tuple(t.shape)}, expected {shape}")
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        _check(lib().gbnf_image_trainer_bind_lu(self.handle, int(level), int(step), ptr(p), ptr(sign_s), ptr(lower), ptr(upper), ptr(log_s)))
+        self._tensors += [p, sign_s, lower, upper, log_s]
+        self._lu[(int(level), int(step))] = (lower, upper, log_s)
+        self._layout_step()
+
+    def _region_shape(self, path):
+        return next((shape for q, _, shape in self._regions if q == path), None)
+
+    def bind_top(self, weight, bias, logs):
+        """learn_top_fn's conv weight (or None), conv bias and logs (gbnf_image_trainer_bind_top): the learned top prior of ``nll_step``."""
+        cz2 = 2 * self.z_shape[0]
+        for name, t, numel in (("weight", weight, cz2 * cz2 * 9), ("bias", bias, cz2), ("logs", logs, cz2)):
+            if t is None and name == "weight":
+                continue
+            _require_device_f32(t, name)
+            if t.numel() != numel:
+                raise GbnfError(f"bind_top: {name} has {t.numel()} elements, expected {numel}")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_image_trainer_bind_top(self.handle, ptr(weight), ptr(bias), ptr(logs)))
+        self._tensors += [t for t in (weight, bias, logs) if t is not None]
+        self._top = (weight, bias, logs)
+        self._layout_step()
+
+    def step_views(self, flat):
+        """{path: view} of a flat buffer in the STEP layout: the paths of ``backward`` plus (..., "lower" | "upper" | "log_s") of the
+        bound LU steps and ("learn_top", "w" | "b" | "logs")."""
+        if flat.numel() != self.step_grad_floats:
+            raise GbnfError(f"flat has {flat.numel()} elements, expected {self.step_grad_floats}")
+        return {path: flat[off: off + int(np.prod(shape))].view(shape) for path, off, shape in self._step_regions}
+
+    _hyper = None      # (set below the class: NativeTrainer._hyper, the same gbnf_opt_hyper)
+
+    def apply_update(self, flat_grads, state, **hyper):
+        """clip_grad_norm_ + one optimiser step on the bound tensors, in place, from a flat gradient buffer in the STEP layout
+        (gbnf_image_trainer_apply_update).  ``state``: an ``OptState`` of this trainer, advanced by one step.  ``hyper``: lr,
+        weight_decay, max_grad_norm, betas, eps.  -> stats (4,) device tensor: [1] gradient norm, [2] clip coefficient."""
+        import torch
+        _require_device_f32(flat_grads, "flat_grads")
+        if flat_grads.numel() != self.step_grad_floats:
+            raise GbnfError(f"flat_grads has {flat_grads.numel()} elements, expected {self.step_grad_floats}")
+        state.check(self)
+        h = self._hyper(state, **hyper)
+        stats = torch.zeros(4, dtype=torch.float32, device=flat_grads.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_image_trainer_apply_update(self.handle, ptr(flat_grads), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h),
+                                                     ptr(stats), _stream_ptr()))
+        state.step += 1
+        return stats
+
+    def nll_step(self, x, noise, state, loss_scale=1.0, **hyper):
+        """One whole training step of this component on the device (gbnf_image_trainer_nll_step): 1x1 log-dets (LU matrices composed) ->
+        forward on the live parameters -> loss_scale * mean nll and its seed -> backward -> log-det / LU / top-prior gradients -> clip ->
+        optimiser update, no host read in between.  -> (stats (4,) device tensor: mean nll in nats (unscaled), norm of the scaled
+        gradient, clip coefficient, 0; the flat unclipped scaled gradient in the STEP layout)."""
+        import torch
+        _require_device_f32(x, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
+            raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        n = x.shape[0]
+        state.check(self)
+        h = self._hyper(state, **hyper)
+        nb = C.c_int64()
+        _check(lib().gbnf_image_trainer_step_workspace_bytes(self.handle, n, C.byref(nb)))
+        if self._step_ws is None or self._step_ws.numel() * 4 < nb.value or self._step_ws.device != x.device:
+            self._step_ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        flat = torch.empty(self.step_grad_floats, dtype=torch.float32, device=x.device)
+        stats = torch.zeros(4, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_image_trainer_nll_step(self.handle, ptr(x), ptr(noise), n, float(loss_scale), ptr(flat), ptr(state.exp_avg),
+                                                 ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(self._step_ws),
+                                                 self._step_ws.numel() * 4, _stream_ptr()))
+        state.step += 1
+        return stats, flat
 
     def _workspace(self, n):
         import torch
@@ -1044,8 +1176,12 @@ class NativeTrainer:
             pass
 
 
+NativeImageTrainer._hyper = NativeTrainer._hyper
+
+
 class OptState:
-    """Caller-owned optimiser state of one trainer's parameters for ``NativeTrainer.apply_update`` / ``nll_step``: ``exp_avg`` and
+    """Caller-owned optimiser state of one trainer's parameters for ``NativeTrainer.apply_update`` / ``nll_step`` (or those of a
+    ``NativeImageTrainer``, whose step layout sizes it: create it after ``bind_lu`` / ``bind_top``): ``exp_avg`` and
     ``exp_avg_sq`` as flat device tensors in the layout of the flat gradient buffer (None for SGD), ``step`` = updates taken so far,
     ``kind`` = "adamw" | "sgd".  It maps one to one onto the state of a ``torch.optim.AdamW`` (``load_from`` / ``store_to``)."""
 
@@ -1055,7 +1191,7 @@ class OptState:
             raise GbnfError(f"OptState: kind must be one of {sorted(OPT_KIND)}, got {kind!r}")
         self.kind = kind
         self.step = 0
-        self.grad_floats = trainer.grad_floats
+        self.grad_floats = self._floats_of(trainer)
         self._shapes = [(None if t is None else tuple(t.shape), size) for t, size in zip(trainer.params, trainer._sizes)]
         self.exp_avg_device = device = trainer.device if device is None else device
         self.exp_avg = self.exp_avg_sq = None
@@ -1063,8 +1199,13 @@ class OptState:
             self.exp_avg = torch.zeros(self.grad_floats, dtype=torch.float32, device=device)
             self.exp_avg_sq = torch.zeros(self.grad_floats, dtype=torch.float32, device=device)
 
+    @staticmethod
+    def _floats_of(trainer):
+        """Floats of the buffer the trainer's update walks: an image trainer's STEP layout, a tabular trainer's gradient buffer."""
+        return getattr(trainer, "step_grad_floats", None) or trainer.grad_floats
+
     def check(self, trainer):
-        if self.grad_floats != trainer.grad_floats:
+        if self.grad_floats != self._floats_of(trainer):
             raise GbnfError("OptState belongs to a trainer of another geometry")
 
     def _views(self, flat):

@@ -722,6 +722,52 @@ int gbnf_image_trainer_grad_floats(const gbnf_image_trainer* trainer, int64_t* f
 int gbnf_image_trainer_backward(gbnf_image_trainer* trainer, const float* trace, int64_t n, const float* g_z,
                                 const float* g_ldj, float* grads, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- one image training step in one call: loss, 1x1 log-determinants, clip, AdamW / SGD -----------------------------------
+ * Replaces: one iteration of image_experiment.py:378-419 for the component being trained -- the loss (:227-229)
+ *   nll_i = -(log_normal_diag(z, z_mu, z_var) + logdet),  loss = loss_scale * mean_i(nll_i)   (the reference: 1 / (ln 2 C H W)),
+ * loss.backward(), clip_grad_norm_ and optimizer.step() (optimization/optimizers.py:54-65) -- on the trainer's live tensors, with no
+ * host read and no synchronisation.  The boosted image loss (:247-261) differs from this one by a term that does not depend on the
+ * trained component: its gradient is this one, and there is no resampling on the image path.
+ *
+ * The calls below add what gbnf_image_trainer_forward / _backward leave to the caller:
+ *   - the log-determinants of the 1 x 1 matrices, sum over the steps of hw * log|det W| (hw: pixels of the step's level), and their
+ *     gradient -loss_scale * hw * W^-T (Gauss-Jordan with partial pivoting in f64; a singular W gives a non-finite nll, as torch);
+ *   - the LU form of a 1 x 1 (models/layers.py:757-768): W = p (lower . m + I)(upper . m^T + diag(sign_s e^log_s)), m the strict lower
+ *     triangle.  gbnf_image_trainer_bind_lu names the live factors of one step (DEVICE pointers; p and sign_s are buffers); the step's
+ *     perm_weight of the descriptor is then the persistent (C, C) tensor the matrix is composed into before each forward of nll_step
+ *     (gbnf_image_trainer_forward itself does not compose).  GBNF_ERR_INVALID: a step outside the component or without perm_weight.
+ *   - the learned top prior (gbnf_image_trainer_bind_top: learn_top_fn's weight (may be NULL), bias and logs, 2 Cz channels):
+ *     h = bias * exp(3 logs), z_mu = h[:Cz], z_var = h[Cz:].  The weight gets a zero gradient but is a region of the update (weight
+ *     decay acts on it, as in torch).  Never bound: the zero-mean unit-variance prior.
+ * Both bind calls rebuild the trainer's tables (they allocate and synchronise; nll_step does neither).
+ *
+ * STEP gradient layout (gbnf_image_trainer_step_grad_floats): the gbnf_image_trainer_grad_floats layout unchanged, followed by, per
+ * bound LU step in bind order, [lower C*C] [upper C*C] [log_s C], then [top weight] [top bias 2Cz] [top logs 2Cz] when bound.  The
+ * perm_weight region of an LU step is reserved: zero behind a step, no tensor behind it, skipped by the update.  The optimiser state
+ * (exp_avg / exp_avg_sq) has this layout too. */
+int gbnf_image_trainer_bind_lu(gbnf_image_trainer* trainer, int32_t level, int32_t step, const float* p, const float* sign_s,
+                               float* lower, float* upper, float* log_s);
+int gbnf_image_trainer_bind_top(gbnf_image_trainer* trainer, float* weight_or_null, float* bias, float* logs);
+int gbnf_image_trainer_step_grad_floats(const gbnf_image_trainer* trainer, int64_t* floats);
+/* Bytes of caller-owned DEVICE scratch of one gbnf_image_trainer_nll_step over n images: z, ldj, the trace, g_z, g_ldj, the
+ * forward / backward workspace and the reductions' partial sums. */
+int gbnf_image_trainer_step_workspace_bytes(const gbnf_image_trainer* trainer, int64_t n, int64_t* bytes);
+/* gbnf_trainer_apply_update for an image trainer: clip_grad_norm_ + the optimiser step from a flat gradient buffer in the STEP
+ * layout, same kernels, same stats_dev.  Bit-identical from run to run for the same buffer. */
+int gbnf_image_trainer_apply_update(gbnf_image_trainer* trainer, const float* grads, float* exp_avg, float* exp_avg_sq,
+                                    const gbnf_opt_hyper* hyper, float* stats_dev, void* stream);
+/* The whole step:  1. compose the LU matrices and take every bound 1 x 1's log-det;  2. gbnf_image_trainer_forward (x, noise as
+ * there), trace in `workspace`;  3. + 4. the loss with the log-dets added and its seed g_z = k (z - mu) e^-lv / n, g_ldj = -k / n,
+ * k = loss_scale;  5. `grads` (STEP layout) is zeroed;  6. gbnf_image_trainer_backward;  7. the log-det, LU and prior gradients are
+ * added;  8. gbnf_image_trainer_apply_update.
+ * stats_dev (4 floats): [0] mean nll in nats, UNSCALED; [1] the 2-norm of the SCALED gradient (what the reference clips); [2] the clip
+ * coefficient; [3] 0.  `grads` holds the unclipped scaled gradient afterwards.  hyper.bn_momentum is ignored.
+ * GBNF_ERR_INVALID (nothing launched): the cases of gbnf_trainer_apply_update, n < 1 (or more than 65535 images), a workspace
+ * smaller than gbnf_image_trainer_step_workspace_bytes(n), a null x / grads / stats_dev / workspace. */
+int gbnf_image_trainer_nll_step(gbnf_image_trainer* trainer, const float* x, const float* noise, int64_t n, float loss_scale,
+                                float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper,
+                                float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
