@@ -183,6 +183,11 @@ def main(argv=None):
     objs.append(boost_o)
     if args.force or not newer(boost_o, [boost_src, opt_hdr, hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", boost_src, "-o", boost_o])
+    # boosting for image components (one update_rho iteration, the boosted step with its fixed-mixture term): gbnf_image_boost.hip
+    iboost_o, iboost_src = os.path.join(OBJ, "gbnf_image_boost.o"), os.path.join(HERE, "gbnf_image_boost.hip")
+    objs.append(iboost_o)
+    if args.force or not newer(iboost_o, [iboost_src, opt_hdr, os.path.join(HERE, "gbnf_image_train.h"), hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", iboost_src, "-o", iboost_o])
     for v in read_variants():
         o = os.path.join(OBJ, "v_" + "_".join(str(a) for a in v) + ".o")
         objs.append(o)

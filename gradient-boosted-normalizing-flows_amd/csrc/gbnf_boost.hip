@@ -7,6 +7,7 @@
 //   rho_partial_kernel       per-workgroup sums of fixed_ll - new_ll, fixed_ll by the un-normalised recursion of
 //                            models/boosted_flow.py:119-139
 //   rho_finalize_kernel      the gradient, the step and the clamp of update_rho                           (models/boosted_flow.py:141-207)
+//   rho_update_launch        those two launches on a (component + 1, n) table: shared with the image call (gbnf_image_boost.hip)
 //
 // Launch-latency sized like boosting_weights_kernel (gbnf_api.hip): no matrix pipe, no LDS staging.  Every reduction runs in f64 in an
 // order that depends on the sizes alone -- no atomics --, so the cdf, the rows and the statistics are bit-identical from run to run.
@@ -181,10 +182,37 @@ __global__ void __launch_bounds__(RHO_THREADS) rho_finalize_kernel(const double*
   stats[3] = fabsf(after - before);
 }
 
-// per device: the partial sums between the two kernels of gbnf_mixture_rho_step (the call has no workspace argument for them);
-// allocated on first use, never freed
+// per device: the partial sums between the two kernels of a rho update (neither gbnf_mixture_rho_step nor its image counterpart has
+// a workspace argument for them); allocated on first use, never freed
 static double* g_rho_partials[MAX_DEVICES] = {};
 static std::mutex g_rho_mu;
+
+// The tail of one update_rho iteration, shared by gbnf_mixture_rho_step and gbnf_image_mixture_rho_step (gbnf_image_boost.hip): the two
+// launches above on a (component + 1, n) log-likelihood table, through the current device's partial-sum buffer.
+int rho_update_launch(const char* fn, const float* ll, int64_t n, int component, float* rho_dev, float step_size, float* stats_dev,
+                      hipStream_t s) {
+  double* partial = nullptr;
+  {
+    int dev = 0;
+    hipError_t e = hipGetDevice(&dev);
+    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: hipGetDevice: %s", fn, hipGetErrorString(e));
+    if (dev < 0 || dev >= MAX_DEVICES) return fail(GBNF_ERR_UNSUPPORTED, "%s: device index %d", fn, dev);
+    std::lock_guard<std::mutex> lk(g_rho_mu);
+    if (!g_rho_partials[dev]) {
+      e = hipMalloc((void**)&g_rho_partials[dev], sizeof(double) * RHO_MAX_PARTIALS);
+      if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: hipMalloc: %s", fn, hipGetErrorString(e));
+    }
+    partial = g_rho_partials[dev];
+  }
+  int64_t nb = (n + 4 * RHO_THREADS - 1) / (4 * RHO_THREADS);
+  if (nb > RHO_MAX_PARTIALS) nb = RHO_MAX_PARTIALS;
+  hipLaunchKernelGGL(rho_partial_kernel, dim3((unsigned)nb), dim3(RHO_THREADS), 0, s, ll, n, component, (const float*)rho_dev, partial);
+  hipLaunchKernelGGL(rho_finalize_kernel, dim3(1), dim3(RHO_THREADS), 0, s, (const double*)partial, (int)nb, n, component, rho_dev,
+                     step_size, stats_dev);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s launch: %s", fn, hipGetErrorString(e));
+  return GBNF_OK;
+}
 
 static int launch_resample(const float* w, int64_t n, const float* u, int64_t m, int64_t* rows, int64_t* rows_copy, double* cdf,
                            const float* G, float* stats, hipStream_t s, const char* fn) {
@@ -295,30 +323,8 @@ int gbnf_mixture_rho_step(const gbnf_mixture* mix, const float* x, int64_t n, in
   int C = 0, d = 0;
   if (const int rc = mixture_shape(mix, &C, &d)) return rc;
   if (component < 1 || component >= C) return fail(GBNF_ERR_INVALID, "%s: component = %d outside [1,%d)", fn, component, C);
-  double* partial = nullptr;
-  {
-    int dev = 0;
-    hipError_t e = hipGetDevice(&dev);
-    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: hipGetDevice: %s", fn, hipGetErrorString(e));
-    if (dev < 0 || dev >= MAX_DEVICES) return fail(GBNF_ERR_UNSUPPORTED, "%s: device index %d", fn, dev);
-    std::lock_guard<std::mutex> lk(g_rho_mu);
-    if (!g_rho_partials[dev]) {
-      e = hipMalloc((void**)&g_rho_partials[dev], sizeof(double) * RHO_MAX_PARTIALS);
-      if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: hipMalloc: %s", fn, hipGetErrorString(e));
-    }
-    partial = g_rho_partials[dev];
-  }
   if (const int rc = gbnf_mixture_component_log_prob(mix, x, n, 0, component + 1, ll_workspace, stream)) return rc;
-  int64_t nb = (n + 4 * RHO_THREADS - 1) / (4 * RHO_THREADS);
-  if (nb > RHO_MAX_PARTIALS) nb = RHO_MAX_PARTIALS;
-  hipStream_t s = (hipStream_t)stream;
-  hipLaunchKernelGGL(rho_partial_kernel, dim3((unsigned)nb), dim3(RHO_THREADS), 0, s, (const float*)ll_workspace, n, (int)component,
-                     (const float*)rho_dev, partial);
-  hipLaunchKernelGGL(rho_finalize_kernel, dim3(1), dim3(RHO_THREADS), 0, s, (const double*)partial, (int)nb, n, (int)component, rho_dev,
-                     step_size, stats_dev);
-  const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s launch: %s", fn, hipGetErrorString(e));
-  return GBNF_OK;
+  return rho_update_launch(fn, ll_workspace, n, (int)component, rho_dev, step_size, stats_dev, (hipStream_t)stream);
 }
 
 }  // extern "C"

@@ -1102,6 +1102,12 @@ hipError_t allow_lds() {
 
 }  // namespace
 
+int gbnf::image_flow_input_shape(const gbnf_image_flow* f, int* channels, int* height, int* width) {
+  if (!f || !channels || !height || !width) return fail(GBNF_ERR_INVALID, "image_flow_input_shape: null argument");
+  *channels = f->C; *height = f->Hi; *width = f->Wi;
+  return GBNF_OK;
+}
+
 extern "C" {
 
 #ifdef GBNF_IMG_STAMPS

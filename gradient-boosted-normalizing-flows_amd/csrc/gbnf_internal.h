@@ -23,6 +23,14 @@ unsigned* training_saturation_counter();
 // How many components a mixture holds and their feature count, for the translation units that do not see the handle (gbnf_boost.hip)
 int mixture_shape(const gbnf_mixture* mix, int* n_components, int* d);
 
+// The tail of one update_rho iteration (gbnf_boost.hip: rho_partial_kernel + rho_finalize_kernel through the current device's
+// partial-sum buffer) on a (component + 1, n) DEVICE table of per-component log-likelihoods: what gbnf_mixture_rho_step and
+// gbnf_image_mixture_rho_step (gbnf_image_boost.hip) share.  Writes rho_dev[component] and the 4 floats of stats_dev; no host read.
+int rho_update_launch(const char* fn, const float* ll, int64_t n, int component, float* rho_dev, float step_size, float* stats_dev,
+                      hipStream_t s);
+// The input proper of an image evaluation handle (channels, height, width), for gbnf_image_boost.hip (gbnf_image.hip)
+int image_flow_input_shape(const gbnf_image_flow* f, int* channels, int* height, int* width);
+
 // Kernel-variant key only (not a descriptor value): the activation differs between the steps / nets of a component
 // (`--coupling_network random` in the reference); the kernel reads it per step and net from the step header.
 constexpr int GBNF_ACT_PER_STEP = 3;

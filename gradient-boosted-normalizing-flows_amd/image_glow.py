@@ -542,34 +542,58 @@ class BoostedImageFlow(nn.Module):
         return st
 
     def training_step(self, x, *, lr, weight_decay=0.0, max_grad_norm=0.0, optimizer="adamw", betas=(0.9, 0.999), eps=1e-8,
-                      noise=None, bits_per_dim=True, want_grads=False):
+                      noise=None, bits_per_dim=True, want_grads=False, fixed=None, g_floor=-10.0):
         """The body of one iteration of the reference's image training loop (image_experiment.py:378-419) for ``self.component`` in one
         library call (gbnf_image_trainer_nll_step): the loss ``mean(-(log_normal_diag(z, z_mu, z_var) + logdet))`` -- divided by
         ``ln 2 * C*H*W`` with ``bits_per_dim`` (:227-229) --, ``loss.backward()``, ``clip_grad_norm_`` (``max_grad_norm`` > 0) and the
         step of ``optim.AdamW`` / ``optim.SGD`` ("adamw" | "sgd") on the component's parameters, in place: the LU factors of the 1x1
-        convolutions and ``learn_top_fn`` included.  ``lr`` is per call (schedulers stay with the caller).  The boosted image loss
-        (:247-261) has the same gradient; its ``G_nll`` term is ``component_forward`` in ``eval()``.  ``noise``: the U(0,1) dequantisation
-        noise (drawn when None).  Returns 0-dim DEVICE tensors (nothing is read back): ``nll`` (nats), ``bpd``, ``grad_norm`` (of the
-        scaled loss: what the reference clips), ``clip_coef``; with ``want_grads`` also ``grads``: {parameter name within
-        ``flows[c]``: view of the unclipped gradient}.  The optimiser state is kept per component (``self.opt_state(c)``).  No
-        ``p.grad`` is written."""
+        convolutions and ``learn_top_fn`` included.  ``lr`` is per call (schedulers stay with the caller).  ``noise``: the U(0,1)
+        dequantisation noise (drawn when None).  Returns 0-dim DEVICE tensors (nothing is read back): ``nll`` (nats), ``bpd``,
+        ``grad_norm`` (of the scaled loss: what the reference clips), ``clip_coef``; with ``want_grads`` also ``grads``: {parameter name
+        within ``flows[c]``: view of the unclipped gradient}.  The optimiser state is kept per component (``self.opt_state(c)``).  No
+        ``p.grad`` is written.
+
+        ``fixed``: the fixed-mixture term of the boosted image loss (:247-261, :398-402).  It has no gradient with respect to the trained
+        component, so the update is the same with and without it; with it the step is gbnf_image_boosted_nll_step, which also evaluates
+        the fixed component on the same ``(x, noise)`` and returns, besides the keys above, ``G_nll`` = mean(-max(ll_G, ``g_floor``))
+        (the reference's G_MAX_LOSS is -10), ``boosted_nll`` = nll - G_nll (what the reference reports and feeds its plateau scheduler)
+        and ``boosted_bpd`` as 0-dim device tensors, and ``fixed_component`` (int).  ``fixed=None`` (default): no such term, today's
+        return.  ``fixed="sample"``: the reference's draw, ``_sample_component('-c' if all_trained else '1:c-1')`` (a host read of
+        ``rho`` with more than one candidate); for the FIRST component this is the trained component itself, as in the reference, whose
+        evaluation handle is then re-packed every step because its parameters move: ``fixed=None`` is recommended there.  ``fixed=int``:
+        that component."""
         self._check(x)
         if x.requires_grad:
             raise NotImplementedError("the image training path has no gradient with respect to x")
         c = int(self.component)
         flow = self.flows[c]
+        fc = None
+        if isinstance(fixed, str):
+            if fixed != "sample":
+                raise ValueError(f"fixed must be None, 'sample' or a component index, got {fixed!r}")
+            fc = self._sample_component("-c" if self.all_trained else "1:c-1")
+        elif fixed is not None:
+            fc = int(fixed)
+            if isinstance(fixed, bool) or not 0 <= fc < self.num_components:
+                raise ValueError(f"fixed={fixed!r} is no component of this model (0 .. {self.num_components - 1})")
         x = x.contiguous().float()
         noise = torch.rand_like(x) if noise is None else noise.contiguous().float()
         with torch.cuda.device(x.device):
             trainer, bind = self._step_trainer(c)
             state = self.opt_state(c, optimizer, trainer)
             per_dim = 1.0 / (float(np.log(2.0)) * float(np.prod(flow.input_size)))
-            stats, flat = trainer.nll_step(x, noise, state, loss_scale=per_dim if bits_per_dim else 1.0, lr=lr, weight_decay=weight_decay,
-                                           max_grad_norm=max_grad_norm, betas=betas, eps=eps)
+            hyper = dict(loss_scale=per_dim if bits_per_dim else 1.0, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
+                         betas=betas, eps=eps)
+            if fixed is None:
+                stats, flat = trainer.nll_step(x, noise, state, **hyper)
+            else:
+                stats, flat = trainer.boosted_nll_step(self.native_flow(fc), x, noise, state, g_floor=g_floor, **hyper)
         # the kernels wrote the parameters behind autograd's back: move their version counters (host only, no launch) so that the
         # packed evaluation copy keyed on them (native_flow) is rebuilt
         torch.autograd.graph.increment_version(self._component_tensors(c)[0])
         out = {"nll": stats[0], "bpd": stats[0] * per_dim, "grad_norm": stats[1], "clip_coef": stats[2]}
+        if fc is not None:
+            out.update({"G_nll": stats[4], "boosted_nll": stats[5], "boosted_bpd": stats[5] * per_dim, "fixed_component": fc})
         if want_grads:
             views = trainer.step_views(flat)
             out["grads"] = {name: views[path] for path, name in self._step_names(c, bind).items()}
@@ -808,3 +832,102 @@ class BoostedImageFlow(nn.Module):
         ll = self.component_log_prob(x, n_used, noise)
         with torch.cuda.device(x.device):
             return native.mixture_lse(ll.t().contiguous(), self.rho)
+
+    # ---- the mixture weights (models/boosted_flow.py:119-207)
+    @torch.no_grad()
+    def _rho_gradients(self, x, noise=None):
+        """models/boosted_flow.py:119-139 -> (new_ll, fixed_ll, full_ll) device tensors, with the image path's own log-likelihood
+        (``component_log_prob``: log_normal_diag(z, z_mu, z_var) + logdet; the reference's log_normal_standard(z, dim=-1) raises on a
+        4-D z) and the reference's recursion: un-normalised rho, all three zeros where component 0 leaves them."""
+        self._check(x)
+        ll = self.component_log_prob(x, self.component + 1, noise)
+        full_ll = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
+        fixed_ll = torch.zeros_like(full_ll)
+        new_ll = torch.zeros_like(full_ll)
+        for c in range(self.component + 1):
+            if c == 0:
+                full_ll = ll[:, 0]
+            else:
+                new_ll = ll[:, c]
+                prev = torch.log(1 - self.rho[c]) + full_ll
+                nxt = torch.log(self.rho[c]) + new_ll
+                full_ll = torch.logsumexp(torch.stack([prev, nxt], dim=1), dim=1)
+            if c == self.component - 1:
+                fixed_ll = full_ll
+        return new_ll, fixed_ll, full_ll
+
+    @torch.no_grad()
+    def update_rho(self, data_loader, noise_generator=None):
+        """models/boosted_flow.py:141-207 (approximate branch) for image components.  The reference's log line references an undefined
+        ``g_nll``; the update rule is reproduced, the broken log message is not.  For ``component`` >= 1 every
+        iteration is ONE library call (gbnf_image_mixture_rho_step: the components' forwards, the recursion, the gradient and the
+        clamped update of ``self.rho`` on the device) with step size ``rho_lr / (0.05 batch_id + 1)``; nothing is read back up to
+        iteration ``min_iters`` = 10, where the reference cannot stop, and the call's 4 statistics per iteration after that.  The
+        loader yields ``(x, _)`` with x in [0, 1]; the dequantisation noise is one ``torch.rand(x.shape, generator=noise_generator)``
+        draw on the device per batch, the same for every component.  For ``component == 0 and all_trained`` the reference's
+        gradient is identically 0 (new_ll = fixed_ll = 0): rho[0] is clamped to [0.01, 100], without a library call."""
+        if self.component == 0 and not self.all_trained:
+            return
+        if getattr(self.args, "rho_iters", 0) == 0:
+            return
+        self.eval()
+        c = int(self.component)
+        rho = self.rho
+        if rho.dtype != torch.float32 or not rho.is_contiguous():
+            raise ValueError("update_rho writes self.rho in place: it must be contiguous float32")
+        if c == 0:
+            rho[0:1].clamp_(0.01, 100.0)
+            return
+        tolerance, min_iters = 0.001, 10
+        init_step, max_iters = self.args.rho_lr, self.args.rho_iters
+        data_iter = iter(data_loader)
+        for batch_id in range(max_iters):
+            try:
+                (x, _) = next(data_iter)
+            except StopIteration:
+                data_iter = iter(data_loader)
+                (x, _) = next(data_iter)
+            x = x.detach().to(rho.device).contiguous().float()
+            self._check(x)
+            noise = torch.rand(x.shape, generator=noise_generator, device=x.device)
+            with torch.cuda.device(x.device):
+                stats = native.NativeImageFlow.rho_step([self.native_flow(k) for k in range(c + 1)], x, noise, c, rho,
+                                                        init_step / (0.05 * batch_id + 1))
+            # the kernel wrote rho behind autograd's back: move its version counter as training_step does for parameters
+            torch.autograd.graph.increment_version([rho])
+            if batch_id > min_iters and (batch_id > max_iters or stats.tolist()[3] < tolerance):
+                break
+
+    # ---- checkpoint side-car (SURVEY.md S5 for image components)
+    def _side_car_modules(self, c):
+        flow = self.flows[c]
+        return [m for m in flow.modules() if isinstance(m, Permute2d)], flow._actnorms()
+
+    def permutation_state(self):
+        """What the reference's checkpoints lose, in the layout of ``BoostedFlow.permutation_state``: ``component``,
+        ``all_trained``, the ``Permute2d.indices`` of every step that has one and the ``inited`` flag of every ActNorm2d, keyed
+        "component.position" with the position in module order.  Save next to ``state_dict()`` (``checkpoint.save`` does)."""
+        st = {"component": self.component, "all_trained": self.all_trained, "indices": {}, "actnorm_inited": {}}
+        for c in range(len(self.flows)):
+            perms, actnorms = self._side_car_modules(c)
+            for k, m in enumerate(perms):
+                st["indices"][f"{c}.{k}"] = m.indices.detach().cpu().clone()
+            for k, m in enumerate(actnorms):
+                st["actnorm_inited"][f"{c}.{k}"] = bool(m.inited)
+        return st
+
+    def load_permutation_state(self, st):
+        self.component = int(st["component"])
+        self.all_trained = bool(st["all_trained"])
+        touched = set()
+        for name, idx in st["indices"].items():
+            c, k = (int(v) for v in name.split("."))
+            self._side_car_modules(c)[0][k].set_indices(idx)
+            touched.add(c)
+        for name, flag in st["actnorm_inited"].items():
+            c, k = (int(v) for v in name.split("."))
+            self._side_car_modules(c)[1][k].inited = bool(flag)
+            touched.add(c)
+        for c in touched:           # handles and trainers were packed with the old permutations
+            self._handles.pop(c, None)
+            self._trainers.pop(c, None)

@@ -48,6 +48,8 @@ ABI_SYMBOLS = (
     "gbnf_image_trainer_forward", "gbnf_image_trainer_grad_floats", "gbnf_image_trainer_backward",
     "gbnf_image_trainer_bind_lu", "gbnf_image_trainer_bind_top", "gbnf_image_trainer_step_grad_floats",
     "gbnf_image_trainer_step_workspace_bytes", "gbnf_image_trainer_apply_update", "gbnf_image_trainer_nll_step",
+    "gbnf_image_rho_step_workspace_bytes", "gbnf_image_mixture_rho_step",
+    "gbnf_image_boosted_step_workspace_bytes", "gbnf_image_boosted_nll_step",
 )
 
 
@@ -234,6 +236,10 @@ def lib():
     L.gbnf_image_trainer_apply_update.argtypes = [vp, vp, vp, vp, C.POINTER(_OptHyper), vp, vp]
     L.gbnf_image_trainer_nll_step.argtypes = [vp, vp, vp, i64, C.c_float, vp, vp, vp, C.POINTER(_OptHyper), vp, vp, i64, vp]
     L.gbnf_image_flow_inverse.argtypes = [vp, vp, vp, C.c_float, i64, vp, vp, i64, vp]
+    L.gbnf_image_rho_step_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
+    L.gbnf_image_mixture_rho_step.argtypes = [C.POINTER(vp), i32, vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp]
+    L.gbnf_image_boosted_step_workspace_bytes.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.gbnf_image_boosted_nll_step.argtypes = [vp, C.c_float, vp, vp, vp, i64, C.c_float, vp, vp, vp, C.POINTER(_OptHyper), vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -596,6 +602,46 @@ class NativeImageFlow:
                                                  ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         return x
 
+    _rho_ws = {}       # device -> workspace of rho_step (grown to the largest call so far)
+
+    @staticmethod
+    def rho_step(flows, x, noise, component, rho, step_size):
+        """One iteration of ``update_rho`` for image ``component`` >= 1 on the device (gbnf_image_mixture_rho_step): the forwards of
+        ``flows[0 .. component]`` (``NativeImageFlow`` handles in component order, the same ``noise`` for all, None = none) one after
+        another on the current stream, the reference's un-normalised recursion, grad = mean(fixed_ll - new_ll) and
+        ``rho[component] = clamp(rho[component] - step_size * grad, 0.01, 100)`` written IN PLACE into ``rho`` (a contiguous float32
+        device tensor; no version counter moves).  -> stats (4,) device tensor: grad, rho before, rho after, |after - before|.  The
+        (component + 1, n) log-likelihood table of the call stays in ``flows[component].rho_ll``."""
+        import torch
+        component = int(component)
+        flows = list(flows)[: max(component, 0) + 1]
+        if component < 1 or len(flows) != component + 1:
+            raise GbnfError(f"rho_step needs component >= 1 and handles of components 0 .. component, got component = {component} "
+                            f"and {len(flows)} handle(s)")
+        _require_device_f32(x, "x")
+        _require_device_f32(rho, "rho")
+        if x.dim() != 4 or x.shape[0] < 1 or any(tuple(x.shape[1:]) != f.input_size for f in flows):
+            raise GbnfError(f"x must be (n,{flows[0].input_size}) with n >= 1 for every handle, got {tuple(x.shape)}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        if rho.dim() != 1 or rho.numel() <= component:
+            raise GbnfError("rho has no entry for this component")
+        n = x.shape[0]
+        handles = (C.c_void_p * len(flows))(*[f.handle.value for f in flows])
+        nb = C.c_int64()
+        _check(lib().gbnf_image_rho_step_workspace_bytes(handles, len(flows), n, C.byref(nb)))
+        ws = NativeImageFlow._rho_ws.get(x.device)
+        if ws is None or ws.numel() * 4 < nb.value:
+            ws = NativeImageFlow._rho_ws[x.device] = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        table = flows[component].rho_ll = torch.empty((component + 1, n), dtype=torch.float32, device=x.device)
+        stats = torch.zeros(4, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_image_mixture_rho_step(handles, component, ptr(x), ptr(noise), n, ptr(rho), float(step_size), ptr(table),
+                                                 ptr(stats), ptr(ws), ws.numel() * 4, _stream_ptr()))
+        return stats
+
     def close(self):
         if getattr(self, "handle", None):
             lib().gbnf_image_flow_destroy(self.handle)
@@ -707,6 +753,7 @@ class NativeImageTrainer:
         self.device = self._tensors[0].device
         self._ws = None
         self._step_ws = None
+        self._boost_ws = None       # workspace of boosted_nll_step
         self._layout_step()
 
     def key(self):
@@ -827,6 +874,39 @@ class NativeImageTrainer:
         _check(lib().gbnf_image_trainer_nll_step(self.handle, ptr(x), ptr(noise), n, float(loss_scale), ptr(flat), ptr(state.exp_avg),
                                                  ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(self._step_ws),
                                                  self._step_ws.numel() * 4, _stream_ptr()))
+        state.step += 1
+        return stats, flat
+
+    def boosted_nll_step(self, fixed, x, noise, state, *, g_floor=-10.0, loss_scale=1.0, **hyper):
+        """``nll_step`` with the fixed-mixture term of the boosted image loss (gbnf_image_boosted_nll_step): the forward of ``fixed`` (a
+        ``NativeImageFlow`` of the same input size) on the same ``(x, noise)``, G_nll = mean(-max(ll_G, g_floor)) (``g_floor``
+        = -inf: no clamp), then the step of this component, unchanged -- the G term is never differentiated.  -> (stats (8,) device
+        tensor: [0..3] as ``nll_step``, [4] G_nll in nats, [5] nll - G_nll, [6] rows below the floor or non-finite, [7] 0; the flat
+        unclipped scaled gradient in the STEP layout)."""
+        import torch
+        if not isinstance(fixed, NativeImageFlow) or not fixed.handle:
+            raise GbnfError("fixed must be an open NativeImageFlow")
+        _require_device_f32(x, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size or tuple(fixed.input_size) != self.input_size:
+            raise GbnfError(f"x must be (n,{self.input_size}) and fixed take the same images, got {tuple(x.shape)} and {fixed.input_size}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        n = x.shape[0]
+        state.check(self)
+        h = self._hyper(state, **hyper)
+        nb = C.c_int64()
+        _check(lib().gbnf_image_boosted_step_workspace_bytes(fixed.handle, self.handle, n, C.byref(nb)))
+        if self._boost_ws is None or self._boost_ws.numel() * 4 < nb.value or self._boost_ws.device != x.device:
+            self._boost_ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        ws = self._boost_ws
+        flat = torch.empty(self.step_grad_floats, dtype=torch.float32, device=x.device)
+        stats = torch.zeros(8, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_image_boosted_nll_step(fixed.handle, float(g_floor), self.handle, ptr(x), ptr(noise), n, float(loss_scale),
+                                                 ptr(flat), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(ws),
+                                                 ws.numel() * 4, _stream_ptr()))
         state.step += 1
         return stats, flat
 

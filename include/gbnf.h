@@ -727,7 +727,8 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* trainer, const float* trace,
  *   nll_i = -(log_normal_diag(z, z_mu, z_var) + logdet),  loss = loss_scale * mean_i(nll_i)   (the reference: 1 / (ln 2 C H W)),
  * loss.backward(), clip_grad_norm_ and optimizer.step() (optimization/optimizers.py:54-65) -- on the trainer's live tensors, with no
  * host read and no synchronisation.  The boosted image loss (:247-261) differs from this one by a term that does not depend on the
- * trained component: its gradient is this one, and there is no resampling on the image path.
+ * trained component: its gradient is this one, and there is no resampling on the image path (gbnf_image_boosted_nll_step reports
+ * that term next to this step).
  *
  * The calls below add what gbnf_image_trainer_forward / _backward leave to the caller:
  *   - the log-determinants of the 1 x 1 matrices, sum over the steps of hw * log|det W| (hw: pixels of the step's level), and their
@@ -767,6 +768,61 @@ int gbnf_image_trainer_apply_update(gbnf_image_trainer* trainer, const float* gr
 int gbnf_image_trainer_nll_step(gbnf_image_trainer* trainer, const float* x, const float* noise, int64_t n, float loss_scale,
                                 float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper,
                                 float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* ---- boosting for image components: the mixture weight of a component, and the boosted step's fixed-mixture term -----------------
+ * Replaces: ONE iteration of BoostedFlow.update_rho (models/boosted_flow.py:119-207, the approximate branch) for image components --
+ * the image counterpart of gbnf_mixture_rho_step -- in one call on `stream`, with no host read and no synchronisation.
+ * flows: a HOST array of component + 1 evaluation handles in component order.  x, noise as gbnf_image_flow_forward (noise may be
+ * NULL); every component sees the same noise.  For c = 0 .. component the component's forward runs through the code path of
+ * gbnf_image_flow_forward -- each handle keeps its own numerics protocol (range marks, the same-call repair launch, the on-data check;
+ * a demoted or GBNF_MATH_F32 handle is fine) -- and row c of ll_workspace ((component + 1, n) contiguous DEVICE floats, also an
+ * output) receives its ll.  The chains are launched on the caller's stream one after another: the call forks no stream of its own.
+ * Then, on that table, exactly what gbnf_mixture_rho_step does: the un-normalised recursion (:124-137), grad = mean(fixed_ll - new_ll),
+ *   rho[component] = min(max(rho[component] - step_size * grad, 0.01), 100)   (:193-199), in place on the DEVICE buffer.
+ * Only entry `component` of rho_dev is written, and the recursion never reads it.  stats_dev: 4 DEVICE floats [grad, rho before,
+ * rho after, |after - before|].  The step-size schedule and the stopping rule (:193, :200-204) stay with the caller.
+ *
+ * What `ll` means here: the reference's _rho_gradients applies log_normal_standard(z, dim=-1) to z, which for a 4-D image z raises a
+ * shape error (and would ignore the learned top prior): that method has never run for images.  This call uses the image path's own
+ * log-likelihood, ll = log_normal_diag(z, z_mu, z_var) + logdet (image_experiment.py:227), what gbnf_image_flow_forward writes to `ll`.
+ * The update rule, the un-normalised recursion and the clamp are the reference's.  A constant added to every component's ll cancels in
+ * fixed_ll - new_ll (every recursion stage weighs with 1 - rho[c] and rho[c]), so the 2 pi term that log_normal_diag leaves out
+ * changes nothing.
+ *
+ * workspace: caller-owned DEVICE scratch of gbnf_image_rho_step_workspace_bytes(flows, component + 1, n) bytes -- the largest
+ * gbnf_image_flow_workspace_bytes of the handles and the call's ldj accumulator, each 256-byte aligned.  GBNF_ERR_INVALID (nothing
+ * launched): a null flows / x / rho_dev / ll_workspace / stats_dev / workspace or a null entry of flows, component < 1, n < 1, handles
+ * whose input shape (channels, height, width) differs, a short workspace.  The partial sums live in the per-device buffer of
+ * gbnf_mixture_rho_step: two rho calls on one device must not run concurrently. */
+int gbnf_image_rho_step_workspace_bytes(const gbnf_image_flow* const* flows, int32_t n_flows, int64_t n, int64_t* bytes);
+int gbnf_image_mixture_rho_step(const gbnf_image_flow* const* flows, int32_t component, const float* x, const float* noise,
+                                int64_t n, float* rho_dev, float step_size, float* ll_workspace, float* stats_dev,
+                                void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Replaces: one iteration of image_experiment.py:398-419 for the component being trained, the fixed-mixture term of
+ * compute_boosted_loss (:247-261) included -- the image counterpart of gbnf_boosted_nll_step -- in one call on `stream`, with no host
+ * read and no synchronisation:
+ *   1. gbnf_image_flow_forward of `fixed` (the component the reference draws with _sample_component, :400-401) on (x, noise), ll only;
+ *   2. G_nll = mean_i(-max(ll_G,i, g_floor))  (:252-254; the reference's G_MAX_LOSS is -10; g_floor = -INFINITY: no clamp), summed per
+ *      workgroup in double precision and re-added in a fixed order; a NaN ll stays NaN, as torch.max keeps it.  The same pass counts
+ *      the rows with ll_G < g_floor or a non-finite ll_G;
+ *   3. gbnf_image_trainer_nll_step on the same (x, noise), unchanged;
+ *   4. stats[5] = stats[0] - stats[4].
+ * The G term does not depend on the trained parameters, and this call NEVER differentiates it: in the reference a gradient could flow
+ * through max only for rows above the floor of a fixed component that is also the one being trained (the first component, all_trained
+ * False); the gradient here is that of gbnf_image_trainer_nll_step in every case.
+ * stats_dev: 8 DEVICE floats: [0..3] as gbnf_image_trainer_nll_step writes them; [4] G_nll in nats; [5] stats[0] - stats[4], the
+ * reference's `nll` (:256), unscaled; [6] the row count of step 2 (the batch size when every image lies below the floor); [7] 0.
+ * workspace: caller-owned DEVICE scratch of gbnf_image_boosted_step_workspace_bytes bytes -- the nll_step workspace, the fixed
+ * component's forward workspace, its ldj and ll, the partial sums, each 256-byte aligned.  GBNF_ERR_INVALID (nothing launched):
+ * everything gbnf_image_trainer_nll_step refuses, a null `fixed`, a `fixed` whose input shape differs from the trainer's, a short
+ * workspace. */
+int gbnf_image_boosted_step_workspace_bytes(const gbnf_image_flow* fixed, const gbnf_image_trainer* trainer, int64_t n,
+                                            int64_t* bytes);
+int gbnf_image_boosted_nll_step(const gbnf_image_flow* fixed, float g_floor, gbnf_image_trainer* trainer, const float* x,
+                                const float* noise, int64_t n, float loss_scale, float* grads, float* exp_avg, float* exp_avg_sq,
+                                const gbnf_opt_hyper* hyper, float* stats_dev, void* workspace, int64_t workspace_bytes,
+                                void* stream);
 
 #ifdef __cplusplus
 }
