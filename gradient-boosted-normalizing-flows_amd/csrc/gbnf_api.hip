@@ -397,19 +397,110 @@ static float bf16_to_f32(uint16_t b) {
   return f;
 }
 
-// The NP pieces of one weight tile at word offset `off` (NP consecutive fragments, largest piece first): 16 rows x 32
-// k-slots.  elem(i, g, j) returns the f32 weight of row i and k-slot (g, j); lane (i,g) stores its 8 narrow values as
-// 4 words, element 2q in the low half.  NP = 2: fp16 (hi, mid); NP = 3: bf16 (p0, p1, p2); every piece rounded to nearest.
-// Returns false if a weight does not fit the narrow type's range (fp16: |w| > 65504).
-template <typename F>
-static bool put_tile(std::vector<uint32_t>& blob, size_t off, int NP, F elem) {
+// ---- the plan of a packed hx3 blob: WHERE every value-dependent word comes from ----------------------------------------------
+// One walk of the layout (plan_net_hx3 for a net's stages and bias rows, step_order / for_table_entries for a step's tables) emits
+// these records; the host packer evaluates them on host arrays (pack_net_hx3, pack_component), the live packer uploads them and
+// evaluates them on the device from the live parameter tensors at every training step (live_pack_kernel).
+struct LiveLayer { const float* W; const float* b; int rows, cols; };
+// what a weight tile holds.  The forward blob: layer 0 (a = tile t), a hidden -> hidden layer (a = out tile u, b = chunk c), the
+// output layer (a = chunk c, b = out tile o).  The backward blob's TRANSPOSED tiles (A = W^T: tile row index = a column of W):
+// the output layer's (a = hidden tile t, b = chunk c of net outputs), a hidden layer's (a = out tile u, b = chunk c), layer 0's
+// (a = chunk c of hidden units, b = tile o of net inputs)
+enum TileKind : uint16_t { TILE_L0, TILE_HIDDEN, TILE_OUT, TILE_OUT_T, TILE_HIDDEN_T, TILE_L0_T };
+// one weight tile of the blob: NP fragments at word `dst`; rows / cols: the layer's live extent (beyond it the tile is zero)
+struct LiveTile { uint32_t dst; uint16_t lid; uint16_t kind; uint16_t a, b; float scale; int rows, cols; };
+struct LiveBias { uint32_t dst; int lid; int row; int fold; float scale; };       // scale * (b[row] + (fold ? sum_k W[row][k] : 0)), row < 0: 0
+struct LiveEntry { uint32_t dst; int m; int step; };                               // a live table entry: p0..p3 at dst + 32 / 64 / 96 / 128
+struct LiveNorm { const float *na, *nb, *mean, *var; float eps; int has_norm; uint32_t ld_dst; };
+struct BlobPlan {
+  std::vector<LiveLayer> layers;       // per step and net: layer 0, the hidden -> hidden layers, the output layer
+  std::vector<LiveTile> tiles;
+  std::vector<LiveBias> biases;
+  std::vector<LiveEntry> entries;
+  std::vector<LiveNorm> norms;         // [K]
+  std::vector<int32_t> bwd_tab;        // FlowLaunch::bwd_tab
+};
+
+// k-slot (g, j) of hidden chunk c  <->  hidden unit 16*(2c + (j>>2)) + 4g + (j&3): the D-register layout of two
+// consecutive 16-unit accumulator tiles read as one k = 32 B operand
+__host__ __device__ inline int hx3_hidden_unit(int c, int gg, int j) { return 16 * (2 * c + (j >> 2)) + 4 * gg + (j & 3); }
+
+// element (row i, k-slot (g, j)) of a tile = W[row][col] of its layer (layer 0: k-slot (g, j) = input feature 8g + j)
+__host__ __device__ inline void tile_elem(int kind, int a, int b, int i, int gg, int j, int& row, int& col) {
+  const int kslot_b = hx3_hidden_unit(b, gg, j), kslot_a = hx3_hidden_unit(a, gg, j);
+  if (kind == TILE_L0) { row = 16 * a + i; col = 8 * gg + j; }
+  else if (kind == TILE_HIDDEN) { row = 16 * a + i; col = kslot_b; }
+  else if (kind == TILE_OUT) { row = 16 * b + i; col = kslot_a; }
+  else if (kind == TILE_OUT_T || kind == TILE_HIDDEN_T) { row = kslot_b; col = 16 * a + i; }      // contraction over W's rows
+  else { row = kslot_a; col = 16 * b + i; }
+}
+
+// The tiles and bias rows of one coupling network at word `base` (Hx3Layout's stage order); its layers are LiveLayers
+// lid0 .. lid0 + depth + 1.
+// tanh networks (gbnf_flow_kernel_hx3.hip.h, tanh_hx3): a layer whose output goes through tanh carries the factor
+// T = 2*log2(e) of tanh(x) = 1 - 2/(2^(T x) + 1); the kernel hands on r = 1/(2^(T x) + 1), and the layer that
+// consumes t = 1 - 2 r folds the affine map:  W.t + b = (-2 W).r + (b + W.1)   (row sums in double)
+static void plan_net_hx3(const Hx3Layout& L, int HT, int OT, int activation, int in_f, int h, int out_f, size_t base, int lid0,
+                         std::vector<LiveTile>& tiles, std::vector<LiveBias>& biases) {
+  const int depth = L.DEPTH, lout = lid0 + depth + 1;
+  const bool tanh_net = activation == GBNF_ACT_TANH;
+  const float T = tanh_net ? 2.8853900817779268f : 1.0f;
+  const float R = tanh_net ? -2.0f : 1.0f;                  // factor on the weights of a layer fed by an activation
+  const int fold = tanh_net ? 1 : 0;
+  const size_t TW = (size_t)L.NP * 256;                      // words per weight tile
+  for (int t = 0; t < HT; ++t)
+    for (int k = 0; k < 16; ++k) {
+      const int u = 16 * t + k;
+      for (int j = 0; j <= depth; ++j)
+        biases.push_back(LiveBias{(uint32_t)(base + (size_t)(j * HT + t) * 16 + k), lid0 + j, u < h ? u : -1, j > 0 ? fold : 0, T});
+    }
+  for (int o = 0; o < OT; ++o)
+    for (int k = 0; k < 16; ++k) {
+      const int r = 16 * o + k;
+      biases.push_back(LiveBias{(uint32_t)(base + (size_t)((depth + 1) * HT + o) * 16 + k), lout, r < out_f ? r : -1, fold, 1.0f});
+    }
+  auto tile = [&](int s, int n, int lid, TileKind kind, int a, int b, float scale, int rows, int cols) {      // tile n of stage s
+    tiles.push_back(LiveTile{(uint32_t)(base + L.off[s] + (size_t)n * TW), (uint16_t)lid, kind, (uint16_t)a, (uint16_t)b, scale, rows, cols});
+  };
+  int s = 0;
+  for (int i0 = 0; i0 < L.N_L0; ++i0, ++s)
+    for (int tl = 0; tl < L.nf[s] / L.NP; ++tl) tile(s, tl, lid0, TILE_L0, i0 * L.TL0 + tl, 0, T, h, in_f);
+  for (int jl = 1; jl <= depth; ++jl)
+    for (int u = 0; u < HT; ++u, ++s) {                       // hidden row u (+ output chunk (u-2)/2 in the last hidden layer)
+      for (int c = 0; c < L.HC; ++c) tile(s, c, lid0 + jl, TILE_HIDDEN, u, c, T * R, h, h);
+      if (jl == depth && u % 2 == 0 && u >= 2)
+        for (int o = 0; o < OT; ++o) tile(s, L.HC + o, lout, TILE_OUT, (u - 2) / 2, o, R, out_f, h);
+    }
+  if (depth >= 1) {                                            // drain: output chunk HC-1
+    for (int o = 0; o < OT; ++o) tile(s, o, lout, TILE_OUT, L.HC - 1, o, R, out_f, h);
+  } else {                                                     // no hidden layer: output stages of CG chunks
+    for (int k = 0; k < L.N_OUT; ++k, ++s) {
+      const int c0 = k * L.CG, cnt = std::min(L.CG, L.HC - c0);
+      for (int cc = 0; cc < cnt; ++cc)
+        for (int o = 0; o < OT; ++o) tile(s, cc * OT + o, lout, TILE_OUT, c0 + cc, o, R, out_f, h);
+    }
+  }
+}
+
+// The NP pieces of one weight tile (NP consecutive fragments at word T.dst, largest piece first): 16 rows x 32 k-slots of layer `l`.
+// Lane (i,g) stores its 8 narrow values as 4 words, element 2q in the low half.  NP = 2: fp16 (hi, mid); NP = 3: bf16 (p0, p1, p2);
+// every piece rounded to nearest.  Returns false if a weight does not fit the narrow type's range (fp16: |w| > 65504).
+// (KIND as a constant: tile_elem folds to the one map of the tile, as the device's does per wave; the branch per element cost
+//  flow creation 11 %)
+template <int KIND>
+static bool put_tile_k(std::vector<uint32_t>& blob, const LiveTile T, const gbnf_linear& l, int NP) {
+  const float* W = l.weight;
+  const size_t ld = (size_t)l.in_features;
+  uint32_t* out = blob.data() + T.dst;
   bool ok = true;
   for (int lane = 0; lane < 64; ++lane) {
     const int i = lane & 15, gg = lane >> 4;
     for (int q = 0; q < 4; ++q) {
       uint32_t w[3] = {0, 0, 0};
       for (int e = 0; e < 2; ++e) {
-        float r = elem(i, gg, 2 * q + e);
+        int row, col;
+        tile_elem(KIND, T.a, T.b, i, gg, 2 * q + e, row, col);
+        float r = (row < T.rows && col < T.cols) ? T.scale * W[row * ld + col] : 0.0f;
         if (NP == 2 && !(std::fabs(r) <= 65504.0f)) ok = false;
         for (int k = 0; k < NP; ++k) {
           const uint16_t b = NP == 2 ? f16_bits(r) : bf16_bits(r);
@@ -417,87 +508,71 @@ static bool put_tile(std::vector<uint32_t>& blob, size_t off, int NP, F elem) {
           r -= NP == 2 ? f16_to_f32(b) : bf16_to_f32(b);
         }
       }
-      for (int k = 0; k < NP; ++k) blob[off + (size_t)k * 256 + (size_t)lane * 4 + q] = w[k];
+      for (int k = 0; k < NP; ++k) out[(size_t)k * 256 + (size_t)lane * 4 + q] = w[k];
     }
   }
   return ok;
 }
 
-// k-slot (g, j) of hidden chunk c  <->  hidden unit 16*(2c + (j>>2)) + 4g + (j&3): the D-register layout of two
-// consecutive 16-unit accumulator tiles read as one k = 32 B operand
-static int hx3_hidden_unit(int c, int gg, int j) { return 16 * (2 * c + (j >> 2)) + 4 * gg + (j & 3); }
+static bool put_tile(std::vector<uint32_t>& blob, const LiveTile T, const gbnf_linear& l, int NP) {      // (the forward blob's kinds)
+  return T.kind == TILE_L0       ? put_tile_k<TILE_L0>(blob, T, l, NP)
+         : T.kind == TILE_HIDDEN ? put_tile_k<TILE_HIDDEN>(blob, T, l, NP)
+                                 : put_tile_k<TILE_OUT>(blob, T, l, NP);
+}
 
-static bool pack_net_hx3(std::vector<uint32_t>& blob, size_t base, const gbnf_net& net, int HT, int OT, int NP, int depth,
-                         int in_f, int h, int out_f) {
-  const Hx3Layout L(HT, OT, NP, depth);
-  auto put = [&](size_t off, float v) { std::memcpy(&blob[base + off], &v, 4); };
-  const gbnf_linear& l0 = net.layers[0];
-  const gbnf_linear& lout = net.layers[depth + 1];
+// The host packer of one coupling network: the plan, evaluated on the host arrays of `net`.
+static bool pack_net_hx3(std::vector<uint32_t>& blob, size_t base, const gbnf_net& net, const Hx3Layout& L, int HT, int OT, int in_f,
+                         int h, int out_f) {
+  std::vector<LiveTile> tiles;
+  std::vector<LiveBias> biases;
+  plan_net_hx3(L, HT, OT, net.activation, in_f, h, out_f, base, 0, tiles, biases);
+  for (const LiveBias& B : biases) {
+    float v = 0.0f;
+    if (B.row >= 0) {
+      const gbnf_linear& l = net.layers[B.lid];
+      double b = l.bias[B.row];
+      if (B.fold)
+        for (int k = 0; k < l.in_features; ++k) b += (double)l.weight[(size_t)B.row * l.in_features + k];
+      v = B.scale * (float)b;
+    }
+    std::memcpy(&blob[B.dst], &v, 4);
+  }
   bool ok = true;
-  // tanh networks (gbnf_flow_kernel_hx3.hip.h, tanh_hx3): a layer whose output goes through tanh carries the factor
-  // T = 2*log2(e) of tanh(x) = 1 - 2/(2^(T x) + 1); the kernel hands on r = 1/(2^(T x) + 1), and the layer that
-  // consumes t = 1 - 2 r folds the affine map:  W.t + b = (-2 W).r + (b + W.1)   (row sums in double)
-  const bool tanh_net = net.activation == GBNF_ACT_TANH;
-  const float T = tanh_net ? 2.8853900817779268f : 1.0f;
-  const float R = tanh_net ? -2.0f : 1.0f;                  // factor on the weights of a layer fed by an activation
-  auto folded_bias = [&](const gbnf_linear& l, int row, int n_in) {
-    double b = l.bias[row];
-    if (tanh_net)
-      for (int k = 0; k < n_in; ++k) b += (double)l.weight[(size_t)row * n_in + k];
-    return (float)b;
-  };
-  for (int t = 0; t < HT; ++t)
-    for (int k = 0; k < 16; ++k) {
-      const int u = 16 * t + k;
-      put((size_t)t * 16 + k, u < h ? T * l0.bias[u] : 0.0f);
-      for (int j = 1; j <= depth; ++j)
-        put((size_t)(j * HT + t) * 16 + k, u < h ? T * folded_bias(net.layers[j], u, h) : 0.0f);
-    }
-  for (int o = 0; o < OT; ++o)
-    for (int k = 0; k < 16; ++k) {
-      const int r = 16 * o + k;
-      put((size_t)((depth + 1) * HT + o) * 16 + k, r < out_f ? folded_bias(lout, r, h) : 0.0f);
-    }
-  const size_t TW = (size_t)NP * 256;                        // words per weight tile
-  auto out_tile = [&](size_t off, int c, int o) {             // output-layer tile o of hidden chunk c
-    ok &= put_tile(blob, off, NP, [&](int i, int gg, int j) {
-      const int row = 16 * o + i, ui = hx3_hidden_unit(c, gg, j);
-      return (row < out_f && ui < h) ? R * lout.weight[(size_t)row * h + ui] : 0.0f;
-    });
-  };
-  int s = 0;
-  for (int i0 = 0; i0 < L.N_L0; ++i0, ++s) {               // layer 0: k-slot (g,j) = input feature 8g + j
-    const int t0 = i0 * L.TL0;
-    for (int tl = 0; tl < L.nf[s] / NP; ++tl) {
-      const int t = t0 + tl;
-      ok &= put_tile(blob, base + L.off[s] + (size_t)tl * TW, NP, [&](int i, int gg, int j) {
-        const int u = 16 * t + i, k = 8 * gg + j;
-        return (u < h && k < in_f) ? T * l0.weight[(size_t)u * in_f + k] : 0.0f;
-      });
-    }
-  }
-  for (int jl = 1; jl <= depth; ++jl) {
-    const gbnf_linear& lj = net.layers[jl];
-    for (int u = 0; u < HT; ++u, ++s) {                       // hidden row u (+ output chunk (u-2)/2 in the last hidden layer)
-      for (int c = 0; c < L.HC; ++c)
-        ok &= put_tile(blob, base + L.off[s] + (size_t)c * TW, NP, [&](int i, int gg, int j) {
-          const int uo = 16 * u + i, ui = hx3_hidden_unit(c, gg, j);
-          return (uo < h && ui < h) ? T * R * lj.weight[(size_t)uo * h + ui] : 0.0f;
-        });
-      if (jl == depth && u % 2 == 0 && u >= 2)
-        for (int o = 0; o < OT; ++o) out_tile(base + L.off[s] + (size_t)(L.HC + o) * TW, (u - 2) / 2, o);
-    }
-  }
-  if (depth >= 1) {                                            // drain: output chunk HC-1
-    for (int o = 0; o < OT; ++o) out_tile(base + L.off[s] + (size_t)o * TW, L.HC - 1, o);
-  } else {                                                     // no hidden layer: output stages of CG chunks
-    for (int k = 0; k < L.N_OUT; ++k, ++s) {
-      const int c0 = k * L.CG, cnt = std::min(L.CG, L.HC - c0);
-      for (int cc = 0; cc < cnt; ++cc)
-        for (int o = 0; o < OT; ++o) out_tile(base + L.off[s] + (size_t)(cc * OT + o) * TW, c0 + cc, o);
-    }
-  }
+  for (const LiveTile& T : tiles) ok &= put_tile(blob, T, net.layers[T.lid], L.NP);
   return ok;
+}
+
+// The feature order of step s: src[j] = the index, in the step's parameter vectors (= the logical order in front of the step), of
+// logical feature j behind its permutation (Glow) / half swap (RealNVP: cat(z1, z2) with z1 = the upper half when flipped).
+// Features [0, in_f) feed the net(s), [in_f, in_f + out_f) are coupled.
+struct StepOrder { std::vector<int> src; int in_f, out_f, net_out; bool paired; };
+static StepOrder step_order(const gbnf_flow_desc* desc, int s) {
+  const int d = desc->d, d1 = d / 2, d2 = d - d1;
+  const bool glow = desc->kind == GBNF_KIND_GLOW;
+  StepOrder o;
+  o.src.resize(d);
+  const bool flipped = !glow && desc->realnvp_steps[s].flipped;
+  o.in_f = flipped ? d2 : d1;
+  o.out_f = flipped ? d1 : d2;
+  for (int j = 0; j < d; ++j)
+    o.src[j] = glow ? (int)desc->glow_steps[s].perm_indices[j] : flipped ? ((j < d2) ? d1 + j : j - d2) : j;
+  o.paired = glow && desc->coupling != GBNF_COUPLING_ADDITIVE;      // affine Glow: net rows (shift_j, raw_j) adjacent
+  o.net_out = o.paired ? 2 * o.out_f : o.out_f;
+  return o;
+}
+
+// The in (which = 0) and out (which = 1) table entries [g][e] of a step: fn(which, g * NENT + e, logical feature or -1).
+//   in : split kernels k = 8g + e; f32 kernels k = 4e + g (k-step e, lane group g)
+//   out: affine pairs j = 8o + 2g + pp (e = 2o + pp); plain j = 16o + 4g + r (e = 4o + r)
+template <typename F>
+static void for_table_entries(const StepOrder& o, bool hx3, F fn) {
+  for (int gg = 0; gg < 4; ++gg)
+    for (int e = 0; e < NENT; ++e) {
+      const int k = hx3 ? 8 * gg + e : 4 * e + gg;
+      fn(0, gg * NENT + e, k < o.in_f ? k : -1);
+      const int jj = o.paired ? 8 * (e >> 1) + 2 * gg + (e & 1) : 16 * (e >> 2) + 4 * gg + (e & 3);
+      fn(1, gg * NENT + e, jj < o.out_f ? o.in_f + jj : -1);
+    }
 }
 
 static const Variant* find_variant(const VariantKey& k) {
@@ -728,20 +803,26 @@ static bool choose_f32(int kind, int ht, int ksl, int ks1, int ot, int depth, in
 }
 
 // Pads, tiles and folds the slot maps of `desc` for the kernel variant `vc` (host memory only).
-static void pack_component(const gbnf_flow_desc* desc, const DescInfo& info, const VariantChoice& vc, PackedBlob* pb) {
+// plan != null (split kernels): structure only -- the parameter arrays of `desc` are DEVICE memory and are not read.  The words that
+// do not depend on parameter values are written (header, slot and activation words, the identity constants of every table entry,
+// the final slot map), and *plan receives where every other word comes from.
+static void pack_component(const gbnf_flow_desc* desc, const DescInfo& info, const VariantChoice& vc, PackedBlob* pb, BlobPlan* plan = nullptr) {
   const int d = desc->d, K = desc->n_steps;
   const bool glow = desc->kind == GBNF_KIND_GLOW;
-  const bool additive = glow && desc->coupling == GBNF_COUPLING_ADDITIVE;
-  const int d1 = d / 2, d2 = d - d1;
   const int h = info.ref.hidden, depth = info.ref.depth;
   const bool hx3 = vc.hx3;
   const int HT = vc.ht, OT = vc.ot, KS1V = vc.ks1;
   const int nnets = glow ? 1 : 2;
-  const size_t NW = hx3 ? (size_t)Hx3Layout(HT, OT, vc.np, depth).NET_WORDS : net_words(HT, KS1V, OT, depth);
+  const Hx3Layout L(HT, OT, hx3 ? vc.np : 2, hx3 ? depth : 1);      // (read for the split kernels only)
+  const size_t NW = hx3 ? (size_t)L.NET_WORDS : net_words(HT, KS1V, OT, depth);
   const size_t step_words = SMALL_WORDS + nnets * NW;
   const size_t total_words = step_words * K + 64;
   std::vector<uint32_t>& blob = pb->words;
   blob.assign(total_words, 0u);
+  if (plan) {
+    plan->norms.resize(K);
+    plan->bwd_tab.assign((size_t)K * 2 * 4 * NENT, -1);
+  }
 
   // slot map: sigma[j] = LDS slot of logical feature j at the current step
   std::vector<int> sigma(d), prev(d);
@@ -753,104 +834,72 @@ static void pack_component(const gbnf_flow_desc* desc, const DescInfo& info, con
   double macs = 0, padded = 0;
   for (int s = 0; s < K; ++s) {
     const size_t sb = step_words * s;
+    const StepOrder o = step_order(desc, s);
+    const int in_f = o.in_f, net_out = o.net_out;
     prev = sigma;
-    int in_f, out_f;
-    // per logical (post-permutation) feature j: slot + norm params p0..p3
-    std::vector<float> P0(d, 0.f), P1(d, 1.f), P2(d, 1.f), P3(d, 0.f);
-    std::vector<int> in_feat, out_feat;  // logical (new order) feature ids feeding the net / being coupled
+    for (int j = 0; j < d; ++j) sigma[j] = prev[o.src[j]];
+    // norm params p0..p3 per feature in the step's parameter order (identity: no normalisation, or structure only)
+    std::vector<float> q0(d, 0.f), q1(d, 1.f), q2(d, 1.f), q3(d, 0.f);
     float ld_const = 0.f;
+    bool live_norm = glow;
     if (glow) {
       const gbnf_glow_step& st = desc->glow_steps[s];
-      // z'[j] = actnorm(z)[perm[j]]
-      float sum_logs = 0.f;
-      for (int m = 0; m < d; ++m) sum_logs += st.actnorm_logs[m];   // torch.sum(logs), sequential f32
-      ld_const = sum_logs;
-      for (int j = 0; j < d; ++j) {
-        const int m = (int)st.perm_indices[j];
-        sigma[j] = prev[m];
-        P0[j] = st.actnorm_bias[m];
-        P1[j] = expf(st.actnorm_logs[m]);
-        P2[j] = expf(-st.actnorm_logs[m]);      // for the inverse flow (ActNorm reverse multiplies by exp(-logs))
+      if (plan) {
+        plan->norms[s] = LiveNorm{st.actnorm_bias, st.actnorm_logs, nullptr, nullptr, 0.0f, 1, (uint32_t)(sb + 1)};
+      } else {
+        for (int m = 0; m < d; ++m) {      // z'[j] = actnorm(z)[perm[j]]
+          ld_const += st.actnorm_logs[m];   // torch.sum(logs), sequential f32
+          q0[m] = st.actnorm_bias[m];
+          q1[m] = expf(st.actnorm_logs[m]);
+          q2[m] = expf(-st.actnorm_logs[m]);      // for the inverse flow (ActNorm reverse multiplies by exp(-logs))
+        }
       }
-      in_f = d1; out_f = d2;
-      for (int j = 0; j < d1; ++j) in_feat.push_back(j);
-      for (int j = 0; j < d2; ++j) out_feat.push_back(d1 + j);
     } else {
-      const gbnf_realnvp_step& st = desc->realnvp_steps[s];
-      // BN acts on the OLD logical order; new order = cat(z1, z2) with z1 = upper half when flipped
-      std::vector<float> q0(d, 0.f), q1(d, 1.f), q2(d, 1.f), q3(d, 0.f);
-      if (st.has_batch_norm) {
-        float acc = 0.f;
+      const gbnf_realnvp_step& st = desc->realnvp_steps[s];      // BN acts on the OLD logical order
+      live_norm = st.has_batch_norm != 0;
+      if (plan) {
+        plan->norms[s] = LiveNorm{st.bn_log_gamma, st.bn_beta, st.bn_running_mean, st.bn_running_var, st.bn_eps, live_norm ? 1 : 0, (uint32_t)(sb + 1)};
+      } else if (st.has_batch_norm) {
         for (int m = 0; m < d; ++m) {
           const float ve = st.bn_running_var[m] + st.bn_eps;
           q0[m] = st.bn_running_mean[m];
           q1[m] = sqrtf(ve);
           q2[m] = expf(st.bn_log_gamma[m]);
           q3[m] = st.bn_beta[m];
-          acc += st.bn_log_gamma[m] - 0.5f * logf(ve);      // models/layers.py:357-358
+          ld_const += st.bn_log_gamma[m] - 0.5f * logf(ve);      // models/layers.py:357-358
         }
-        ld_const = acc;
       }
-      in_f = st.flipped ? d2 : d1;
-      out_f = st.flipped ? d1 : d2;
-      for (int j = 0; j < d; ++j) {
-        int m;  // old logical index of new logical feature j
-        if (st.flipped) m = (j < d2) ? d1 + j : j - d2;
-        else m = j;
-        sigma[j] = prev[m];
-        P0[j] = q0[m]; P1[j] = q1[m]; P2[j] = q2[m]; P3[j] = q3[m];
-      }
-      for (int j = 0; j < in_f; ++j) in_feat.push_back(j);
-      for (int j = 0; j < out_f; ++j) out_feat.push_back(in_f + j);
     }
+    const gbnf_net& na = glow ? desc->glow_steps[s].block : desc->realnvp_steps[s].t_net;
+    const gbnf_net& nb = glow ? desc->glow_steps[s].block : desc->realnvp_steps[s].s_net;
     put_i(sb + 0, ceil_div(in_f, 4));
     put_f(sb + 1, ld_const);
-    {   // activation of the step's net(s): 1 = relu (read by the per-step-activation kernel variants only)
-      const gbnf_net& na = glow ? desc->glow_steps[s].block : desc->realnvp_steps[s].t_net;
-      const gbnf_net& nb = glow ? desc->glow_steps[s].block : desc->realnvp_steps[s].s_net;
-      put_i(sb + 2, na.activation == GBNF_ACT_RELU ? 1 : 0);
-      put_i(sb + 3, nb.activation == GBNF_ACT_RELU ? 1 : 0);
-    }
-    // in tables [g][e]: f32 kernel k = 4e + g (k-step e, lane group g); split kernels k = 8g + e
-    for (int gg = 0; gg < 4; ++gg)
-      for (int e = 0; e < NENT; ++e) {
-        const int k = hx3 ? 8 * gg + e : 4 * e + gg;
-        const size_t o = sb + SMALL_HDR + gg * NENT + e;
-        if (k < in_f) {
-          const int j = in_feat[k];
-          put_i(o, sigma[j]); put_f(o + 32, P0[j]); put_f(o + 64, P1[j]); put_f(o + 96, P2[j]); put_f(o + 128, P3[j]);
-        } else {
-          put_i(o, -1); put_f(o + 32, 0.f); put_f(o + 64, 1.f); put_f(o + 96, 1.f); put_f(o + 128, 0.f);
-        }
+    // activation of the step's net(s): 1 = relu (read by the per-step-activation kernel variants only)
+    put_i(sb + 2, na.activation == GBNF_ACT_RELU ? 1 : 0);
+    put_i(sb + 3, nb.activation == GBNF_ACT_RELU ? 1 : 0);
+    for_table_entries(o, hx3, [&](int which, int idx, int j) {
+      const size_t w = sb + SMALL_HDR + 160 * which + idx;
+      const int m = j >= 0 ? o.src[j] : 0;       // (an unused entry: slot -1 and the identity)
+      put_i(w, j >= 0 ? sigma[j] : -1);
+      put_f(w + 32, j >= 0 ? q0[m] : 0.f); put_f(w + 64, j >= 0 ? q1[m] : 1.f); put_f(w + 96, j >= 0 ? q2[m] : 1.f); put_f(w + 128, j >= 0 ? q3[m] : 0.f);
+      if (plan && j >= 0 && live_norm) {          // (a RealNVP step without BatchNorm keeps the identity constants)
+        plan->entries.push_back(LiveEntry{(uint32_t)w, m, s});
+        plan->bwd_tab[((size_t)s * 2 + which) * 4 * NENT + idx] = m;
       }
-    // out tables [g][e]: affine pairs j = 8o + 2g + pp (e = 2o + pp); plain j = 16o + 4g + r (e = 4o + r)
-    const bool paired = glow && !additive;
-    for (int gg = 0; gg < 4; ++gg)
-      for (int e = 0; e < NENT; ++e) {
-        int jj;
-        if (paired) jj = 8 * (e >> 1) + 2 * gg + (e & 1);
-        else jj = 16 * (e >> 2) + 4 * gg + (e & 3);
-        const size_t o = sb + SMALL_HDR + 160 + gg * NENT + e;
-        if (jj < out_f) {
-          const int j = out_feat[jj];
-          put_i(o, sigma[j]); put_f(o + 32, P0[j]); put_f(o + 64, P1[j]); put_f(o + 96, P2[j]); put_f(o + 128, P3[j]);
-        } else {
-          put_i(o, -1); put_f(o + 32, 0.f); put_f(o + 64, 1.f); put_f(o + 96, 1.f); put_f(o + 128, 0.f);
-        }
-      }
-    const int net_out = paired ? 2 * out_f : out_f;
-    if (hx3) {
-      if (glow) {
-        pb->in_range &= pack_net_hx3(blob, sb + SMALL_WORDS, desc->glow_steps[s].block, HT, OT, vc.np, depth, in_f, h, net_out);
+    });
+    for (int n = 0; n < nnets; ++n) {
+      const gbnf_net& net = n == 0 ? na : nb;
+      const size_t base = sb + SMALL_WORDS + n * NW;
+      if (plan) {
+        const int lid0 = (int)plan->layers.size();
+        for (int l = 0; l < depth + 2; ++l)
+          plan->layers.push_back(LiveLayer{net.layers[l].weight, net.layers[l].bias, net.layers[l].out_features, net.layers[l].in_features});
+        plan_net_hx3(L, HT, OT, net.activation, in_f, h, net_out, base, lid0, plan->tiles, plan->biases);
+      } else if (hx3) {
+        pb->in_range &= pack_net_hx3(blob, base, net, L, HT, OT, in_f, h, net_out);
       } else {
-        pb->in_range &= pack_net_hx3(blob, sb + SMALL_WORDS, desc->realnvp_steps[s].t_net, HT, OT, vc.np, depth, in_f, h, net_out);
-        pb->in_range &= pack_net_hx3(blob, sb + SMALL_WORDS + NW, desc->realnvp_steps[s].s_net, HT, OT, vc.np, depth, in_f, h, net_out);
+        pack_net(blob, base, net, HT, KS1V, OT, depth, in_f, h, net_out);
       }
-    } else if (glow) {
-      pack_net(blob, sb + SMALL_WORDS, desc->glow_steps[s].block, HT, KS1V, OT, depth, in_f, h, net_out);
-    } else {
-      pack_net(blob, sb + SMALL_WORDS, desc->realnvp_steps[s].t_net, HT, KS1V, OT, depth, in_f, h, net_out);
-      pack_net(blob, sb + SMALL_WORDS + NW, desc->realnvp_steps[s].s_net, HT, KS1V, OT, depth, in_f, h, net_out);
     }
     macs += (double)nnets * ((double)in_f * h + (double)depth * h * h + (double)h * net_out);
     if (hx3) {   // executed narrow MACs / products per f32 product, k padded to 32
@@ -1809,16 +1858,6 @@ namespace gbnf {
 
 static_assert(CHAIN_TABLE_STEPS == LDS_TABLE_STEPS, "gbnf_internal.h: the trainer refuses at create time what the sweeps refuse at launch");
 
-struct LiveLayer { const float* W; const float* b; int rows, cols; };
-// one weight tile of the blob: NP fragments at word `dst`; kind 0: layer 0 (a = tile t), 1: hidden (a = out tile u, b = chunk c),
-// 2: output layer (a = chunk c, b = out tile o); rows / cols: the layer's live extent (beyond it the tile is zero).
-// The backward blob's TRANSPOSED tiles (A = W^T: tile row index = a column of W): kind 3: W3^T (a = hidden tile t, b = chunk c of
-// net outputs), 4: W2^T (a = out tile u, b = chunk c), 5: W1^T (a = chunk c of hidden units, b = tile o of net inputs)
-struct LiveTile { uint32_t dst; uint16_t lid; uint16_t kind; uint16_t a, b; float scale; int rows, cols; };
-struct LiveBias { uint32_t dst; int lid; int row; int fold; float scale; };       // scale * (b[row] + (fold ? sum_k W[row][k] : 0)), row < 0: 0
-struct LiveEntry { uint32_t dst; int m; int step; };                               // a live table entry: p0..p3 at dst + 32 / 64 / 96 / 128
-struct LiveNorm { const float *na, *nb, *mean, *var; float eps; int has_norm; uint32_t ld_dst; };
-
 struct LiveBlob {
   int kind = 0, d = 0, K = 0, additive = 0, nnets = 1;
   uint32_t* blob_dev = nullptr;
@@ -1850,7 +1889,7 @@ struct LiveBlob {
   bool tilesB_packed = false;           // the last re-pack included the transposed tiles
 };
 
-// the device twin of put_tile(): lane (i,g) computes its 8 values of one tile and writes 4 words per piece
+// put_tile() on the device: lane (i,g) computes its 8 values of one tile and writes 4 words per piece
 // (sat: the device's range counter -- a weight beyond the fp16 range, +-65504 after the tanh pre-scale, cannot be split: hi rounds to inf, the
 //  residual to -inf, a ReLU of the NaN they produce is 0.  No trained model has such weights; a diverged one is COUNTED here like every other
 //  operand that leaves the range (gbnf_saturation_count), not passed over in silence)
@@ -1871,12 +1910,7 @@ __device__ __forceinline__ void live_tile(const LiveTile T, const LiveLayer* __r
     for (int e = 0; e < 2; ++e) {
       const int j = 2 * q + e;
       int row, col;                          // element W[row][col] of the layer
-      const int kslot_b = 16 * (2 * T.b + (j >> 2)) + 4 * gg + (j & 3), kslot_a = 16 * (2 * T.a + (j >> 2)) + 4 * gg + (j & 3);
-      if (T.kind == 0) { row = 16 * T.a + i; col = 8 * gg + j; }
-      else if (T.kind == 1) { row = 16 * T.a + i; col = kslot_b; }
-      else if (T.kind == 2) { row = 16 * T.b + i; col = kslot_a; }
-      else if (T.kind == 3 || T.kind == 4) { row = kslot_b; col = 16 * T.a + i; }      // contraction over W's rows
-      else { row = kslot_a; col = 16 * T.b + i; }
+      tile_elem(T.kind, T.a, T.b, i, gg, j, row, col);
       float r = (row < T.rows && col < T.cols) ? T.scale * L.W[(size_t)row * L.cols + col] : 0.0f;
       if constexpr (NP == 2) {
         big = big || !(__builtin_fabsf(r) <= 65504.0f);
@@ -2084,173 +2118,52 @@ int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offset
   VariantChoice vc;
   rc = live_choose(desc, info, &vc, prec == 0 ? -3 : -6);
   if (rc) return rc;
-  // ---- the value-independent words: pack a copy of the descriptor whose parameter arrays are host zeros
-  static const std::vector<float> zeros((size_t)512 * 512 + 64, 0.0f);
-  std::vector<gbnf_glow_step> gsteps;
-  std::vector<gbnf_realnvp_step> rsteps;
-  std::vector<std::vector<gbnf_linear>> lin_store;
-  auto zero_net = [&](const gbnf_net& n) {
-    lin_store.emplace_back(n.layers, n.layers + n.n_layers);
-    for (gbnf_linear& l : lin_store.back()) { l.weight = zeros.data(); l.bias = zeros.data(); }
-    gbnf_net z = n;
-    z.layers = lin_store.back().data();
-    return z;
-  };
-  lin_store.reserve((size_t)2 * K);
-  gbnf_flow_desc dummy = *desc;
-  if (glow) {
-    gsteps.assign(desc->glow_steps, desc->glow_steps + K);
-    for (gbnf_glow_step& g : gsteps) { g.actnorm_bias = zeros.data(); g.actnorm_logs = zeros.data(); g.block = zero_net(g.block); }
-    dummy.glow_steps = gsteps.data();
-  } else {
-    rsteps.assign(desc->realnvp_steps, desc->realnvp_steps + K);
-    for (gbnf_realnvp_step& r : rsteps) {
-      if (r.has_batch_norm) { r.bn_log_gamma = r.bn_beta = r.bn_running_mean = r.bn_running_var = zeros.data(); }
-      r.t_net = zero_net(r.t_net);
-      r.s_net = zero_net(r.s_net);
-    }
-    dummy.realnvp_steps = rsteps.data();
-  }
+  // ---- the words that do not depend on parameter values, and where every other word comes from
   PackedBlob pb;
-  pack_component(&dummy, info, vc, &pb);
+  BlobPlan plan;
+  pack_component(desc, info, vc, &pb, &plan);
 
-  // ---- where every value-dependent word comes from (the loops of pack_component / pack_net_hx3, recording instead of computing)
+  // ---- the backward sweep's blob of transposed tiles
   const int HT = vc.ht, OT = vc.ot, NP = vc.np, nnets = glow ? 1 : 2;
-  const Hx3Layout L(HT, OT, NP, depth);
-  const size_t NW = (size_t)L.NET_WORDS, step_words = SMALL_WORDS + nnets * NW, TW = (size_t)NP * 256;
-  const int d1 = d / 2, d2 = d - d1;
-  std::vector<LiveLayer> layers;
-  std::vector<LiveTile> tiles;
-  std::vector<LiveBias> biases;
-  std::vector<LiveEntry> entries;
-  std::vector<LiveNorm> norms(K);
+  const size_t TW = (size_t)NP * 256;
   const BwdLayout LB(HT, OT, depth, NP);
   const size_t NWB = (size_t)LB.NET_WORDS, step_words_b = nnets * NWB;
   std::vector<LiveTile> tilesB;
-  std::vector<int32_t> bwd_tab((size_t)K * 2 * 4 * NENT, -1);
   // (the stage order of BwdLayout: the output layer's transpose, the hidden -> hidden layers' from the last to the first, layer 0's)
   auto add_net_bwd = [&](int lid0, size_t base, int in_f, int out_f) {       // lid0: the net's first LiveLayer (layers lid0 .. lid0 + depth + 1)
     int s = 0;
     for (int i0 = 0; i0 < LB.N_L0; ++i0, ++s)
       for (int n = 0; n < LB.nf[s] / NP; ++n) {
         const int t = i0 * LB.ROWS0 + n / LB.K0, c = n % LB.K0;
-        tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)n * TW), (uint16_t)(lid0 + depth + 1), 3, (uint16_t)t, (uint16_t)c, 1.0f, out_f, h});
+        tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)n * TW), (uint16_t)(lid0 + depth + 1), TILE_OUT_T, (uint16_t)t, (uint16_t)c, 1.0f, out_f, h});
       }
     if (depth >= 1) {
       for (int j = depth; j >= 2; --j)
         for (int u = 0; u < HT; ++u, ++s)
           for (int c = 0; c < LB.HC; ++c)
-            tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)c * TW), (uint16_t)(lid0 + j), 4, (uint16_t)u, (uint16_t)c, 1.0f, h, h});
+            tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)c * TW), (uint16_t)(lid0 + j), TILE_HIDDEN_T, (uint16_t)u, (uint16_t)c, 1.0f, h, h});
       for (int u = 0; u < HT; ++u, ++s) {
         for (int c = 0; c < LB.HC; ++c)
-          tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)c * TW), (uint16_t)(lid0 + 1), 4, (uint16_t)u, (uint16_t)c, 1.0f, h, h});
+          tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)c * TW), (uint16_t)(lid0 + 1), TILE_HIDDEN_T, (uint16_t)u, (uint16_t)c, 1.0f, h, h});
         if (u % 2 == 0 && u >= 2)
           for (int o = 0; o < 2; ++o)
-            tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)(LB.HC + o) * TW), (uint16_t)lid0, 5, (uint16_t)((u - 2) / 2), (uint16_t)o, 1.0f, h, in_f});
+            tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)(LB.HC + o) * TW), (uint16_t)lid0, TILE_L0_T, (uint16_t)((u - 2) / 2), (uint16_t)o, 1.0f, h, in_f});
       }
       for (int o = 0; o < 2; ++o)
-        tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)o * TW), (uint16_t)lid0, 5, (uint16_t)(LB.HC - 1), (uint16_t)o, 1.0f, h, in_f});
+        tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)o * TW), (uint16_t)lid0, TILE_L0_T, (uint16_t)(LB.HC - 1), (uint16_t)o, 1.0f, h, in_f});
     } else {
       for (int k = 0; k < LB.N_IN; ++k, ++s) {
         const int c0 = k * LB.CGI, cnt = std::min(LB.CGI, LB.HC - c0);
         for (int cc = 0; cc < cnt; ++cc)
           for (int o = 0; o < 2; ++o)
-            tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)(cc * 2 + o) * TW), (uint16_t)lid0, 5, (uint16_t)(c0 + cc), (uint16_t)o, 1.0f, h, in_f});
+            tilesB.push_back(LiveTile{(uint32_t)(base + LB.off[s] + (size_t)(cc * 2 + o) * TW), (uint16_t)lid0, TILE_L0_T, (uint16_t)(c0 + cc), (uint16_t)o, 1.0f, h, in_f});
       }
     }
-  };
-  // (the loops of pack_net_hx3, every depth: layer 0, `depth` hidden -> hidden layers, the output layer)
-  auto add_net = [&](const gbnf_net& net, size_t base, int in_f, int out_f) {
-    const bool tanh_net = net.activation == GBNF_ACT_TANH;
-    const float T = tanh_net ? 2.8853900817779268f : 1.0f, R = tanh_net ? -2.0f : 1.0f;
-    int lid[6];
-    for (int l = 0; l < depth + 2; ++l) {
-      lid[l] = (int)layers.size();
-      layers.push_back(LiveLayer{net.layers[l].weight, net.layers[l].bias, net.layers[l].out_features, net.layers[l].in_features});
-    }
-    const int lout = lid[depth + 1];
-    for (int t = 0; t < HT; ++t)
-      for (int k = 0; k < 16; ++k) {
-        const int u = 16 * t + k;
-        biases.push_back(LiveBias{(uint32_t)(base + (size_t)t * 16 + k), lid[0], u < h ? u : -1, 0, T});
-        for (int j = 1; j <= depth; ++j)
-          biases.push_back(LiveBias{(uint32_t)(base + (size_t)(j * HT + t) * 16 + k), lid[j], u < h ? u : -1, tanh_net ? 1 : 0, T});
-      }
-    for (int o = 0; o < OT; ++o)
-      for (int k = 0; k < 16; ++k) {
-        const int r = 16 * o + k;
-        biases.push_back(LiveBias{(uint32_t)(base + (size_t)((depth + 1) * HT + o) * 16 + k), lout, r < out_f ? r : -1, tanh_net ? 1 : 0, 1.0f});
-      }
-    int s = 0;
-    for (int i0 = 0; i0 < L.N_L0; ++i0, ++s)
-      for (int tl = 0; tl < L.nf[s] / NP; ++tl)
-        tiles.push_back(LiveTile{(uint32_t)(base + L.off[s] + (size_t)tl * TW), (uint16_t)lid[0], 0, (uint16_t)(i0 * L.TL0 + tl), 0, T, h, in_f});
-    for (int jl = 1; jl <= depth; ++jl)
-      for (int u = 0; u < HT; ++u, ++s) {
-        for (int c = 0; c < L.HC; ++c)
-          tiles.push_back(LiveTile{(uint32_t)(base + L.off[s] + (size_t)c * TW), (uint16_t)lid[jl], 1, (uint16_t)u, (uint16_t)c, T * R, h, h});
-        if (jl == depth && u % 2 == 0 && u >= 2)
-          for (int o = 0; o < OT; ++o)
-            tiles.push_back(LiveTile{(uint32_t)(base + L.off[s] + (size_t)(L.HC + o) * TW), (uint16_t)lout, 2, (uint16_t)((u - 2) / 2), (uint16_t)o, R, out_f, h});
-      }
-    if (depth >= 1) {
-      for (int o = 0; o < OT; ++o)
-        tiles.push_back(LiveTile{(uint32_t)(base + L.off[s] + (size_t)o * TW), (uint16_t)lout, 2, (uint16_t)(L.HC - 1), (uint16_t)o, R, out_f, h});
-    } else {
-      for (int k = 0; k < L.N_OUT; ++k, ++s) {
-        const int c0 = k * L.CG, cnt = std::min(L.CG, L.HC - c0);
-        for (int cc = 0; cc < cnt; ++cc)
-          for (int o = 0; o < OT; ++o)
-            tiles.push_back(LiveTile{(uint32_t)(base + L.off[s] + (size_t)(cc * OT + o) * TW), (uint16_t)lout, 2, (uint16_t)(c0 + cc), (uint16_t)o, R, out_f, h});
-      }
-    }
-    return lid[0];
   };
   for (int s = 0; s < K; ++s) {
-    const size_t sb = step_words * s;
-    int in_f, out_f;
-    std::vector<int> src(d);             // src[j] = index into the step's parameter vectors of new logical feature j
-    LiveNorm& N = norms[s];
-    N = LiveNorm{nullptr, nullptr, nullptr, nullptr, 0.0f, 0, (uint32_t)(sb + 1)};
-    if (glow) {
-      const gbnf_glow_step& st = desc->glow_steps[s];
-      N.na = st.actnorm_bias; N.nb = st.actnorm_logs; N.has_norm = 1;
-      for (int j = 0; j < d; ++j) src[j] = (int)st.perm_indices[j];
-      in_f = d1; out_f = d2;
-    } else {
-      const gbnf_realnvp_step& st = desc->realnvp_steps[s];
-      N.has_norm = st.has_batch_norm ? 1 : 0;
-      N.na = st.bn_log_gamma; N.nb = st.bn_beta; N.mean = st.bn_running_mean; N.var = st.bn_running_var; N.eps = st.bn_eps;
-      in_f = st.flipped ? d2 : d1; out_f = st.flipped ? d1 : d2;
-      for (int j = 0; j < d; ++j) src[j] = st.flipped ? ((j < d2) ? d1 + j : j - d2) : j;
-    }
-    const bool paired = glow && !additive;
-    if (glow || N.has_norm) {            // (a RealNVP step without BatchNorm keeps the identity constants of the template)
-      for (int gg = 0; gg < 4; ++gg)
-        for (int e = 0; e < NENT; ++e) {
-          const int k = 8 * gg + e;
-          if (k < in_f) {
-            entries.push_back(LiveEntry{(uint32_t)(sb + SMALL_HDR + gg * NENT + e), src[k], s});
-            bwd_tab[((size_t)s * 2 + 0) * 4 * NENT + gg * NENT + e] = src[k];
-          }
-          const int jj = paired ? 8 * (e >> 1) + 2 * gg + (e & 1) : 16 * (e >> 2) + 4 * gg + (e & 3);
-          if (jj < out_f) {
-            entries.push_back(LiveEntry{(uint32_t)(sb + SMALL_HDR + 160 + gg * NENT + e), src[in_f + jj], s});
-            bwd_tab[((size_t)s * 2 + 1) * 4 * NENT + gg * NENT + e] = src[in_f + jj];
-          }
-        }
-    }
-    const int net_out = paired ? 2 * out_f : out_f;
-    const size_t sbb = step_words_b * s;
-    if (glow) {
-      const int l0 = add_net(desc->glow_steps[s].block, sb + SMALL_WORDS, in_f, net_out);
-      add_net_bwd(l0, sbb, in_f, net_out);
-    } else {
-      const int l0 = add_net(desc->realnvp_steps[s].t_net, sb + SMALL_WORDS, in_f, net_out);
-      const int l1 = add_net(desc->realnvp_steps[s].s_net, sb + SMALL_WORDS + NW, in_f, net_out);
-      add_net_bwd(l0, sbb, in_f, net_out);
-      add_net_bwd(l1, sbb + NWB, in_f, net_out);
-    }
+    const StepOrder o = step_order(desc, s);
+    for (int n = 0; n < nnets; ++n)       // (plan.layers: depth + 2 per net, in step and net order)
+      add_net_bwd((s * nnets + n) * (depth + 2), step_words_b * s + n * NWB, o.in_f, o.net_out);
   }
 
   LiveBlob* lb = new LiveBlob();
@@ -2259,14 +2172,14 @@ int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offset
   lb->ht = vc.ht;
   lb->np = NP;
   lb->depth = depth;
-  lb->n_tiles = (int)tiles.size(); lb->n_bias = (int)biases.size(); lb->n_entries = (int)entries.size();
+  lb->n_tiles = (int)plan.tiles.size(); lb->n_bias = (int)plan.biases.size(); lb->n_entries = (int)plan.entries.size();
   for (int nt = 1; nt <= 2; ++nt) { lb->launch_nt[nt] = vc.launch_nt[nt]; lb->name_nt[nt] = vc.name_nt[nt]; }
   hipError_t e = upload_blob(pb.words, &lb->blob_dev, &lb->table_dev);
-  if (e == hipSuccess) e = upload_vec(layers, &lb->layers_dev);
-  if (e == hipSuccess) e = upload_vec(tiles, &lb->tiles_dev);
-  if (e == hipSuccess) e = upload_vec(biases, &lb->bias_dev);
-  if (e == hipSuccess) e = upload_vec(entries, &lb->entries_dev);
-  if (e == hipSuccess) e = upload_vec(norms, &lb->norms_dev);
+  if (e == hipSuccess) e = upload_vec(plan.layers, &lb->layers_dev);
+  if (e == hipSuccess) e = upload_vec(plan.tiles, &lb->tiles_dev);
+  if (e == hipSuccess) e = upload_vec(plan.biases, &lb->bias_dev);
+  if (e == hipSuccess) e = upload_vec(plan.entries, &lb->entries_dev);
+  if (e == hipSuccess) e = upload_vec(plan.norms, &lb->norms_dev);
   // ---- the backward sweep, where a variant of bwd_kernel_hx3 exists for this geometry (else the caller keeps its own)
   if (e == hipSuccess && norm_grad_offsets != nullptr) {
     const Variant* vb = find_variant(VariantKey{desc->kind, vc.ht, prec == 0 ? -3 : -6, 2, vc.ot, 1, depth, info.act_a, info.act_b});
@@ -2280,7 +2193,7 @@ int live_blob_create(const gbnf_flow_desc* desc, const int64_t* norm_grad_offset
       lb->n_tilesB = (int)tilesB.size();
       e = upload_blob(zerosB, &lb->blobB_dev, &lb->tableB_dev);
       if (e == hipSuccess) e = upload_vec(tilesB, &lb->tilesB_dev);
-      if (e == hipSuccess) e = upload_vec(bwd_tab, &lb->bwd_tab_dev);
+      if (e == hipSuccess) e = upload_vec(plan.bwd_tab, &lb->bwd_tab_dev);
       if (e == hipSuccess) e = upload_vec(goff, &lb->bwd_goff_dev);
       lb->launch_bwd = vb->fn;
       lb->name_bwd = vb->name;
@@ -2331,14 +2244,9 @@ int live_blob_backward(LiveBlob* lb, const TrainLayout& lay, float* trace, const
   hipStream_t s = (hipStream_t)stream;
   // the transposed tiles were packed by the forward call that wrote the trace (the parameters are unchanged since: the trace
   // contract of include/gbnf.h); a trainer that has not run one yet packs them here
-  if (!lb->tilesB_packed) {
-    if (lb->np == 2)
-      hipLaunchKernelGGL(live_tiles_kernel<2>, dim3((unsigned)lb->n_tilesB), dim3(64), 0, s, (const LiveTile*)lb->tilesB_dev,
-                         (const LiveLayer*)lb->layers_dev, lb->blobB_dev, (unsigned*)nullptr);
-    else
-      hipLaunchKernelGGL(live_tiles_kernel<3>, dim3((unsigned)lb->n_tilesB), dim3(64), 0, s, (const LiveTile*)lb->tilesB_dev,
-                         (const LiveLayer*)lb->layers_dev, lb->blobB_dev, (unsigned*)nullptr);
-  }
+  if (!lb->tilesB_packed)
+    hipLaunchKernelGGL(lb->np == 2 ? live_tiles_kernel<2> : live_tiles_kernel<3>, dim3((unsigned)lb->n_tilesB), dim3(64), 0, s,
+                       (const LiveTile*)lb->tilesB_dev, (const LiveLayer*)lb->layers_dev, lb->blobB_dev, (unsigned*)nullptr);
   FlowLaunch p{};
   p.blobs = lb->table_dev; p.blobs_bwd = lb->tableB_dev;
   p.n = lay.n; p.d = lb->d; p.n_steps = lb->K; p.n_comp = 1; p.n_batches = 1; p.additive = lb->additive;
@@ -2373,16 +2281,13 @@ static void live_blob_repack(LiveBlob* lb, hipStream_t s, bool with_backward = f
   const int n_tilesB = (with_backward && lb->launch_bwd != nullptr) ? lb->n_tilesB : 0;
   const int small_blocks = (lb->n_bias + 15) / 16 + (lb->n_entries + lb->K + 255) / 256;
   const int tile_blocks = (lb->n_tiles + n_tilesB + 3) / 4;
-  if (lb->np == 2)
-    hipLaunchKernelGGL(live_pack_kernel<2>, dim3((unsigned)(tile_blocks + small_blocks)), dim3(256), 0, s, (const LiveTile*)lb->tiles_dev,
-                       lb->n_tiles, (const LiveTile*)lb->tilesB_dev, n_tilesB, lb->blobB_dev, (const LiveBias*)lb->bias_dev, lb->n_bias,
-                       (const LiveEntry*)lb->entries_dev, lb->n_entries, (const LiveNorm*)lb->norms_dev, lb->K, lb->d,
-                       lb->kind == GBNF_KIND_GLOW ? 1 : 0, (const LiveLayer*)lb->layers_dev, lb->blob_dev, live_sat(lb), (const unsigned*)nullptr);
-  else
-    hipLaunchKernelGGL(live_pack_kernel<3>, dim3((unsigned)(tile_blocks + small_blocks)), dim3(256), 0, s, (const LiveTile*)lb->tiles_dev,
-                       lb->n_tiles, (const LiveTile*)lb->tilesB_dev, n_tilesB, lb->blobB_dev, (const LiveBias*)lb->bias_dev, lb->n_bias,
-                       (const LiveEntry*)lb->entries_dev, lb->n_entries, (const LiveNorm*)lb->norms_dev, lb->K, lb->d,
-                       lb->kind == GBNF_KIND_GLOW ? 1 : 0, (const LiveLayer*)lb->layers_dev, lb->blob_dev, (unsigned*)nullptr, lb->gate);
+  // (f16x3 counts the weights beyond its range and is never gated: the gate belongs to a repairing trainer's bf16x6 blob, which counts nothing)
+  const bool f16 = lb->np == 2;
+  hipLaunchKernelGGL(f16 ? live_pack_kernel<2> : live_pack_kernel<3>, dim3((unsigned)(tile_blocks + small_blocks)), dim3(256), 0, s,
+                     (const LiveTile*)lb->tiles_dev, lb->n_tiles, (const LiveTile*)lb->tilesB_dev, n_tilesB, lb->blobB_dev,
+                     (const LiveBias*)lb->bias_dev, lb->n_bias, (const LiveEntry*)lb->entries_dev, lb->n_entries, (const LiveNorm*)lb->norms_dev,
+                     lb->K, lb->d, lb->kind == GBNF_KIND_GLOW ? 1 : 0, (const LiveLayer*)lb->layers_dev, lb->blob_dev,
+                     f16 ? live_sat(lb) : (unsigned*)nullptr, f16 ? (const unsigned*)nullptr : lb->gate);
   lb->tilesB_packed = n_tilesB > 0;
 }
 

@@ -110,8 +110,10 @@ struct TrainLayout {
 
 // ---- the training path's forward sweep on the evaluation kernels (gbnf_api.hip; used by gbnf_train.hip) -------------
 // A "live blob": the packed hx3 (f16x3) parameter blob of ONE component whose parameters live in device tensors that an
-// optimiser updates in place.  `live_blob_create` packs everything that does not depend on parameter VALUES once on the
-// host (slot maps, activation flags, layout) and records where every value-dependent word comes from;
+// optimiser updates in place.  The blob's layout is walked in ONE place (gbnf_api.hip: plan_net_hx3, step_order,
+// for_table_entries, tile_elem), which yields records of where every value-dependent word comes from; the host packer of
+// gbnf_flow_create evaluates them on host arrays, `live_blob_create` runs the same pack_component in its structure-only
+// mode (slot maps, activation flags, identity constants written once; the records uploaded) and
 // `live_blob_forward` re-derives those words on the device (one gather + split kernel, ~10 us) and launches the TRAIN
 // instantiation of flow_kernel_hx3: x -> z, ldj + the trace and operand saves the backward pass needs.
 struct LiveBlob;

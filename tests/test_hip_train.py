@@ -589,6 +589,46 @@ def test_device_packer_reproduces_the_host_packer(kind, d, h, kw):
         assert diff.size < 0.01 * host.size            # only table constants may differ in the last bit
 
 
+def _blob_pins():
+    """tests/golden/make_blob_pins.py (the cases, how their blobs are built and hashed) and the JSON it wrote."""
+    import importlib.util
+    import json
+    import os
+    path = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "make_blob_pins.py")
+    spec = importlib.util.spec_from_file_location("make_blob_pins", path)
+    mod = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(mod)
+    with open(mod.PINS) as f:
+        return mod, json.load(f)
+
+
+_PINS_MOD, _PINS = _blob_pins()
+
+
+@pytest.mark.parametrize("name,math", _PINS_MOD.all_keys())
+def test_packed_blobs_match_their_pins(name, math):
+    """The blob of the host packer (gbnf_debug_flow_blob) and of the live packer (gbnf_debug_trainer_blob) against the words recorded
+    before the two packers were given one walk of the layout: every word that is a cast, a float product or a double sum bit for
+    bit (SHA-256 with the table constants zeroed), the slot words exactly, the table constants (expf / sqrtf / logf: another libm
+    or device math library may round differently) within 4 ulp."""
+    mp = _PINS_MOD
+    blobs = mp.blobs_of(name, math)
+    want = {k.split("/")[2] for k in _PINS if k.startswith(f"{name}/{math}/")}
+    assert set(blobs) == want and "flow" in want and (math == "bf16x6" or "trainer" in want)
+    for which, words in blobs.items():
+        pin, got = _PINS[f"{name}/{math}/{which}"], mp.pin_of(words)
+        assert got["n_words"] == pin["n_words"], which
+        assert got["sha256"] == pin["sha256"], which
+        a, b = mp.table_words(got), mp.table_words(pin)
+        assert a.shape == b.shape and a.size == mp.K * 321
+        print(f"{name}/{math}/{which}: {int(np.count_nonzero(a != b))} of {a.size} table words differ from the pin")
+        step = np.arange(a.size) % 321              # per step: the log-det constant, the in table [160], the out table [160]
+        slots = ((step >= 1) & (step < 33)) | ((step >= 161) & (step < 193))
+        assert np.array_equal(a[slots], b[slots]), which
+        key = lambda u: np.where(u >> 31, -(u & 0x7fffffff).astype(np.int64), (u & 0x7fffffff).astype(np.int64))     # f32 bits in value order
+        assert np.all(np.abs(key(a) - key(b)) <= 4), which
+
+
 @pytest.mark.parametrize("kind,d,h,K,n,kw", [("glow", 43, 215, 3, 300, {"depth": 0}), ("glow", 43, 215, 3, 300, {"depth": 2}),
                                              ("glow", 43, 64, 2, 77, {"depth": 0, "coupling": "additive"}), ("glow", 43, 64, 2, 1, {"depth": 2}),
                                              ("realnvp", 21, 105, 4, 129, {"depth": 0}), ("realnvp", 21, 105, 4, 2049, {"depth": 2}),
