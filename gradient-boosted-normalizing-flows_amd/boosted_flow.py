@@ -344,6 +344,22 @@ class _FlowFunction(torch.autograd.Function):
         return (None, g_x) + tuple(out)
 
 
+def deterministic_from(args, env=None):
+    """The deterministic-mode flag of a module: ``args.deterministic`` (a bool, or None / absent = not given), else the environment
+    variable GBNF_DETERMINISTIC ("1" / "0"; unset or empty = off).  Anything else raises ValueError."""
+    given = getattr(args, "deterministic", None)
+    if given is not None:
+        if not isinstance(given, (bool, int)) or given not in (0, 1, True, False):
+            raise ValueError(f"deterministic must be a bool, got {given!r}")
+        return bool(given)
+    text = (os.environ if env is None else env).get("GBNF_DETERMINISTIC", "")
+    if text in ("", "0"):
+        return False
+    if text == "1":
+        return True
+    raise ValueError(f"GBNF_DETERMINISTIC must be 0 or 1, got {text!r}")
+
+
 class BoostedFlow(nn.Module):
     """Drop-in for models/boosted_flow.py:BoostedFlow on the density-evaluation path."""
 
@@ -364,6 +380,9 @@ class BoostedFlow(nn.Module):
         if train_math not in native.NativeTrainer.TRAIN_MATH:
             raise ValueError(f"train_math must be one of {sorted(native.NativeTrainer.TRAIN_MATH)}, got {train_math!r}")
         self.train_math = train_math
+        # bit-reproducible training steps (gbnf_trainer_set_deterministic): args.deterministic, else env GBNF_DETERMINISTIC, else off.
+        # Applied to every trainer native_trainer() hands out; an unsupported geometry is refused by the first training call.
+        self.deterministic = deterministic_from(args)
         self.num_flows = args.num_flows
         self.z_size = args.z_size
         self.density_evaluation = args.density_evaluation
@@ -690,7 +709,10 @@ class BoostedFlow(nn.Module):
         if cached is None or cached[0] != key:
             # (a geometry without the kernels of self.train_math raises GbnfError here: the module never downgrades the mode)
             self._trainers[c] = (key, native.NativeTrainer(gspec.device_spec_from_component(flow), math=self.train_math))
-        return self._trainers[c][1]
+        trainer = self._trainers[c][1]
+        if trainer._deterministic != bool(self.deterministic):         # (also a cached trainer after the module's flag changed)
+            trainer.deterministic = bool(self.deterministic)
+        return trainer
 
     def _ensure_actnorm(self, x, c):
         """_ActNorm.forward initialises itself from the first batch it sees in TRAIN mode and raises in eval mode

@@ -171,7 +171,8 @@ def main(argv=None):
         jobs.append([HIPCC] + FLAGS + ["-c", api_src, "-o", api_o])
     train_o, train_src = os.path.join(OBJ, "gbnf_train.o"), os.path.join(HERE, "gbnf_train.hip")
     objs.append(train_o)
-    if args.force or not newer(train_o, [train_src, os.path.join(HERE, "gbnf_opt.h"), hdr[2], hdr[3]]):
+    if args.force or not newer(train_o, [train_src, os.path.join(HERE, "gbnf_opt.h"), os.path.join(HERE, "gbnf_wgrad_kernel.inc"),
+                                         os.path.join(HERE, "gbnf_wgrad_safe_kernel.inc"), hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", train_src, "-o", train_o])
     # the tail of a training step (loss seed, gradient norm, clip, AdamW / SGD on the live tensors): gbnf_opt.hip
     opt_o, opt_src, opt_hdr = os.path.join(OBJ, "gbnf_opt.o"), os.path.join(HERE, "gbnf_opt.hip"), os.path.join(HERE, "gbnf_opt.h")

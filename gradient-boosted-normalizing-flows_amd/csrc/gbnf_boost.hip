@@ -301,7 +301,8 @@ int gbnf_boosted_nll_step(const gbnf_mixture* fixed, int32_t n_fixed, const floa
   BoostLayout L;
   if (const int rc = boost_layout(trainer, n_fixed, n, &L)) return rc;
   if (workspace_bytes < L.total)
-    return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld (gbnf_boosted_step_workspace_bytes)", fn, (long long)workspace_bytes, (long long)L.total);
+    return fail(GBNF_ERR_INVALID, "%s: workspace too small: %lld bytes < %lld (gbnf_boosted_step_workspace_bytes)", fn, (long long)workspace_bytes, (long long)L.total);
+  if (const int rc = trainer_deterministic_check(trainer, n, /*traced=*/true, fn)) return rc;
   char* ws = (char*)workspace;
   float* ll = (float*)(ws + L.ll);
   float* G = (float*)(ws + L.G);

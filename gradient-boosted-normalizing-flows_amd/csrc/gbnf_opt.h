@@ -31,6 +31,10 @@ struct TrainerOptView {
   OptBnTable bn;
 };
 int trainer_opt_view(const gbnf_trainer* t, TrainerOptView* out);
+// Deterministic mode (gbnf_trainer_set_deterministic): GBNF_ERR_UNSUPPORTED, with the reason, if a backward call of n rows (traced: with
+// the forward call's trace) would run kernels with unordered float accumulation; GBNF_OK otherwise and with the mode off.  Launches
+// nothing: a one-call step asks before its first launch.  gbnf_train.hip
+int trainer_deterministic_check(const gbnf_trainer* t, int64_t n, bool traced, const char* fn);
 // What the norm + update launches need, for an owner that is not a gbnf_trainer (the image trainer, gbnf_image_opt.hip): the region
 // table on the device (sorted by offset, reserved regions not listed) and the floats of the flat gradient buffer.
 struct OptUpdateView {

@@ -311,7 +311,8 @@ int gbnf_trainer_nll_step(const gbnf_trainer* t, const float* x, int64_t n_x, co
   StepLayout L;
   if (const int rc = step_layout(t, tv, n, &L)) return rc;
   if (workspace_bytes < L.total)
-    return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld (gbnf_trainer_step_workspace_bytes)", fn, (long long)workspace_bytes, (long long)L.total);
+    return fail(GBNF_ERR_INVALID, "%s: workspace too small: %lld bytes < %lld (gbnf_trainer_step_workspace_bytes)", fn, (long long)workspace_bytes, (long long)L.total);
+  if (const int rc = trainer_deterministic_check(t, n, /*traced=*/true, fn)) return rc;
   const bool running_update = tv.batch_stats && n >= 2 && h->bn_momentum >= 0.0f && tv.bn.n > 0;
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;

@@ -1026,7 +1026,9 @@ __device__ __forceinline__ void wg_split8(f32x4 lo, f32x4 hi4, u32x4& h, u32x4& 
 // values) so that every wave issues the same loads -- the compiler's s_waitcnt vmcnt(N) in front of a split then names exactly
 // the loads of the OTHER register set; with a conditional fetch anywhere it has to assume the worst and waits for everything
 // in flight.  The bias gradients (row sums of D) are summed by the staging threads from the f32 values they hold anyway.
-template <int ND, int NA, int TM, int TN, bool TWO>
+// DET (deterministic mode): `grads` is this sample chunk's own partials buffer (laid out like the flat gradient buffer) and the flush
+// is plain stores; wgrad_det_reduce_kernel adds the chunks up in chunk order.
+template <int ND, int NA, int TM, int TN, bool TWO, bool DET = false>
 __device__ __forceinline__ void wgrad_block(const WgProblem& P, const float* __restrict__ ws, float* __restrict__ grads, int64_t np,
                                             int64_t s_begin, int64_t s_end, int m0, int n0, float inv_alpha, u32x4* wg_stage_raw) {
   typedef const f32x4 __attribute__((address_space(1)))* gv4;
@@ -1204,7 +1206,10 @@ __device__ __forceinline__ void wgrad_block(const WgProblem& P, const float* __r
       const int te = opaque_tid();
       const int rl = 128 * j + (te >> 2);                 // (a 64-row operand: the upper waves hold copies)
       const int m = m0 + rl;
-      if ((te & 3) == 0 && rl < P.bm && m < P.M) atomicAdd(grads + P.b_off + m, v * inv_alpha);
+      if ((te & 3) == 0 && rl < P.bm && m < P.M) {
+        if constexpr (DET) grads[P.b_off + m] = v * inv_alpha;
+        else atomicAdd(grads + P.b_off + m, v * inv_alpha);
+      }
     }
   }
 #if GBNF_WG_ABL == 1
@@ -1221,7 +1226,10 @@ __device__ __forceinline__ void wgrad_block(const WgProblem& P, const float* __r
 #pragma unroll
       for (int y = 0; y < TN; ++y) {
         const int n = nw + 16 * y + i;
-        if (m < P.M && n < P.N) atomicAdd(C + (size_t)m * P.N + n, acc[x][y][r] * inv_alpha);
+        if (m < P.M && n < P.N) {
+          if constexpr (DET) C[(size_t)m * P.N + n] = acc[x][y][r] * inv_alpha;
+          else atomicAdd(C + (size_t)m * P.N + n, acc[x][y][r] * inv_alpha);
+        }
       }
     }
 }
@@ -1229,65 +1237,37 @@ __device__ __forceinline__ void wgrad_block(const WgProblem& P, const float* __r
 __global__ void __launch_bounds__(WG_THREADS) wgrad_kernel(const WgProblem* __restrict__ probs, int n_probs,
                                                     const float* __restrict__ ws, float* __restrict__ grads, int64_t np, int chunk,
                                                     const unsigned* __restrict__ gmax, int n_blocks, const LiveReduce red) {
-  extern __shared__ __attribute__((aligned(16))) u32x4 wg_stage_raw[];      // WG_LDS_BYTES (dynamic: > 64 KB)
-  // Launch index L = y G + x is dealt out in order (round-robin over the XCDs, a workgroup to every CU as it falls free); work
-  // item L is chunk L mod Y of block L / Y, and the host numbers the blocks heaviest first (a 256 x 256 block streams 64 KB per
-  // k-step, a 256 x 64 one 40 KB: a CU pulls ~24 GB/s whatever it does, so the time of a block is its bytes): the light blocks
-  // fill in behind the heavy ones instead of the heavy ones finishing alone.
-  int bx, by;
-  {
-    const int Y = gridDim.y, L = (int)blockIdx.y * (int)gridDim.x + (int)blockIdx.x;
-    bx = L / Y;
-    by = L - bx * Y;
+#define GBNF_WG_DET 0
+#include "gbnf_wgrad_kernel.inc"
+#undef GBNF_WG_DET
+}
+// Deterministic mode: the same launch (the same text, included again), but sample chunk `by` of a block STORES its dW tile and db rows
+// to part[by][the entry's offset in the flat gradient buffer] (part_stride floats per chunk) and the dW blocks add nothing to `grads`
+// (the reduce blocks behind them add their fixed-order sums as ever); wgrad_det_reduce_kernel follows in stream order.
+__global__ void __launch_bounds__(WG_THREADS) wgrad_det_kernel(const WgProblem* __restrict__ probs, int n_probs,
+                                                    const float* __restrict__ ws, float* __restrict__ grads, int64_t np, int chunk,
+                                                    const unsigned* __restrict__ gmax, int n_blocks, const LiveReduce red,
+                                                    float* __restrict__ part, int64_t part_stride) {
+#define GBNF_WG_DET 1
+#include "gbnf_wgrad_kernel.inc"
+#undef GBNF_WG_DET
+}
+// grads[e] += part[0][e] + part[1][e] + .. + part[Y - 1][e] (in that order) for every dW / db entry e of every problem: one thread per
+// entry, grid (x: slices of a problem's entries, y: problems).  gate: as in wgrad_safe_kernel.
+__global__ void __launch_bounds__(256) wgrad_det_reduce_kernel(const WgProblem* __restrict__ probs, const float* __restrict__ part,
+                                                               int64_t part_stride, int Y, float* __restrict__ grads,
+                                                               const unsigned* __restrict__ gate) {
+  if (gate != nullptr && *gate == 0u) return;
+  const WgProblem& P = probs[blockIdx.y];
+  const int64_t mn = (int64_t)P.M * P.N, total = mn + P.M;
+  for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+    const int64_t off = e < mn ? P.c_off + e : P.b_off + (e - mn);
+    const float* src = part + off;
+    float a = 0.0f;
+#pragma unroll 4
+    for (int y = 0; y < Y; ++y) a += src[(int64_t)y * part_stride];
+    grads[off] += a;
   }
-  // blocks behind the dW blocks (first sample chunk only): the fixed-order sum of the backward kernel's per-workgroup
-  // ActNorm / BatchNorm gradient partials, grads[goff[kw] + j] += sum_b partials[b][kw][j]  (kw = step * 2 + which)
-  if (bx >= n_blocks) {
-    if (by != 0 || red.partials == nullptr || bx - n_blocks >= 2 * red.K) return;
-    float (*rsum)[64] = reinterpret_cast<float (*)[64]>(wg_stage_raw);       // (no static LDS)
-    const int kw = bx - n_blocks, j = threadIdx.x & 63, part = threadIdx.x >> 6;      // 8 parts
-    if ((red.skip_steps >> (kw >> 1)) & 1u) return;           // added already (a BatchNorm step of a batch-statistics sweep)
-    const float* src = red.partials + kw * 64 + j;
-    const int64_t stride = (int64_t)red.K * 128;
-    // (16 loads in flight per thread: with 4 the 512 partials of an N = 65536 sweep were 16 dependent round trips, 11.8 us)
-    float a[16];
-#pragma unroll
-    for (int q = 0; q < 16; ++q) a[q] = 0.0f;
-    int b = part;
-    for (; b + 8 * 15 < red.n_wg; b += 8 * 16) {
-#pragma unroll
-      for (int q = 0; q < 16; ++q) a[q] += src[(int64_t)(b + 8 * q) * stride];
-    }
-    for (; b < red.n_wg; b += 8) a[0] += src[(int64_t)b * stride];
-    rsum[part][j] = (((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]))) +
-                    (((a[8] + a[9]) + (a[10] + a[11])) + ((a[12] + a[13]) + (a[14] + a[15])));
-    __syncthreads();
-    if (part == 0 && j < red.d)
-      grads[red.goff[kw] + j] += ((rsum[0][j] + rsum[1][j]) + (rsum[2][j] + rsum[3][j])) + ((rsum[4][j] + rsum[5][j]) + (rsum[6][j] + rsum[7][j]));
-    return;
-  }
-  float alpha = 1.0f, inv_alpha = 1.0f;          // the gradient-side operands were emitted on the scaled gradient
-  if (gmax != nullptr) tr_grad_scale(__builtin_amdgcn_readfirstlane(*gmax), alpha, inv_alpha);
-  int pi = 0;
-  while (pi + 1 < n_probs && bx >= probs[pi + 1].blk_begin) ++pi;
-  const WgProblem P = probs[pi];
-  const int blk = bx - P.blk_begin;
-  const int m0 = (blk / P.nb) * P.bm, n0 = (blk % P.nb) * P.bn;
-  const int64_t s_begin = (int64_t)by * chunk;       // `chunk` samples per block (a multiple of 32)
-  const int64_t s_end = (s_begin + chunk < np) ? s_begin + chunk : np;
-  // pieces per thread (a 64-row operand: one, repeated by the upper waves) and the wave's tile of the block, see wg_shape()
-#define WG_CASE(BM, BN, ND, NA, TM, TN) \
-  if (P.bm == BM && P.bn == BN) return wgrad_block<ND, NA, TM, TN, (TM * TN < 32)>(P, ws, grads, np, s_begin, s_end, m0, n0, inv_alpha, wg_stage_raw)
-  WG_CASE(256, 256, 2, 2, 8, 4);
-  WG_CASE(256, 128, 2, 1, 4, 4);
-  WG_CASE(256, 64, 2, 1, 2, 4);
-  WG_CASE(128, 256, 1, 2, 4, 4);
-  WG_CASE(64, 256, 1, 2, 4, 2);
-  WG_CASE(128, 128, 1, 1, 4, 2);
-  WG_CASE(128, 64, 1, 1, 2, 2);
-  WG_CASE(64, 128, 1, 1, 2, 2);
-  WG_CASE(64, 64, 1, 1, 2, 1);
-#undef WG_CASE
 }
 // the block of a problem and its 8 waves (wm x wn; every wave TM x TN tiles of 16 x 16 with TM = bm / (16 wm), TN = bn / (16 wn))
 // (cap: largest block edge -- 256 for big batches, where every operand row must be loaded once; 128 for small ones, where the
@@ -1343,126 +1323,19 @@ __global__ void __launch_bounds__(WGS_THREADS) wgrad_safe_kernel(const WgProblem
                                                                  const float* __restrict__ ws, float* __restrict__ grads, int64_t np,
                                                                  int chunk, const unsigned* __restrict__ gmax, int n_blocks,
                                                                  const LiveReduce red, const unsigned* __restrict__ gate) {
-  __shared__ float rsum[4][64];
-  if (gate != nullptr && *gate == 0u) return;        // (the bf16x6 re-run of a repairing trainer's call that did not meet the range)
-  const int bx = blockIdx.x, by = blockIdx.y;
-  if (bx >= n_blocks) {
-    if (by != 0 || red.partials == nullptr || bx - n_blocks >= 2 * red.K) return;
-    const int kw = bx - n_blocks, j = threadIdx.x & 63, part = threadIdx.x >> 6;      // 4 parts
-    if ((red.skip_steps >> (kw >> 1)) & 1u) return;
-    const float* src = red.partials + kw * 64 + j;
-    const int64_t stride = (int64_t)red.K * 128;
-    float a[8];
-#pragma unroll
-    for (int q = 0; q < 8; ++q) a[q] = 0.0f;
-    int b = part;
-    for (; b + 4 * 7 < red.n_wg; b += 4 * 8) {
-#pragma unroll
-      for (int q = 0; q < 8; ++q) a[q] += src[(int64_t)(b + 4 * q) * stride];
-    }
-    for (; b < red.n_wg; b += 4) a[0] += src[(int64_t)b * stride];
-    rsum[part][j] = ((a[0] + a[1]) + (a[2] + a[3])) + ((a[4] + a[5]) + (a[6] + a[7]));
-    __syncthreads();
-    if (part == 0 && j < red.d) grads[red.goff[kw] + j] += (rsum[0][j] + rsum[1][j]) + (rsum[2][j] + rsum[3][j]);
-    return;
-  }
-  float alpha = 1.0f, inv_alpha = 1.0f;          // the gradient-side operands were emitted on the scaled gradient
-  if (gmax != nullptr) tr_grad_scale(__builtin_amdgcn_readfirstlane(*gmax), alpha, inv_alpha);
-  int pi = 0;
-  while (pi + 1 < n_probs && bx >= probs[pi + 1].blk_begin) ++pi;
-  const WgProblem P = probs[pi];
-  const int blk = bx - P.blk_begin;
-  const int m0 = (blk / P.nb) * WGS_BLOCK, n0 = (blk % P.nb) * WGS_BLOCK;
-  const int64_t s_begin = (int64_t)by * chunk;
-  const int64_t s_end = (s_begin + chunk < np) ? s_begin + chunk : np;
-  const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
-  const int wmi = wave >> 1, wni = wave & 1;
-  typedef const f32x4 __attribute__((address_space(1)))* gv4;
-  // this lane's rows (clamped into the operand's own sub-region: a row past it only feeds outputs that are never stored) and its
-  // 8 samples of a 32-sample step: tile g / 2, samples 8 (g & 1) .. + 7
-  unsigned doff[2], aoff[2];
-#pragma unroll
-  for (int x = 0; x < 2; ++x) {
-    const int rd = m0 + 32 * wmi + 16 * x + i, ra = n0 + 32 * wni + 16 * x + i;
-    doff[x] = (unsigned)((g >> 1) * P.d_rows * 16 + (rd < P.d_rows ? rd : P.d_rows - 1) * 16 + 8 * (g & 1));
-    aoff[x] = (unsigned)((g >> 1) * P.a_rows * 16 + (ra < P.a_rows ? ra : P.a_rows - 1) * 16 + 8 * (g & 1));
-  }
-  const float* dbase = ws + P.d_row * np;
-  const float* abase = ws + P.a_row * np;
-  auto fetch = [&](f32x4 (&dv)[2][2], f32x4 (&av)[2][2], int64_t s) {
-    const gv4 dp = (gv4)(dbase + s * P.d_rows), ap = (gv4)(abase + s * P.a_rows);
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      dv[x][0] = dp[doff[x] >> 2]; dv[x][1] = dp[(doff[x] >> 2) + 1];
-      av[x][0] = ap[aoff[x] >> 2]; av[x][1] = ap[(aoff[x] >> 2) + 1];
-    }
-  };
-  const f32x4 zero = {0.f, 0.f, 0.f, 0.f};
-  f32x4 acc[2][2][3];
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y)
-#pragma unroll
-      for (int c = 0; c < 3; ++c) acc[x][y][c] = zero;
-  float bs[2] = {0.0f, 0.0f};
-  const bool own_bias = n0 == 0 && wni == 0;
-  // the products of one f32 product, smallest terms first, and the running sum each goes to (Products<3>)
-  constexpr int PW[6] = {2, 0, 1, 1, 0, 0}, PX[6] = {0, 2, 1, 0, 1, 0}, PA[6] = {2, 2, 2, 1, 1, 0};
-  f32x4 dv[2][2], av[2][2], dn[2][2], an[2][2];
-  fetch(dv, av, s_begin);
-  for (int64_t s = s_begin; s < s_end; s += 32) {
-    fetch(dn, an, s + 32 < s_end ? s + 32 : s);        // one step ahead (past the end: this step again, unused)
-    u32x4 dp[2][3], ap[2][3];
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      wgs_split8(dv[x][0], dv[x][1], dp[x]);
-      wgs_split8(av[x][0], av[x][1], ap[x]);
-      if (own_bias) {
-        const f32x4 u = dv[x][0] + dv[x][1];
-        bs[x] += (u[0] + u[1]) + (u[2] + u[3]);
-      }
-    }
-#pragma unroll
-    for (int pr = 0; pr < 6; ++pr)
-#pragma unroll
-      for (int x = 0; x < 2; ++x)
-#pragma unroll
-        for (int y = 0; y < 2; ++y) acc[x][y][PA[pr]] = wgs_mfma(dp[x][PW[pr]], ap[y][PX[pr]], acc[x][y][PA[pr]]);
-#pragma unroll
-    for (int x = 0; x < 2; ++x) { dv[x][0] = dn[x][0]; dv[x][1] = dn[x][1]; av[x][0] = an[x][0]; av[x][1] = an[x][1]; }
-  }
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) {
-      tr_mfma_drain(acc[x][y][0], acc[x][y][1]);
-      tr_mfma_drain(acc[x][y][2], acc[x][y][2]);
-    }
-  if (own_bias) {      // db[m] = sum over samples of D[m][.]: the four lane groups hold 8 samples each of row i
-#pragma unroll
-    for (int x = 0; x < 2; ++x) {
-      float v = bs[x];
-      v += __shfl_xor(v, 16);
-      v += __shfl_xor(v, 32);
-      const int m = m0 + 32 * wmi + 16 * x + i;
-      if (g == 0 && m < P.M) atomicAdd(grads + P.b_off + m, v * inv_alpha);
-    }
-  }
-  float* C = grads + P.c_off;
-#pragma unroll
-  for (int x = 0; x < 2; ++x)
-#pragma unroll
-    for (int y = 0; y < 2; ++y) {
-      const f32x4 v = acc[x][y][0] + (acc[x][y][1] + acc[x][y][2]);
-      const int n = n0 + 32 * wni + 16 * y + i;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int m = m0 + 32 * wmi + 16 * x + 4 * g + r;
-        if (m < P.M && n < P.N) atomicAdd(C + (size_t)m * P.N + n, v[r] * inv_alpha);
-      }
-    }
+#define GBNF_WG_DET 0
+#include "gbnf_wgrad_safe_kernel.inc"
+#undef GBNF_WG_DET
+}
+// Deterministic mode (see wgrad_det_kernel): chunk `by` stores to part[by][..], wgrad_det_reduce_kernel follows.
+__global__ void __launch_bounds__(WGS_THREADS) wgrad_safe_det_kernel(const WgProblem* __restrict__ probs, int n_probs,
+                                                                     const float* __restrict__ ws, float* __restrict__ grads, int64_t np,
+                                                                     int chunk, const unsigned* __restrict__ gmax, int n_blocks,
+                                                                     const LiveReduce red, const unsigned* __restrict__ gate,
+                                                                     float* __restrict__ part, int64_t part_stride) {
+#define GBNF_WG_DET 1
+#include "gbnf_wgrad_safe_kernel.inc"
+#undef GBNF_WG_DET
 }
 
 // ---- batch-statistics BatchNorm (models/layers.py:338-358 in train mode): the pieces that need the whole batch ----------
@@ -1644,6 +1517,7 @@ struct gbnf_trainer {
   unsigned* gmax_dev = nullptr;        // bits of the largest |upstream gradient| of the current backward call (gradient scaling)
   float* bn_part_dev = nullptr;        // [2][64 slots][BN_CHUNKS]: chunk sums of the batch statistics (bn_stats_part_kernel)
   int batch_stats = 0;                 // BatchNorm on batch statistics (the reference's train() mode)
+  int deterministic = 0;               // ordered weight-gradient flush (gbnf_trainer_set_deterministic); calls on the per-step kernels are refused
   std::vector<int> has_norm;           // per step
   // The step ranges of a batch-statistics sweep: a step with a norm needs the statistics of the whole batch in front of it, so a range
   // starts at step 0 and at every step that has one.  `single_steps`: ranges of one step each, the walk of the per-step kernels.
@@ -2032,6 +1906,8 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
       e = hipFuncSetAttribute(fns[k], hipFuncAttributeMaxDynamicSharedMemorySize, TR_LDS_BYTES);
     if (e == hipSuccess)
       e = hipFuncSetAttribute((const void*)wgrad_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_BYTES);
+    if (e == hipSuccess)
+      e = hipFuncSetAttribute((const void*)wgrad_det_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)WG_LDS_BYTES);
   }
   if (e != hipSuccess) {
     gbnf_trainer_destroy(t);
@@ -2060,6 +1936,55 @@ int gbnf_trainer_create_mode(const gbnf_flow_desc* desc, int32_t math_mode, gbnf
   *out = t;
   return GBNF_OK;
 }
+
+}  // extern "C"
+
+// samples per block of a weight-gradient launch: the largest power of two in [lo, hi] that still leaves `min_blocks` blocks
+static int wgrad_chunk(int blocks, int64_t np, int lo, int hi, int min_blocks) {
+  int chunk = lo;
+  while (chunk < hi && (int64_t)blocks * (np / (2 * chunk)) >= min_blocks) chunk *= 2;
+  return chunk;
+}
+
+// The weight-gradient launch of the chained backward at one batch size: a function of the trainer's problems and np, nothing else
+// (deterministic mode sizes its partials by Y and its sums run over Y terms).
+struct WgPlan {
+  const WgProblem* probs;
+  int blocks, chunk, Y;      // dW blocks, samples per block, sample chunks (grid.y)
+};
+static WgPlan wgrad_plan(const gbnf_trainer* t, const TrainLayout& lay) {
+  WgPlan w{};
+  if (t->math == GBNF_MATH_BF16X6) {
+    // 64 x 64 blocks of 4 waves: samples per block so that ~4 workgroups per CU remain (the threshold of 1024 is reasoned from the
+    // 256 CUs, not measured)
+    w.probs = t->probs_safe_dev; w.blocks = t->wg_blocks_safe;
+    w.chunk = wgrad_chunk(w.blocks, lay.np, 128, 2048, 1024);
+  } else {
+    // samples per block: the largest power of two in [128, 2048] that still leaves ~a block per CU (>= 240 blocks; one 128 KB
+    // workgroup of 8 waves per CU).  Measured (MINIBOONE step, 15 blocks per chunk): N = 65536 with 1024 / 2048 / 4096 samples
+    // per block 64.9 / 66.7 / 63.8 M samples/s, N = 16384 with 512 / 1024 / 2048: 46.1 / 49.2 / 41.2 M, N = 4096 with 128 / 256 /
+    // 512: 16.5 / 19.1 / 18.8 M; every further chunk adds a bm x bn tile of float atomics per block of dW, every chunk less leaves
+    // CUs idle.
+    // (up to 16 k rows the operands fit the L2s: blocks of at most 128 x 128 -- twice the workgroups)
+    const bool small = lay.np <= 16384 && t->probs_small_dev != nullptr;
+    w.probs = small ? t->probs_small_dev : t->probs_dev;
+    w.blocks = small ? t->wg_blocks_small : t->wg_blocks;
+    w.chunk = wgrad_chunk(w.blocks, lay.np, 128, 2048, 240);
+  }
+  w.Y = (int)((lay.np + w.chunk - 1) / w.chunk);
+  return w;
+}
+
+// The backward workspace of one (non-repairing) trainer.  Deterministic mode appends the weight-gradient partials [Y][grad_floats]
+// behind the gradient state (only a trainer with a chained backward ever uses them: every other call is refused in that mode).
+static int64_t det_partials_off(const TrainLayout& lay) { return lay.workspace_bytes() / 4; }
+static int64_t trainer_workspace_bytes(const gbnf_trainer* t, const TrainLayout& lay) {
+  int64_t bytes = lay.workspace_bytes();
+  if (t->deterministic && lay.n > 0 && live_blob_has_backward(t->live)) bytes += (int64_t)wgrad_plan(t, lay).Y * t->grad_floats * 4;
+  return bytes;
+}
+
+extern "C" {
 
 int gbnf_trainer_destroy(gbnf_trainer* t) {
   if (t == nullptr) return GBNF_OK;
@@ -2099,7 +2024,7 @@ int gbnf_trainer_workspace_bytes(const gbnf_trainer* t, int64_t n, int64_t* byte
     *bytes = a > b ? a : b;
     return GBNF_OK;
   }
-  *bytes = t->lay.at(n).workspace_bytes();
+  *bytes = trainer_workspace_bytes(t, t->lay.at(n));
   return GBNF_OK;
 }
 
@@ -2162,6 +2087,22 @@ int gbnf_trainer_set_batch_stats(gbnf_trainer* t, int32_t on) {
         return fail(GBNF_ERR_INVALID, "gbnf_trainer_set_batch_stats: step %d has a BatchNorm but no batch-statistics buffers "
                     "(gbnf_trainer_bind_batch_stats)", (int)k);
   t->batch_stats = on ? 1 : 0;
+  return GBNF_OK;
+}
+
+int gbnf_trainer_set_deterministic(gbnf_trainer* t, int32_t on) {
+  if (!t) return fail(GBNF_ERR_INVALID, "gbnf_trainer_set_deterministic: trainer is null");
+  if (t->rep.f) {
+    t->rep.f->deterministic = on ? 1 : 0;
+    t->rep.s->deterministic = on ? 1 : 0;
+  }
+  t->deterministic = on ? 1 : 0;
+  return GBNF_OK;
+}
+
+int gbnf_trainer_get_deterministic(const gbnf_trainer* t, int32_t* on) {
+  if (!t || !on) return fail(GBNF_ERR_INVALID, "gbnf_trainer_get_deterministic: null argument");
+  *on = t->deterministic;
   return GBNF_OK;
 }
 
@@ -2241,6 +2182,29 @@ static int refuse_range_safe(const char* fn, Chain why, int64_t n) {
   return fail(GBNF_ERR_INVALID, "%s: batch-statistics mode needs every BatchNorm step's buffers (gbnf_trainer_bind_batch_stats)", fn);
 }
 
+// Deterministic mode: a backward call that would run the per-step kernels (float atomics for the ActNorm / BatchNorm and weight
+// gradients) is refused before anything is launched.  traced: the call comes with the forward call's trace (a range-safe trainer
+// runs the traced pair on its own buffer either way).  Also asked by the one-call steps, which would launch a forward first.
+int gbnf::trainer_deterministic_check(const gbnf_trainer* t, int64_t n, bool traced, const char* fn) {
+  if (!t || !t->deterministic) return GBNF_OK;
+  if (t->rep.f) {
+    const int rc = trainer_deterministic_check(t->rep.f, n, traced, fn);
+    return rc ? rc : trainer_deterministic_check(t->rep.s, n, traced, fn);
+  }
+  const TrainLayout lay = t->lay.at(n);
+  static const float some = 0.0f;       // (a stand-in: only whether there is a trace matters)
+  const bool safe = t->math == GBNF_MATH_BF16X6;
+  const Chain why = chained_or_why(t, lay, /*forward=*/false, (traced || safe) ? &some : nullptr, nullptr);
+  if (why == Chain::Yes || safe) return GBNF_OK;          // (a range-safe trainer has no per-step kernels: its own refusals stand)
+  const char* reason = why == Chain::NoSweep   ? "no register-chained backward sweep covers this geometry (more than 24 steps, or a coupling net no "
+                                                 "training variant is compiled for)"
+                       : why == Chain::NoTrace ? "an f16x3 call without the forward call's trace"
+                       : why == Chain::Offsets32 ? "the batch exceeds the chained sweep's 32-bit operand offsets"
+                                                 : "batch-statistics buffers are not bound for every BatchNorm step";
+  return fail(GBNF_ERR_UNSUPPORTED, "%s: deterministic mode is on and this call would run the per-step kernels, which add gradients with "
+              "unordered float atomics: %s", fn, reason);
+}
+
 // ---- BatchNorm on batch statistics (the reference's train() mode, models/layers.py:338-346): one launch per step range ---------------
 // Forward: a sweep is cut in front of every BatchNorm step -- its statistics need the whole batch: one column reduction of the parked
 // state (bn_stats_kernel) -- and the state is parked in HBM in slot layout between the launches (TrainLayout::parked_off: the last
@@ -2278,13 +2242,6 @@ static int bn_backward_walk(const gbnf_trainer* t, const std::vector<StepRange>&
 
 static void launch_prep(const gbnf_trainer* t, hipStream_t s) {
   hipLaunchKernelGGL(prep_kernel, dim3((unsigned)t->prep_blocks), dim3(64), 0, s, (const PrepProblem*)t->prep_dev, t->n_prep, t->frag_dev);
-}
-
-// samples per block of a weight-gradient launch: the largest power of two in [lo, hi] that still leaves `min_blocks` blocks
-static int wgrad_chunk(int blocks, int64_t np, int lo, int hi, int min_blocks) {
-  int chunk = lo;
-  while (chunk < hi && (int64_t)blocks * (np / (2 * chunk)) >= min_blocks) chunk *= 2;
-  return chunk;
 }
 
 // ---- forward ---------------------------------------------------------------------------------------------------------
@@ -2391,6 +2348,12 @@ extern "C" int gbnf_trainer_forward(const gbnf_trainer* t, const float* x, int64
 static int backward_repairing(const gbnf_trainer* t, const float* x, int64_t n, const float* trace, const float* g_z, const float* g_ldj,
                               float* g_x, float* grads, void* workspace, int64_t workspace_bytes, hipStream_t s) {
   const int64_t ng = t->grad_floats, nx = g_x ? n * (int64_t)t->d : 0;
+  {
+    int64_t need = 0;
+    gbnf_trainer_workspace_bytes(t, n, &need);
+    if (workspace_bytes < need)
+      return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: workspace too small: %lld bytes < %lld", (long long)workspace_bytes, (long long)need);
+  }
   if (t->rep.scratch_floats < 2 * ng + 2 * nx) {
     if (t->rep.scratch) (void)hipFree(t->rep.scratch);
     t->rep.scratch = nullptr; t->rep.scratch_floats = 0;
@@ -2423,28 +2386,29 @@ static int backward_repairing(const gbnf_trainer* t, const float* x, int64_t n, 
 
 // The weight gradients of the chained backward, from the operand workspace behind the trace (+ 2 K blocks: the sums of the backward
 // kernel's parameter-gradient partials ride in this launch)
-static int wgrad_chained(const gbnf_trainer* t, const TrainLayout& lay, const float* acts, float* grads, const LiveReduce& red, hipStream_t s) {
-  if (t->math == GBNF_MATH_BF16X6) {
-    // 64 x 64 blocks of 4 waves: samples per block so that ~4 workgroups per CU remain (the threshold of 1024 is reasoned from the
-    // 256 CUs, not measured)
-    const int chunk = wgrad_chunk(t->wg_blocks_safe, lay.np, 128, 2048, 1024);
-    const dim3 grid((unsigned)(t->wg_blocks_safe + 2 * red.K), (unsigned)((lay.np + chunk - 1) / chunk));
-    hipLaunchKernelGGL(wgrad_safe_kernel, grid, dim3(WGS_THREADS), 0, s, (const WgProblem*)t->probs_safe_dev, t->n_probs, acts, grads, lay.np,
-                       chunk, (const unsigned*)t->gmax_dev, t->wg_blocks_safe, red, t->gate);
+static int wgrad_chained(const gbnf_trainer* t, const TrainLayout& lay, const float* acts, float* grads, const LiveReduce& red, float* part,
+                         hipStream_t s) {
+  const WgPlan w = wgrad_plan(t, lay);
+  const bool safe = t->math == GBNF_MATH_BF16X6;
+  const dim3 grid((unsigned)(w.blocks + 2 * red.K), (unsigned)w.Y);
+  const int64_t stride = t->grad_floats;
+  if (!t->deterministic) {
+    if (safe)
+      hipLaunchKernelGGL(wgrad_safe_kernel, grid, dim3(WGS_THREADS), 0, s, w.probs, t->n_probs, acts, grads, lay.np, w.chunk,
+                         (const unsigned*)t->gmax_dev, w.blocks, red, t->gate);
+    else
+      hipLaunchKernelGGL(wgrad_kernel, grid, dim3(WG_THREADS), WG_LDS_BYTES, s, w.probs, t->n_probs, acts, grads, lay.np, w.chunk,
+                         (const unsigned*)t->gmax_dev, w.blocks, red);
   } else {
-    // samples per block: the largest power of two in [128, 2048] that still leaves ~a block per CU (>= 240 blocks; one 128 KB
-    // workgroup of 8 waves per CU).  Measured (MINIBOONE step, 15 blocks per chunk): N = 65536 with 1024 / 2048 / 4096 samples
-    // per block 64.9 / 66.7 / 63.8 M samples/s, N = 16384 with 512 / 1024 / 2048: 46.1 / 49.2 / 41.2 M, N = 4096 with 128 / 256 /
-    // 512: 16.5 / 19.1 / 18.8 M; every further chunk adds a bm x bn tile of float atomics per block of dW, every chunk less leaves
-    // CUs idle.
-    // (up to 16 k rows the operands fit the L2s: blocks of at most 128 x 128 -- twice the workgroups)
-    const bool small = lay.np <= 16384 && t->probs_small_dev != nullptr;
-    const WgProblem* probs = small ? t->probs_small_dev : t->probs_dev;
-    const int blocks = small ? t->wg_blocks_small : t->wg_blocks;
-    const int chunk = wgrad_chunk(blocks, lay.np, 128, 2048, 240);
-    const dim3 grid((unsigned)(blocks + 2 * red.K), (unsigned)((lay.np + chunk - 1) / chunk));
-    hipLaunchKernelGGL(wgrad_kernel, grid, dim3(WG_THREADS), WG_LDS_BYTES, s, probs, t->n_probs, acts, grads, lay.np, chunk,
-                       (const unsigned*)t->gmax_dev, blocks, red);
+    // every chunk's tiles to part[chunk][..], then their sums in chunk order into grads
+    if (safe)
+      hipLaunchKernelGGL(wgrad_safe_det_kernel, grid, dim3(WGS_THREADS), 0, s, w.probs, t->n_probs, acts, grads, lay.np, w.chunk,
+                         (const unsigned*)t->gmax_dev, w.blocks, red, t->gate, part, stride);
+    else
+      hipLaunchKernelGGL(wgrad_det_kernel, grid, dim3(WG_THREADS), WG_LDS_BYTES, s, w.probs, t->n_probs, acts, grads, lay.np, w.chunk,
+                         (const unsigned*)t->gmax_dev, w.blocks, red, part, stride);
+    hipLaunchKernelGGL(wgrad_det_reduce_kernel, dim3(32u, (unsigned)t->n_probs), dim3(256), 0, s, w.probs, (const float*)part, stride, w.Y, grads,
+                       t->gate);
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward launch: %s", hipGetErrorString(e));
@@ -2454,7 +2418,7 @@ static int wgrad_chained(const gbnf_trainer* t, const TrainLayout& lay, const fl
 // The register-chained backward sweep on what the forward sweep saved behind the trace, then the weight gradients from the operand
 // workspace that now lives there too
 static int backward_chained(const gbnf_trainer* t, const TrainLayout& lay, float* trace, const float* g_z, const float* g_ldj, float* g_x,
-                            float* grads, float* gstate, hipStream_t s) {
+                            float* grads, float* gstate, float* part, hipStream_t s) {
   const float* acts = trace + lay.acts_off();
   LiveReduce red{};
   t->last_bwd_ranges = 1;
@@ -2483,7 +2447,7 @@ static int backward_chained(const gbnf_trainer* t, const TrainLayout& lay, float
     if (rc) return rc;
     red.skip_steps = done;
   }
-  return wgrad_chained(t, lay, acts, grads, red, s);
+  return wgrad_chained(t, lay, acts, grads, red, part, s);
 }
 
 static int backward_per_step(const gbnf_trainer* t, const TrainLayout& lay, const float* x, const float* trace, const float* g_z,
@@ -2532,11 +2496,12 @@ int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, cons
   if (n == 0) return GBNF_OK;
   if (!x || !grads || !workspace) return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: x / grads / workspace is null");
   hipStream_t s = (hipStream_t)stream;
+  if (const int rc = trainer_deterministic_check(t, n, trace != nullptr, "gbnf_trainer_backward")) return rc;      // (nothing launched yet)
   if (t->rep.f) return backward_repairing(t, x, n, trace, g_z, g_ldj, g_x, grads, workspace, workspace_bytes, s);
   const TrainLayout lay = t->lay.at(n);
-  if (workspace_bytes < lay.workspace_bytes())
-    return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: workspace of %lld bytes < %lld", (long long)workspace_bytes,
-                (long long)lay.workspace_bytes());
+  if (workspace_bytes < trainer_workspace_bytes(t, lay))
+    return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward: workspace too small: %lld bytes < %lld%s", (long long)workspace_bytes,
+                (long long)trainer_workspace_bytes(t, lay), t->deterministic ? " (deterministic mode needs the weight-gradient partials)" : "");
   const bool safe = t->math == GBNF_MATH_BF16X6;
   if (safe && trace == nullptr) {      // without a trace: the traced pair, the forward into the trainer's own buffer
     float* own_trace = nullptr;
@@ -2556,7 +2521,8 @@ int gbnf_trainer_backward(const gbnf_trainer* t, const float* x, int64_t n, cons
   }
   const Chain why = chained_or_why(t, lay, /*forward=*/false, trace, nullptr);
   // (the sweep writes the gradient-side operands behind the states: `trace` is const for the states only, include/gbnf.h)
-  if (why == Chain::Yes) return backward_chained(t, lay, const_cast<float*>(trace), g_z, g_ldj, g_x, grads, gstate, s);
+  if (why == Chain::Yes)
+    return backward_chained(t, lay, const_cast<float*>(trace), g_z, g_ldj, g_x, grads, gstate, (float*)workspace + det_partials_off(lay), s);
   if (safe) return refuse_range_safe("gbnf_trainer_backward", why, n);
   return backward_per_step(t, lay, x, trace, g_z, g_ldj, g_x, grads, (float*)workspace, gstate, s);
 }

@@ -342,6 +342,11 @@ class BoostedImageFlow(nn.Module):
         if args.component_type != "glow":
             raise NotImplementedError("image components are Glow (models/boosted_flow.py:44-50 builds nothing else for images)")
         self.args = args
+        # deterministic mode (BoostedFlow: args.deterministic / env GBNF_DETERMINISTIC) orders the tabular trainer's sums only.  The
+        # flag is kept and the module builds and evaluates as ever; the first TRAINING call is refused (native_trainer) rather than
+        # served by the image trainer's float atomics.
+        from .boosted_flow import deterministic_from
+        self.deterministic = deterministic_from(args)
         self.num_flows, self.z_size = args.num_flows, args.z_size
         self.density_evaluation = args.density_evaluation
         self.all_trained, self.component_type = False, args.component_type
@@ -421,6 +426,9 @@ class BoostedImageFlow(nn.Module):
         """(native.NativeImageTrainer bound to component c's live parameter storage, bindings), cached like ``native_flow`` and keyed
         on the tensors' addresses (not their versions: an optimiser's in-place update needs no new trainer).  bindings: one
         (path, parameter | InvertibleConv1x1 module, persistent composed matrix | None, pixels of the level) per bound tensor."""
+        if self.deterministic:
+            raise native.GbnfError("deterministic mode is on and the image trainer has no ordered path: its weight gradients and "
+                                   "log-det sums are added with unordered float atomics (gbnf_image_trainer_backward)")
         flow = self.flows[c]
         params, buffers, perms, actnorms = self._component_tensors(c)
         if not all(bool(m.inited) for m in actnorms):

@@ -35,6 +35,7 @@ ABI_SYMBOLS = (
     "gbnf_trainer_grad_floats", "gbnf_trainer_workspace_bytes", "gbnf_trainer_backward", "gbnf_trainer_trace_floats",
     "gbnf_trainer_bind_batch_stats", "gbnf_trainer_set_batch_stats", "gbnf_trainer_create_mode", "gbnf_trainer_repair_count",
     "gbnf_trainer_apply_update", "gbnf_trainer_step_workspace_bytes", "gbnf_trainer_nll_step",
+    "gbnf_trainer_set_deterministic", "gbnf_trainer_get_deterministic",
     "gbnf_image_flow_create", "gbnf_image_flow_destroy", "gbnf_image_flow_info", "gbnf_image_flow_workspace_bytes",
     "gbnf_image_flow_forward", "gbnf_image_flow_prior", "gbnf_image_flow_eps_floats", "gbnf_image_flow_inverse",
     "gbnf_image_flow_numerics", "gbnf_image_flow_repair_counts", "gbnf_image_flow_create_mode", "gbnf_image_flow_actnorm_stats",
@@ -196,6 +197,8 @@ def lib():
     L.gbnf_trainer_trace_floats.argtypes = [vp, i64, C.POINTER(i64)]
     L.gbnf_trainer_bind_batch_stats.argtypes = [vp, i32, vp, vp]
     L.gbnf_trainer_set_batch_stats.argtypes = [vp, i32]
+    L.gbnf_trainer_set_deterministic.argtypes = [vp, i32]
+    L.gbnf_trainer_get_deterministic.argtypes = [vp, C.POINTER(i32)]
     L.gbnf_trainer_grad_floats.argtypes = [vp, C.POINTER(i64)]
     L.gbnf_trainer_workspace_bytes.argtypes = [vp, i64, C.POINTER(i64)]
     L.gbnf_trainer_backward.argtypes = [vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, vp]
@@ -995,11 +998,16 @@ class NativeTrainer:
     ``math``: "f16x3" (default: the fast sweeps, operands beyond +-65504 saturate and are counted) or "bf16x6" (range-safe: f32
     range in every sweep, the re-pack and the weight gradients) or "repair" (f16x3 first; a call that met the range is re-run in
     bf16x6 within the same call, decided on the device: GBNF_MATH_DEFAULT) -- gbnf_trainer_create_mode.  A geometry without the
-    kernels of the mode raises GbnfError; nothing falls back."""
+    kernels of the mode raises GbnfError; nothing falls back.
+
+    ``deterministic``: the weight gradients are flushed as per-chunk partials and added in a fixed order
+    (gbnf_trainer_set_deterministic): ``backward``, ``nll_step`` and ``boosted_nll_step`` are bit-reproducible for fixed inputs,
+    parameters and batch size.  A call that would run the per-step kernels (unordered float atomics) raises GbnfError with the
+    library's reason.  The workspaces grow: every helper asks the library for the size at every call."""
 
     TRAIN_MATH = {"f16x3": MATH["f16x3"], "bf16x6": MATH["bf16x6"], "repair": MATH["default"]}
 
-    def __init__(self, dev_spec, math="f16x3"):
+    def __init__(self, dev_spec, math="f16x3", deterministic=False):
         import torch
         if math not in self.TRAIN_MATH:
             raise GbnfError(f"NativeTrainer: math must be one of {sorted(self.TRAIN_MATH)}, got {math!r}")
@@ -1096,9 +1104,24 @@ class NativeTrainer:
         self._step_ws = None
         self._boost_ws = None
         self.device = self._tensors[0].device
+        self._deterministic = False
+        if deterministic:
+            self.deterministic = True
 
     def key(self):
         return tuple(t.data_ptr() for t in self._tensors)
+
+    @property
+    def deterministic(self):
+        """Deterministic mode of the trainer (gbnf_trainer_get_deterministic / gbnf_trainer_set_deterministic)."""
+        on = C.c_int32(0)
+        _check(lib().gbnf_trainer_get_deterministic(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    @deterministic.setter
+    def deterministic(self, on):
+        _check(lib().gbnf_trainer_set_deterministic(self.handle, 1 if on else 0))
+        self._deterministic = bool(on)
 
     def _hyper(self, state, lr, weight_decay=0.0, max_grad_norm=0.0, betas=(0.9, 0.999), eps=1e-8, bn_momentum=-1.0):
         """The gbnf_opt_hyper of the NEXT update of ``state`` (its ``step`` + 1)."""

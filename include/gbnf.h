@@ -444,16 +444,18 @@ int gbnf_trainer_set_batch_stats(gbnf_trainer* trainer, int32_t on);
  *   glow:    [actnorm bias (d)] [actnorm logs (d)]  then per Linear of the block:   [weight (out*in)] [bias (out)]
  *   realnvp: [bn log_gamma (d)] [bn beta (d)]  (left zero without batch norm)  then t_net's Linears, then s_net's. */
 int gbnf_trainer_grad_floats(const gbnf_trainer* trainer, int64_t* n_floats);
-/* Bytes of caller-owned DEVICE scratch one backward call over n samples needs. */
+/* Bytes of caller-owned DEVICE scratch one backward call over n samples needs (larger in deterministic mode, below: ask again
+ * after switching it). */
 int gbnf_trainer_workspace_bytes(const gbnf_trainer* trainer, int64_t n, int64_t* bytes);
 
 /* Backward of (z, ldj) = flows[c](x): given g_z = dL/dz (n,d) and g_ldj = dL/dldj (n,) (either may be NULL = zero),
  * ACCUMULATES dL/dparameters into `grads` (the caller zeroes it; layout above) and writes dL/dx to g_x (n,d) unless
  * NULL.  `trace` is the forward call's trace buffer or NULL.  With it, a flow on the register-chained kernels (above)
  * recomputes nothing: the backward kernel chains W3^T -> W2^T -> W1^T on the saved activations, ActNorm / BatchNorm
- * gradients are summed per workgroup and added in a fixed order (bit-identical from run to run; the weight gradients still
- * use float atomics across sample blocks).  Other flows recompute the coupling nets' activations from the trace, and with
- * NULL the whole forward sweep from x.
+ * gradients are summed per workgroup and added in a fixed order (bit-identical from run to run).  By default the weight
+ * gradients are added with float atomics across sample blocks: their last bits depend on the order; deterministic mode
+ * (below): every sample block stores its partial and the partials are added in block order.  Other flows recompute the
+ * coupling nets' activations from the trace, and with NULL the whole forward sweep from x.
  * Batch-statistics mode (gbnf_trainer_set_batch_stats): the BatchNorm entries of `grads` (log_gamma, beta of every step) MUST
  * be zero on entry -- the correction for the statistics' dependence on every sample reads THIS call's two batch sums from
  * them; accumulate several calls by adding up separately zeroed buffers (what the Python mirror does: a fresh buffer per
@@ -461,6 +463,27 @@ int gbnf_trainer_workspace_bytes(const gbnf_trainer* trainer, int64_t n, int64_t
 int gbnf_trainer_backward(const gbnf_trainer* trainer, const float* x, int64_t n, const float* trace, const float* g_z,
                           const float* g_ldj, float* g_x, float* grads, void* workspace, int64_t workspace_bytes,
                           void* stream);
+
+/* Deterministic mode, a property of the trainer like gbnf_trainer_set_batch_stats (off at creation; the default path,
+ * its kernels and its results do not change).  While it is on, for a fixed trainer, fixed inputs, fixed parameter
+ * values, a fixed n and fixed tuning keys, gbnf_trainer_backward, gbnf_trainer_nll_step and gbnf_boosted_nll_step write
+ * bit-identical `grads`, g_x, parameters, exp_avg, exp_avg_sq, stats_dev and rows_out on every call, in every math mode
+ * (a repairing trainer decides from the data, so its decision repeats too).  How: sample chunk y of a weight-gradient
+ * block stores its dW tile and db rows to partials[y][..] in the backward workspace (plain stores, no atomics), and a
+ * second launch adds the Y partials of every entry in chunk order into `grads`; Y is a function of the trainer's layer
+ * shapes and of n only.  Everything else in those calls is ordered already.  Cost: Y x gbnf_trainer_grad_floats floats
+ * of workspace -- gbnf_trainer_workspace_bytes, gbnf_trainer_step_workspace_bytes and gbnf_boosted_step_workspace_bytes
+ * report the larger sizes while the mode is on, and a workspace sized before switching it on is refused with
+ * GBNF_ERR_INVALID ("workspace too small"), never overrun. Limits: a call that would run the per-step kernels, whose
+ * gradients are added with unordered float atomics -- a flow of more than 24 steps, a two-block ResidualNet wider than
+ * 256, any geometry without a register-chained backward sweep, an f16x3 call without the forward call's trace --
+ * returns GBNF_ERR_UNSUPPORTED with the reason and launches nothing.  (A GBNF_MATH_BF16X6 trainer has no per-step
+ * kernels: a call it cannot serve is refused as ever, with its own reason, behind the launch that finds the scale of
+ * the upstream gradient; it never gives an unordered result either.)  Nothing is promised across different n, tuning
+ * keys, math modes or builds.  The image trainer (gbnf_image_trainer_*) has no such mode: its weight gradients and
+ * log-det sums stay as documented there. */
+int gbnf_trainer_set_deterministic(gbnf_trainer* trainer, int32_t on);
+int gbnf_trainer_get_deterministic(const gbnf_trainer* trainer, int32_t* on);
 
 /* ---- the rest of the step: loss seed, gradient-norm clip and the optimiser, on the device -------------------------------
  * Between and behind the two calls above the reference's driver runs eager PyTorch: the NLL and its autograd seed, clip_grad_norm_,

@@ -34,11 +34,14 @@ def main():
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--rounds", type=int, default=5)
     ap.add_argument("--components", type=int, default=4)
+    ap.add_argument("--deterministic", action="store_true", help="time the same step in deterministic mode (ordered weight-gradient flush)")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     torch.manual_seed(0)
     d, h, K, C = 43, 215, 5, a.components
-    m = BoostedFlow(_args("glow", d, h, K, C, dev)).to(dev)
+    margs = _args("glow", d, h, K, C, dev)
+    margs.deterministic = a.deterministic
+    m = BoostedFlow(margs).to(dev)
     x = torch.randn(a.batch, d, device=dev)
     m.train()
     with torch.no_grad():

@@ -80,6 +80,7 @@ def main():
                     help="the trainer's math mode (native.NativeTrainer): the saturating f16x3 sweeps, the range-safe bf16x6 ones, or f16x3 with the same-call bf16x6 re-run")
     ap.add_argument("--out-of-range-rows", type=int, default=0, help="put this many rows of the batch beyond the fp16 range (3e5): the cost of a repaired step")
     ap.add_argument("--no-torch-legs", action="store_true", help="skip the eager-PyTorch GPU leg (profiler runs: thousands of tiny dispatches)")
+    ap.add_argument("--deterministic", action="store_true", help="time the same step in deterministic mode (ordered weight-gradient flush)")
     a = ap.parse_args()
     cfg = CONFIGS[a.config]
     from gbnf_amd import native, synth
@@ -94,7 +95,7 @@ def main():
             if st.get("bn") is not None:
                 st["bn"]["batch_mean"] = torch.zeros(cfg["d"], device=dev)
                 st["bn"]["batch_var"] = torch.zeros(cfg["d"], device=dev)
-    tr = native.NativeTrainer(dv, math=a.math)
+    tr = native.NativeTrainer(dv, math=a.math, deterministic=a.deterministic)
     if a.batch_stats:
         tr.set_batch_stats(True)
     xh = synth.synth_batch(a.batch, cfg["d"], seed=0)
