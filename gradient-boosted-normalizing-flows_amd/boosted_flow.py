@@ -347,17 +347,27 @@ class _FlowFunction(torch.autograd.Function):
 def deterministic_from(args, env=None):
     """The deterministic-mode flag of a module: ``args.deterministic`` (a bool, or None / absent = not given), else the environment
     variable GBNF_DETERMINISTIC ("1" / "0"; unset or empty = off).  Anything else raises ValueError."""
-    given = getattr(args, "deterministic", None)
+    return _flag_from(args, env, "deterministic", "GBNF_DETERMINISTIC")
+
+
+def image_deterministic_from(args, env=None):
+    """The deterministic-mode flag of an IMAGE module's trainers (image_glow.BoostedImageFlow.image_deterministic):
+    ``args.image_deterministic``, else the environment variable GBNF_IMAGE_DETERMINISTIC; the rules of ``deterministic_from``."""
+    return _flag_from(args, env, "image_deterministic", "GBNF_IMAGE_DETERMINISTIC")
+
+
+def _flag_from(args, env, attr, var):
+    given = getattr(args, attr, None)
     if given is not None:
         if not isinstance(given, (bool, int)) or given not in (0, 1, True, False):
-            raise ValueError(f"deterministic must be a bool, got {given!r}")
+            raise ValueError(f"{attr} must be a bool, got {given!r}")
         return bool(given)
-    text = (os.environ if env is None else env).get("GBNF_DETERMINISTIC", "")
+    text = (os.environ if env is None else env).get(var, "")
     if text in ("", "0"):
         return False
     if text == "1":
         return True
-    raise ValueError(f"GBNF_DETERMINISTIC must be 0 or 1, got {text!r}")
+    raise ValueError(f"{var} must be 0 or 1, got {text!r}")
 
 
 class BoostedFlow(nn.Module):

@@ -221,7 +221,8 @@ def main(argv=None):
     imgt_o, imgt_src = os.path.join(OBJ, "gbnf_image_train.o"), os.path.join(HERE, "gbnf_image_train.hip")
     objs.append(imgt_o)
     imgt_hdr = os.path.join(HERE, "gbnf_image_train.h")
-    if args.force or not newer(imgt_o, [imgt_src, imgt_hdr, os.path.join(HERE, "gbnf_image_net.h"), hdr[2], hdr[3]]):
+    if args.force or not newer(imgt_o, [imgt_src, imgt_hdr, os.path.join(HERE, "gbnf_image_wgrad_kernel.inc"), os.path.join(HERE, "gbnf_image_net.h"),
+                                        hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", imgt_src, "-o", imgt_o])
     # one image training step in one call (1x1 log-dets and LU chain, loss seed, top prior; the update is gbnf_opt.hip's): gbnf_image_opt.hip
     imgo_o, imgo_src = os.path.join(OBJ, "gbnf_image_opt.o"), os.path.join(HERE, "gbnf_image_opt.hip")

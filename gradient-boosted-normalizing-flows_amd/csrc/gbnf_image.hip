@@ -263,7 +263,7 @@ __device__ __forceinline__ void img_conv_body(const ConvLaunch& p, const int n, 
           const float h0 = acc[2 * q] + bias[co], h1 = acc[2 * q + 1] + bias[co + 1];
           float* zp = st + (int64_t)j * H * W + pix;
           const float z2 = *zp;
-          if constexpr (EPI == EPI_COUPLE_AFFINE) {
+          if constexpr (EPI == EPI_COUPLE_AFFINE || EPI == EPI_COUPLE_AFFINE_ORD) {
             const float e = __expf(-(h1 + 2.0f));                   // scale = sigmoid(raw + 2), models/glow.py:333
             const float sc = 1.0f / (1.0f + e);
             *zp = (z2 + h0) * sc;                                   // models/glow.py:334-335
@@ -341,6 +341,24 @@ __device__ __forceinline__ void img_conv_body(const ConvLaunch& p, const int n, 
     for (int m = 1; m < 64; m <<= 1) ld += __shfl_xor(ld, m);
     if (lane == 0) atomicAdd(p.ldj + n, ld);
   }
+  // the ordered forms: every wave of every workgroup reaches this point and stores its partial (zero if it ran no epilogue) to its
+  // slot of image n; img_ldj_reduce_kernel adds the slots in slot order
+  if constexpr (EPI == EPI_COUPLE_AFFINE_ORD || EPI == EPI_SPLIT_ORD) {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) ld += __shfl_xor(ld, m);
+    const int slots = p.n_strips * p.o_split * IMG_WAVES;
+    if (lane == 0) p.ldj[(int64_t)n * slots + (strip * p.o_split + osp) * IMG_WAVES + wave] = ld;
+  }
+}
+
+// ldj[i] += the sum of image i's log-det slots of one EPI_*_ORD launch, in slot order
+__global__ void __launch_bounds__(256) img_ldj_reduce_kernel(const float* __restrict__ part, int slots, float* __restrict__ ldj, int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float* src = part + i * slots;
+  float s = 0.0f;
+  for (int k = 0; k < slots; ++k) s += src[k];
+  ldj[i] += s;
 }
 
 template <int EPI, int PT, int KS>
@@ -1059,6 +1077,14 @@ struct Recorder {
   }
 };
 
+// workgroups sharing one strip of a launch with OT output tiles over `strips` (image, strip) pairs (ConvLaunch::o_split)
+int conv_o_split(int OT, int64_t strips) {
+  int o_split = 1;
+  if (OT >= 2 * IMG_WAVES && strips < 512) o_split = 2;      // < 2 workgroups per CU otherwise
+  if (OT >= 4 * IMG_WAVES && strips < 256) o_split = 4;
+  return o_split;
+}
+
 template <int EPI>
 void launch_conv(const ConvLaunch& p, int n, hipStream_t s, Recorder* rec = nullptr) {
   const int halo = p.ks >> 1;
@@ -1073,9 +1099,7 @@ void launch_conv(const ConvLaunch& p, int n, hipStream_t s, Recorder* rec = null
   }
   if (p.pre_in != nullptr) lds += (size_t)((p.pre_cin + 15) / 16) * 16 * (IMG_R + 2) * (p.W + 2) * 4;
   if (OT < IMG_WAVES) lds = std::max(lds, (size_t)IMG_WAVES * (IMG_WAVES - 1) * PT * 64 * 16);
-  q.o_split = 1;
-  if (OT >= 2 * IMG_WAVES && (int64_t)n * p.n_strips < 512) q.o_split = 2;      // < 2 workgroups per CU otherwise
-  if (OT >= 4 * IMG_WAVES && (int64_t)n * p.n_strips < 256) q.o_split = 4;
+  q.o_split = conv_o_split(OT, (int64_t)n * p.n_strips);
   if (rec != nullptr) {
     RepairOp& op = rec->add(ROP_CONV);
     q.o_split = 1;
@@ -1971,11 +1995,23 @@ hipError_t img_allow_lds() {
   if (e == hipSuccess) e = allow_lds<EPI_COUPLE_AFFINE>();
   if (e == hipSuccess) e = allow_lds<EPI_COUPLE_ADD>();
   if (e == hipSuccess) e = allow_lds<EPI_SPLIT>();
+  if (e == hipSuccess) e = allow_lds<EPI_COUPLE_AFFINE_ORD>();
+  if (e == hipSuccess) e = allow_lds<EPI_SPLIT_ORD>();
   return e;
+}
+
+int img_ldj_slots(int cout, int n_strips, int64_t n) {
+  return n_strips * conv_o_split((cout + 15) / 16, n * n_strips) * IMG_WAVES;
+}
+
+void img_launch_ldj_reduce(const float* part, int slots, float* ldj, int64_t n, hipStream_t s) {
+  hipLaunchKernelGGL(img_ldj_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, part, slots, ldj, n);
 }
 
 bool img_launch_conv(int epi, const ConvLaunch& p, int n, hipStream_t s) {
   switch (epi) {
+    case EPI_COUPLE_AFFINE_ORD: launch_conv<EPI_COUPLE_AFFINE_ORD>(p, n, s); return true;
+    case EPI_SPLIT_ORD: launch_conv<EPI_SPLIT_ORD>(p, n, s); return true;
     case EPI_RELU: launch_conv<EPI_RELU>(p, n, s); return true;
     case EPI_STORE: launch_conv<EPI_STORE>(p, n, s); return true;
     case EPI_COUPLE_AFFINE: launch_conv<EPI_COUPLE_AFFINE>(p, n, s); return true;

@@ -197,7 +197,7 @@ int gbnf_image_boosted_nll_step(const gbnf_image_flow* fixed, float g_floor, gbn
   ImageBoostLayout L;
   if (const int rc = image_boost_layout(fixed, trainer, n, &L)) return rc;
   if (workspace_bytes < L.total)
-    return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld (gbnf_image_boosted_step_workspace_bytes)", fn,
+    return fail(GBNF_ERR_INVALID, "%s: workspace too small: %lld bytes < %lld (gbnf_image_boosted_step_workspace_bytes)", fn,
                 (long long)workspace_bytes, (long long)L.total);
   hipStream_t s = (hipStream_t)stream;
   char* ws = (char*)workspace;

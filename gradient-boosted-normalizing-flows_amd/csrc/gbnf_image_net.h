@@ -9,7 +9,10 @@ namespace gbnf {
 // epilogues of the image convolution kernels (img_conv_kernel, img_last_hx3_kernel, img_net_hx3_kernel)
 enum { EPI_RELU = 0, EPI_STORE = 1, EPI_COUPLE_AFFINE = 2, EPI_COUPLE_ADD = 3, EPI_SPLIT = 4,
        // the z -> x direction (gbnf_image_flow_inverse): coupling^-1 and Split2d's re-draw of the half it dropped
-       EPI_COUPLE_AFFINE_INV = 5, EPI_COUPLE_ADD_INV = 6, EPI_SPLIT_INV = 7 };
+       EPI_COUPLE_AFFINE_INV = 5, EPI_COUPLE_ADD_INV = 6, EPI_SPLIT_INV = 7,
+       // the image trainer's deterministic mode: EPI_COUPLE_AFFINE / EPI_SPLIT whose waves STORE their log-det partials to per-image
+       // slots (ConvLaunch::ldj, img_ldj_slots) instead of adding them into ldj[n]; img_launch_ldj_reduce adds the slots in order
+       EPI_COUPLE_AFFINE_ORD = 8, EPI_SPLIT_ORD = 9 };
 
 struct NetLaunch {
   const float* pre_in;      // (n, *, H, W) f32: the coupling net's input z1
@@ -55,7 +58,8 @@ struct ConvLaunch {
   int64_t out_img;
   float* st;              // EPI_COUPLE_* / EPI_SPLIT: the coupled half z2 (n, *, H, W), first channel of image 0
   int64_t st_img;
-  float* ldj;             // (n,) accumulated with atomics (EPI_COUPLE_AFFINE / EPI_SPLIT)
+  float* ldj;             // (n,) accumulated with atomics (EPI_COUPLE_AFFINE / EPI_SPLIT); EPI_*_ORD: (n, slots) partials, slot
+                          // (strip * o_split + osp) * IMG_WAVES + wave of image n is STORED by that wave (zero if it ran no epilogue)
   int cin, cout, H, W, ks, n_strips;
   int Hv, Wv;             // the map proper: rows < Hv, columns < Wv of the H x W storage (a 14 x 14 map lives in 16 x 16 storage;
                           // everything outside is ZERO in every tensor in HBM -- the 'same' padding of the map -- and stays so)
@@ -74,9 +78,14 @@ struct ConvLaunch {
 
 // ---- the evaluation path's kernels as the training path (gbnf_image_train.hip) launches them; defined in gbnf_image.hip.
 // img_allow_lds: the convolution kernels' opt-in to 160 KB of dynamic LDS on the CURRENT device.  img_launch_conv: epi = EPI_RELU,
-// EPI_STORE, EPI_COUPLE_AFFINE, EPI_COUPLE_ADD or EPI_SPLIT (false: another value); c_chunk and o_split are chosen here.
+// EPI_STORE, EPI_COUPLE_AFFINE, EPI_COUPLE_ADD, EPI_SPLIT, EPI_COUPLE_AFFINE_ORD or EPI_SPLIT_ORD (false: another value); c_chunk
+// and o_split are chosen here.  img_ldj_slots: the log-det slots per image of an EPI_*_ORD launch of that shape (cout output
+// channels, n_strips strips, n images) -- n_strips * o_split * waves, with the o_split img_launch_conv chooses.
+// img_launch_ldj_reduce: ldj[i] += part[i][0] + part[i][1] + ... in slot order, one thread per image.
 hipError_t img_allow_lds();
 bool img_launch_conv(int epi, const ConvLaunch& p, int n, hipStream_t s);
+int img_ldj_slots(int cout, int n_strips, int64_t n);
+void img_launch_ldj_reduce(const float* part, int slots, float* ldj, int64_t n, hipStream_t s);
 void img_launch_pre(const float* x, const float* noise, float* out, float* ldj, int C, int H, int W, int Hi, int Wi, float bounds,
                     float ld_const, int64_t n, hipStream_t s);
 void img_launch_squeeze(const float* in, int64_t in_img, float* out, int C, int H, int W, int Ho, int Wo, int64_t n, hipStream_t s);

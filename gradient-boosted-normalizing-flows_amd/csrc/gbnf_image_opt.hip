@@ -535,7 +535,7 @@ int gbnf_image_trainer_nll_step(gbnf_image_trainer* t, const float* x, const flo
   ImageStepLayout L;
   if (const int rc = image_step_layout(t, n, &L)) return rc;
   if (workspace_bytes < L.total)
-    return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld (gbnf_image_trainer_step_workspace_bytes)", fn,
+    return fail(GBNF_ERR_INVALID, "%s: workspace too small: %lld bytes < %lld (gbnf_image_trainer_step_workspace_bytes)", fn,
                 (long long)workspace_bytes, (long long)L.total);
   if (mix_allow_lds() != hipSuccess) return fail(GBNF_ERR_HIP, "%s: the 1x1 kernels' LDS opt-in failed", fn);
   const ImageStepState* st = t->step;

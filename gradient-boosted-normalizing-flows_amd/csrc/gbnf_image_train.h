@@ -49,6 +49,8 @@ struct gbnf_image_trainer {
   int n_net = 0;                               // convolutions per coupling net
   int64_t state_img = 0;                       // floats of the largest state tensor of one image
   int64_t trace_img = 0;                       // trace floats per image
-  gbnf::ImageStepState* step = nullptr;        // what the one-call training step adds (gbnf_image_opt.hip): bindings, region table, partial sums
+  int deterministic = 0;                       // gbnf_image_trainer_set_deterministic: ordered weight-gradient and log-det sums; the
+                                               // workspace then ends with the log-det slots and the weight-gradient partials
+  gbnf::ImageStepState* step = nullptr;       // what the one-call training step adds (gbnf_image_opt.hip): bindings, region table, partial sums
 };
 

@@ -22,6 +22,11 @@
 // flush of the block; the launch gives a slice at least WGRAD_ITEMS items (measured per shape) and makes at
 // most about 1024 workgroups.
 //
+// Deterministic mode (gbnf_image_trainer_set_deterministic): the slices STORE their blocks to per-slice partials in the workspace
+// (img_train_wgrad_det_kernel) and img_train_wgrad_reduce_kernel adds them in slice order; the coupling / Split2d epilogues of the
+// forward store per-wave log-det slots that img_ldj_reduce_kernel (gbnf_image.hip) adds in slot order.  Nothing else in the step adds
+// floats in an unordered way.
+//
 // Reference semantics: as gbnf_image.hip (models/glow.py:92-110, 317-342; models/layers.py:488-533, 577-630, 685-705, 751-796).
 #include <hip/hip_runtime.h>
 
@@ -186,95 +191,40 @@ __device__ __forceinline__ void tr_drain(f32x4& c) { asm volatile("s_nop 7\n\ts_
 // PT: pixel tiles of a strip (4: 16-wide maps, 2: 8-wide); KS: 1 | 3.  NP (block pairs per wave) = 2 (3x3) | 4 (1x1).
 template <int PT, int KS>
 __global__ void __launch_bounds__(256) img_train_wgrad_kernel(const WgradLaunch p) {
-  extern __shared__ __attribute__((aligned(16))) float lds[];
-  constexpr int W = 16 * PT / TR_R, NPIX = 16 * PT, HALO = KS >> 1;
-  constexpr int WP = W + 2 * HALO, RP = TR_R + 2 * HALO, CS = RP * WP;
-  constexpr int CSP = CS | 1, GSP = NPIX + 1;                 // odd channel strides: the 16 channels of a fragment hit 16 banks
-  constexpr int TAPS = KS * KS, NP = KS == 3 ? 2 : 4;
-  const int lane = threadIdx.x & 63, i = lane & 15, g = lane >> 4;
-  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int ob = blockIdx.x / p.n_ib, ib = blockIdx.x - ob * p.n_ib;
-  const int och = p.obt * 16, ich = p.ibt * 16, npairs = p.obt * p.ibt;
-  const int co0 = ob * och, ci0 = ib * ich;
-  float* gL = lds;
-  float* aL = lds + och * GSP;
-  const int H = p.H;
+#define GBNF_IWG_DET 0
+#include "gbnf_image_wgrad_kernel.inc"
+#undef GBNF_IWG_DET
+}
 
-  f32x4 acc[NP][TAPS];
-#pragma unroll
-  for (int j = 0; j < NP; ++j)
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t) acc[j][t] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float dbacc = 0.0f;
+// Deterministic mode: the same text a second time (a shared `template <bool DET>` body is not guaranteed to leave the default
+// kernel's code alone), the flush a plain store to slice blockIdx.y's copy of the convolution's (dW', db') region.  p.dw / p.db:
+// slice 0's copy; part_stride = cout cin taps + cout floats.  Every valid entry is stored by exactly one workgroup of every slice:
+// the blocks tile the (output tile, input tile) pairs, a block's pairs are dealt to its waves completely (npairs <= 4 NP).
+template <int PT, int KS>
+__global__ void __launch_bounds__(256) img_train_wgrad_det_kernel(const WgradLaunch p, const int64_t part_stride) {
+#define GBNF_IWG_DET 1
+#include "gbnf_image_wgrad_kernel.inc"
+#undef GBNF_IWG_DET
+}
 
-  for (int item = blockIdx.y; item < p.n_items; item += gridDim.y) {
-    const int n = item / p.n_strips, strip = item - n * p.n_strips, r0 = strip * TR_R;
-    if (r0 >= p.Hv) continue;                                // (uniform) the gradient is zero on rows outside the map
-    __syncthreads();                                         // the previous item's fragments are read
-    {
-      const float* gs = p.g + (int64_t)n * p.g_img + (int64_t)r0 * W;
-      for (int idx = threadIdx.x; idx < och * NPIX; idx += 256) {
-        const int ch = idx / NPIX, px = idx - ch * NPIX, co = co0 + ch;
-        gL[ch * GSP + px] = co < p.cout ? gs[(int64_t)co * H * W + px] : 0.0f;
-      }
-      const float* as = p.a + (int64_t)n * p.a_img;
-      for (int idx = threadIdx.x; idx < ich * CS; idx += 256) {
-        const int ch = idx / CS, rem = idx - ch * CS, rr = rem / WP, cc = rem - rr * WP;
-        const int row = r0 + rr - HALO, col = cc - HALO, ci = ci0 + ch;
-        float v = 0.0f;
-        if (ci < p.cin && row >= 0 && row < H && col >= 0 && col < W) v = as[((int64_t)ci * H + row) * W + col];
-        aL[ch * CSP + rem] = v;
-      }
-    }
-    __syncthreads();
+// dst[e] = part[0][e] + part[1][e] + ... in slice order; one thread per entry of the convolution's (dW', db') region.  Eight loads
+// in flight, added in order.
+__global__ void __launch_bounds__(256) img_train_wgrad_reduce_kernel(const float* __restrict__ part, int64_t part_stride, int slices,
+                                                                     float* __restrict__ dst) {
+  const int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= part_stride) return;
+  const float* src = part + e;
+  float acc = 0.0f;
+  int y = 0;
+  for (; y + 8 <= slices; y += 8) {
+    float v[8];
 #pragma unroll
-    for (int j = 0; j < NP; ++j) {
-      const int q = wave + 4 * j;
-      if (q < npairs) {
-        const int ol = q % p.obt, il = q / p.obt;
-        const float* gf = gL + (ol * 16 + i) * GSP + g;
-        const float* af = aL + (il * 16 + i) * CSP + HALO * WP + HALO;
-        for (int kk = 0; kk < NPIX / 4; ++kk) {
-          const int px = 4 * kk + g, pr = px / W, pc = px - pr * W;
-          const float gv = gf[4 * kk];
-          const float* ap = af + pr * WP + pc;
+    for (int q = 0; q < 8; ++q) v[q] = src[(int64_t)(y + q) * part_stride];
 #pragma unroll
-          for (int t = 0; t < TAPS; ++t) {
-            const int dy = t / KS - HALO, dx = t % KS - HALO;
-            acc[j][t] = tr_mfma(gv, ap[dy * WP + dx], acc[j][t]);
-          }
-        }
-      }
-    }
-    if (ib == 0 && (int)threadIdx.x < och) {
-      float s = 0.0f;
-      for (int px = 0; px < NPIX; ++px) s += gL[threadIdx.x * GSP + px];
-      dbacc += s;
-    }
+    for (int q = 0; q < 8; ++q) acc += v[q];
   }
-#pragma unroll
-  for (int j = 0; j < NP; ++j)
-#pragma unroll
-    for (int t = 0; t < TAPS; ++t) tr_drain(acc[j][t]);
-  // flush: lane (i, g) holds dW'[16 ot + 4 g + r][16 it + i] of every tap
-#pragma unroll
-  for (int j = 0; j < NP; ++j) {
-    const int q = wave + 4 * j;
-    if (q < npairs) {
-      const int ol = q % p.obt, il = q / p.obt;
-      const int ci = ci0 + il * 16 + i;
-#pragma unroll
-      for (int r = 0; r < 4; ++r) {
-        const int co = co0 + ol * 16 + 4 * g + r;
-        if (co < p.cout && ci < p.cin) {
-          float* dst = p.dw + ((int64_t)co * p.cin + ci) * TAPS;
-#pragma unroll
-          for (int t = 0; t < TAPS; ++t) atomicAdd(dst + t, acc[j][t][r]);
-        }
-      }
-    }
-  }
-  if (ib == 0 && (int)threadIdx.x < och && co0 + (int)threadIdx.x < p.cout) atomicAdd(p.db + co0 + threadIdx.x, dbacc);
+  for (; y < slices; ++y) acc += src[(int64_t)y * part_stride];
+  dst[e] = acc;
 }
 
 // ---- unfold: grid (512 / 4, entries); one WAVE per output channel (mix: per input channel), lanes along the row: coalesced ------
@@ -344,11 +294,15 @@ namespace {
 int64_t tile_floats(int cout, int cin, int ks) { return (int64_t)((cout + 15) / 16) * ((cin + 15) / 16) * ks * ks * 256; }
 
 // workspace (floats): activations A[0..3] | GA | GB (hidden-wide, n images each) | HO (64 channels) | GS0 | GS1 (state) | zero g_ldj (n)
-// | (dW', db') scratch
+// | (dW', db') scratch; deterministic mode appends | log-det slots of one launch (n x the most slots of a coupling / Split2d launch)
+// | weight-gradient partials [slices][dW', db'] of the largest launch at this n
 struct TrainSpace {
   float* A[4]; float* GA; float* GB; float* HO; float* GS0; float* GS1; float* gl0; float* scr;
+  float* ldp; float* wpart;          // null unless the trainer is deterministic
   int64_t total;
 };
+int64_t det_ldj_floats(const gbnf_image_trainer* t, int64_t n);
+int64_t det_wgrad_floats(const gbnf_image_trainer* t, int64_t n);
 TrainSpace train_space(const gbnf_image_trainer* t, float* ws, int64_t n) {
   TrainSpace s{};
   const int64_t hid = (int64_t)((t->hidden + 15) / 16 * 16) * 256 * n, ho = (int64_t)64 * 256 * n, st = t->state_img * n;
@@ -359,6 +313,10 @@ TrainSpace train_space(const gbnf_image_trainer* t, float* ws, int64_t n) {
   s.GS0 = p; p += st; s.GS1 = p; p += st;
   s.gl0 = p; p += (n + 63) / 64 * 64;
   s.scr = p; p += (t->scratch_floats + 63) / 64 * 64;
+  if (t->deterministic) {
+    s.ldp = p; p += (det_ldj_floats(t, n) + 63) / 64 * 64;
+    s.wpart = p; p += (det_wgrad_floats(t, n) + 63) / 64 * 64;
+  }
   s.total = p - ws;
   return s;
 }
@@ -402,11 +360,10 @@ void place(gbnf_image_trainer* t) {          // pack blob and scratch offsets of
   t->scratch_floats = scr;
 }
 
-bool launch_wgrad(const TConv& e, const float* a, int64_t a_img, const float* g, int64_t g_img, float* scr, int H, int W, int Hv, int64_t n,
-                  hipStream_t s) {
-  WgradLaunch p{};
-  p.a = a; p.a_img = a_img; p.g = g; p.g_img = g_img; p.dw = scr + e.gw_off; p.db = scr + e.gb_off;
-  p.cin = e.cin; p.cout = e.cout; p.H = H; p.Hv = Hv; p.n_strips = H / TR_R; p.n_items = (int)(n * p.n_strips);
+// the shape of entry e's weight-gradient launch on H-row maps at a batch of n: p's block / item fields, -> the slice count.  A function
+// of the layer's shape, n and WGRAD_ITEMS only (deterministic mode sizes its partials with it and adds them in slice order).
+int wgrad_shape(const TConv& e, int H, int64_t n, WgradLaunch& p, int* blocks_out) {
+  p.cin = e.cin; p.cout = e.cout; p.H = H; p.n_strips = H / TR_R; p.n_items = (int)(n * p.n_strips);
   const int OT = (e.cout + 15) / 16, IT = (e.cin + 15) / 16, NP = e.ks == 3 ? 2 : 4;
   p.obt = OT >= 4 ? 4 : (OT >= 2 ? 2 : 1);
   p.ibt = std::min(std::min(4 * NP / p.obt, 8), IT);
@@ -425,10 +382,33 @@ bool launch_wgrad(const TConv& e, const float* a, int64_t a_img, const float* g,
     return r;
   }();
   const int min_items = items.v[e.ks == 1 ? 2 : (OT >= IT ? 0 : 1)];
-  const int slices = std::max(1, std::min((p.n_items + min_items - 1) / min_items, 1024 / blocks));
+  *blocks_out = blocks;
+  return std::max(1, std::min((p.n_items + min_items - 1) / min_items, 1024 / blocks));
+}
+
+// part: null = the flush adds into scr with float atomics; else (deterministic mode) the slices store to part[slice][dW', db'] and a
+// second launch adds them in slice order into scr
+bool launch_wgrad(const TConv& e, const float* a, int64_t a_img, const float* g, int64_t g_img, float* scr, float* part, int H, int W, int Hv,
+                  int64_t n, hipStream_t s) {
+  WgradLaunch p{};
+  int blocks = 0;
+  const int slices = wgrad_shape(e, H, n, p, &blocks);
+  p.a = a; p.a_img = a_img; p.g = g; p.g_img = g_img; p.dw = scr + e.gw_off; p.db = scr + e.gb_off;
+  p.Hv = Hv;
   const int halo = e.ks >> 1, cs = ((TR_R + 2 * halo) * (W + 2 * halo)) | 1, npix = TR_R * W;
   const size_t lds = ((size_t)p.obt * 16 * (npix + 1) + (size_t)p.ibt * 16 * cs) * 4;
   const dim3 grid((unsigned)blocks, (unsigned)slices), blk(256);
+  if (part != nullptr) {
+    const int64_t wn = (int64_t)e.cout * e.cin * e.ks * e.ks, stride = wn + e.cout;       // (gb_off = gw_off + wn: place())
+    p.dw = part; p.db = part + wn;
+    if (W == 16 && e.ks == 3) hipLaunchKernelGGL((img_train_wgrad_det_kernel<4, 3>), grid, blk, lds, s, p, stride);
+    else if (W == 16) hipLaunchKernelGGL((img_train_wgrad_det_kernel<4, 1>), grid, blk, lds, s, p, stride);
+    else if (e.ks == 3) hipLaunchKernelGGL((img_train_wgrad_det_kernel<2, 3>), grid, blk, lds, s, p, stride);
+    else hipLaunchKernelGGL((img_train_wgrad_det_kernel<2, 1>), grid, blk, lds, s, p, stride);
+    hipLaunchKernelGGL(img_train_wgrad_reduce_kernel, dim3((unsigned)((stride + 255) / 256)), blk, 0, s, (const float*)part, stride, slices,
+                       scr + e.gw_off);
+    return true;
+  }
   if (W == 16 && e.ks == 3) hipLaunchKernelGGL((img_train_wgrad_kernel<4, 3>), grid, blk, lds, s, p);
   else if (W == 16) hipLaunchKernelGGL((img_train_wgrad_kernel<4, 1>), grid, blk, lds, s, p);
   else if (e.ks == 3) hipLaunchKernelGGL((img_train_wgrad_kernel<2, 3>), grid, blk, lds, s, p);
@@ -436,9 +416,48 @@ bool launch_wgrad(const TConv& e, const float* a, int64_t a_img, const float* g,
   return true;
 }
 
+// deterministic mode's workspace pieces at a batch of n.  Both walk the launches the backward / forward make: per level its steps'
+// mix and net convolutions and its split prior, all on the level's H-row maps.
+int64_t det_wgrad_floats(const gbnf_image_trainer* t, int64_t n) {
+  int64_t worst = 0;
+  for (size_t l = 0; l < t->levels.size(); ++l) {
+    auto one = [&](const TConv& e) {
+      WgradLaunch p{};
+      int blocks = 0;
+      const int slices = wgrad_shape(e, t->levels[l].H, n, p, &blocks);
+      worst = std::max(worst, (int64_t)slices * ((int64_t)e.cout * e.cin * e.ks * e.ks + e.cout));
+    };
+    for (int first : t->step_first[l])
+      for (int q = 0; q <= t->n_net; ++q) one(t->table[first + q]);
+    if (t->split_entry[l] >= 0) one(t->table[t->split_entry[l]]);
+  }
+  return worst;
+}
+int64_t det_ldj_floats(const gbnf_image_trainer* t, int64_t n) {
+  int slots = 0;
+  for (size_t l = 0; l < t->levels.size(); ++l) {
+    const int n_strips = t->levels[l].H / TR_R;
+    for (int first : t->step_first[l]) slots = std::max(slots, img_ldj_slots(t->table[first + t->n_net].cout, n_strips, n));
+    if (t->split_entry[l] >= 0) slots = std::max(slots, img_ldj_slots(t->table[t->split_entry[l]].cout, n_strips, n));
+  }
+  return (int64_t)slots * n;
+}
+
 }  // namespace
 
 extern "C" {
+
+int gbnf_image_trainer_set_deterministic(gbnf_image_trainer* t, int32_t on) {
+  if (!t) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_set_deterministic: trainer is null");
+  t->deterministic = on ? 1 : 0;
+  return GBNF_OK;
+}
+
+int gbnf_image_trainer_get_deterministic(const gbnf_image_trainer* t, int32_t* on) {
+  if (!t || !on) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_get_deterministic: bad argument");
+  *on = t->deterministic;
+  return GBNF_OK;
+}
 
 int gbnf_image_trainer_destroy(gbnf_image_trainer* t) {
   if (!t) return GBNF_OK;
@@ -644,7 +663,14 @@ int gbnf_image_trainer_forward(gbnf_image_trainer* t, const float* x, const floa
       ConvLaunch q = conv_base(lv, ldj);
       q.in = hin; q.in_img = hin_img; q.wp = t->blob_dev + c.fwd_off; q.bias = t->blob_dev + c.b_off;
       q.st = O + (int64_t)c1 * lv.H * lv.W; q.st_img = img; q.cin = c.cin; q.cout = c.cout; q.ks = c.ks;
-      img_launch_conv(t->additive ? EPI_COUPLE_ADD : EPI_COUPLE_AFFINE, q, (int)n, s);
+      if (t->deterministic && !t->additive) {
+        // the waves store their log-det partials to the launch's slots; one thread per image adds them onto ldj in slot order
+        q.ldj = sp.ldp;
+        img_launch_conv(EPI_COUPLE_AFFINE_ORD, q, (int)n, s);
+        img_launch_ldj_reduce(sp.ldp, img_ldj_slots(c.cout, q.n_strips, n), ldj, n, s);
+      } else {
+        img_launch_conv(t->additive ? EPI_COUPLE_ADD : EPI_COUPLE_AFFINE, q, (int)n, s);
+      }
     }
     if (l < t->L - 1) {
       float* O = trace_slot(t, trace, n, l, 2 * lv.K);
@@ -652,7 +678,13 @@ int gbnf_image_trainer_forward(gbnf_image_trainer* t, const float* x, const floa
       ConvLaunch p = conv_base(lv, ldj);
       p.in = O; p.in_img = img; p.wp = t->blob_dev + c.fwd_off; p.bias = t->blob_dev + c.b_off;
       p.st = O + (int64_t)c1 * lv.H * lv.W; p.st_img = img; p.cin = c.cin; p.cout = c.cout; p.ks = c.ks;
-      img_launch_conv(EPI_SPLIT, p, (int)n, s);
+      if (t->deterministic) {
+        p.ldj = sp.ldp;
+        img_launch_conv(EPI_SPLIT_ORD, p, (int)n, s);
+        img_launch_ldj_reduce(sp.ldp, img_ldj_slots(c.cout, p.n_strips, n), ldj, n, s);
+      } else {
+        img_launch_conv(EPI_SPLIT, p, (int)n, s);
+      }
       const auto& nx = t->levels[l + 1];
       img_launch_squeeze(O, img, trace_slot(t, trace, n, l + 1, 0), c1, lv.H, lv.W, nx.H, nx.W, n, s);
     }
@@ -670,8 +702,9 @@ int gbnf_image_trainer_forward(gbnf_image_trainer* t, const float* x, const floa
 // weight gradient of entry `c` and the data gradient of its input.  dst_store: the adjoint's result is stored there (stride dst_img);
 // dst_add: it is ADDED there (the z1 half of the state gradient); both null: no data gradient wanted.
 static void conv_backward(const gbnf_image_trainer* t, const gbnf_image_trainer::Level& lv, const TConv& c, const float* in, int64_t in_img,
-                          const float* G, int64_t G_img, float* scr, float* dst_store, float* dst_add, int64_t dst_img, int64_t n, hipStream_t s) {
-  launch_wgrad(c, in, in_img, G, G_img, scr, lv.H, lv.W, lv.Hv, n, s);
+                          const float* G, int64_t G_img, float* scr, float* part, float* dst_store, float* dst_add, int64_t dst_img, int64_t n,
+                          hipStream_t s) {
+  launch_wgrad(c, in, in_img, G, G_img, scr, part, lv.H, lv.W, lv.Hv, n, s);
   if (!dst_store && !dst_add) return;
   ConvLaunch p = conv_base(lv, nullptr);
   p.in = G; p.in_img = G_img; p.wp = t->blob_dev + c.bwd_off; p.bias = t->blob_dev + t->zero_off;
@@ -721,7 +754,7 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* t, const float* trace_c, int
       const int64_t total = n * (int64_t)c1 * HW;              // (C even: the dropped half has c1 channels)
       hipLaunchKernelGGL(img_train_split_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sp.HO, p.out_img,
                          (const float*)(O + (int64_t)c1 * HW), img, cur + (int64_t)c1 * HW, img, gl, c1, lv.H, lv.W, lv.Hv, lv.Wv, total);
-      conv_backward(t, lv, c, O, img, sp.HO, p.out_img, sp.scr, nullptr, cur, img, n, s);
+      conv_backward(t, lv, c, O, img, sp.HO, p.out_img, sp.scr, sp.wpart, nullptr, cur, img, n, s);
     }
     for (int k = lv.K - 1; k >= 0; --k) {
       const int first = t->step_first[l][k];
@@ -752,11 +785,11 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* t, const float* trace_c, int
       for (int q = t->n_net - 1; q >= 0; --q) {
         const TConv& c = t->table[first + 1 + q];
         if (q == 0) {
-          conv_backward(t, lv, c, P, img, G, G_img, sp.scr, nullptr, cur, img, n, s);
+          conv_backward(t, lv, c, P, img, G, G_img, sp.scr, sp.wpart, nullptr, cur, img, n, s);
         } else {
           float* Gn = (G == sp.GA) ? sp.GB : sp.GA;
           const int64_t a_img = (int64_t)c.cin * HW;
-          conv_backward(t, lv, c, sp.A[q - 1], a_img, G, G_img, sp.scr, Gn, nullptr, a_img, n, s);
+          conv_backward(t, lv, c, sp.A[q - 1], a_img, G, G_img, sp.scr, sp.wpart, Gn, nullptr, a_img, n, s);
           const int64_t total4 = n * a_img / 4;
           hipLaunchKernelGGL(img_train_relu_mask_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, Gn, (const float*)sp.A[q - 1], total4);
           G = Gn; G_img = a_img;
@@ -764,7 +797,7 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* t, const float* trace_c, int
       }
       // the mix: cur is the gradient of P_k now
       const bool need_data = !(l == 0 && k == 0);                // (there is no gradient with respect to x)
-      conv_backward(t, lv, t->table[first], prev, img, cur, img, sp.scr, need_data ? oth : nullptr, nullptr, img, n, s);
+      conv_backward(t, lv, t->table[first], prev, img, cur, img, sp.scr, sp.wpart, need_data ? oth : nullptr, nullptr, img, n, s);
       if (need_data) std::swap(cur, oth);
     }
   }

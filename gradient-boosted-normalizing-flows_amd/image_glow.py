@@ -342,11 +342,15 @@ class BoostedImageFlow(nn.Module):
         if args.component_type != "glow":
             raise NotImplementedError("image components are Glow (models/boosted_flow.py:44-50 builds nothing else for images)")
         self.args = args
-        # deterministic mode (BoostedFlow: args.deterministic / env GBNF_DETERMINISTIC) orders the tabular trainer's sums only.  The
-        # flag is kept and the module builds and evaluates as ever; the first TRAINING call is refused (native_trainer) rather than
-        # served by the image trainer's float atomics.
-        from .boosted_flow import deterministic_from
+        # Two flags.  `deterministic` (BoostedFlow: args.deterministic / env GBNF_DETERMINISTIC) was defined when only the tabular
+        # trainer had ordered sums: an image module that carries it builds and evaluates as ever and its first TRAINING call is
+        # refused (native_trainer) -- behaviour the suite pins.  `image_deterministic` (args.image_deterministic / env
+        # GBNF_IMAGE_DETERMINISTIC) asks for the image trainer's own ordered path (gbnf_image_trainer_set_deterministic) and is
+        # applied to every trainer native_trainer() hands out; with it set the refusal does not fire.  (One flag would do once
+        # the refusal is no longer expected of `deterministic` alone.)
+        from .boosted_flow import deterministic_from, image_deterministic_from
         self.deterministic = deterministic_from(args)
+        self.image_deterministic = image_deterministic_from(args)
         self.num_flows, self.z_size = args.num_flows, args.z_size
         self.density_evaluation = args.density_evaluation
         self.all_trained, self.component_type = False, args.component_type
@@ -425,10 +429,20 @@ class BoostedImageFlow(nn.Module):
     def native_trainer(self, c):
         """(native.NativeImageTrainer bound to component c's live parameter storage, bindings), cached like ``native_flow`` and keyed
         on the tensors' addresses (not their versions: an optimiser's in-place update needs no new trainer).  bindings: one
-        (path, parameter | InvertibleConv1x1 module, persistent composed matrix | None, pixels of the level) per bound tensor."""
-        if self.deterministic:
-            raise native.GbnfError("deterministic mode is on and the image trainer has no ordered path: its weight gradients and "
-                                   "log-det sums are added with unordered float atomics (gbnf_image_trainer_backward)")
+        (path, parameter | InvertibleConv1x1 module, persistent composed matrix | None, pixels of the level) per bound tensor.
+
+        Two flags, for a reason of history: ``deterministic`` alone is refused here, as it was while the image trainer had no
+        ordered path; ``image_deterministic`` switches every trainer handed out (cached ones included) to the ordered sums."""
+        if self.deterministic and not self.image_deterministic:
+            raise native.GbnfError("deterministic mode is on, but the image trainer's ordered path is asked for by a flag of its own: "
+                                   "set image_deterministic (args.image_deterministic / env GBNF_IMAGE_DETERMINISTIC) as well "
+                                   "(without it the weight gradients and log-det sums are added with unordered float atomics)")
+        trainer, bind = self._native_trainer(c)
+        if trainer._deterministic != bool(self.image_deterministic):     # (also a cached trainer after the module's flag changed)
+            trainer.deterministic = bool(self.image_deterministic)
+        return trainer, bind
+
+    def _native_trainer(self, c):
         flow = self.flows[c]
         params, buffers, perms, actnorms = self._component_tensors(c)
         if not all(bool(m.inited) for m in actnorms):

@@ -47,6 +47,7 @@ ABI_SYMBOLS = (
     "gbnf_flow_numerics_inverse", "gbnf_image_flow_inverse_check_counts",
     "gbnf_image_trainer_create", "gbnf_image_trainer_destroy", "gbnf_image_trainer_trace_floats", "gbnf_image_trainer_workspace_bytes",
     "gbnf_image_trainer_forward", "gbnf_image_trainer_grad_floats", "gbnf_image_trainer_backward",
+    "gbnf_image_trainer_set_deterministic", "gbnf_image_trainer_get_deterministic",
     "gbnf_image_trainer_bind_lu", "gbnf_image_trainer_bind_top", "gbnf_image_trainer_step_grad_floats",
     "gbnf_image_trainer_step_workspace_bytes", "gbnf_image_trainer_apply_update", "gbnf_image_trainer_nll_step",
     "gbnf_image_rho_step_workspace_bytes", "gbnf_image_mixture_rho_step",
@@ -232,6 +233,8 @@ def lib():
     L.gbnf_image_trainer_forward.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.gbnf_image_trainer_grad_floats.argtypes = [vp, C.POINTER(i64)]
     L.gbnf_image_trainer_backward.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp]
+    L.gbnf_image_trainer_set_deterministic.argtypes = [vp, i32]
+    L.gbnf_image_trainer_get_deterministic.argtypes = [vp, C.POINTER(i32)]
     L.gbnf_image_trainer_bind_lu.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.gbnf_image_trainer_bind_top.argtypes = [vp, vp, vp, vp]
     L.gbnf_image_trainer_step_grad_floats.argtypes = [vp, C.POINTER(i64)]
@@ -664,11 +667,16 @@ class NativeImageTrainer:
     ``dev_spec`` has the shape of an image flow spec (synth.synth_image_glow_spec) but every float array is a contiguous float32
     CUDA tensor -- the caller's parameter storage itself (``perm`` stays a host int64 array; ``perm_w`` is the composed C x C matrix
     of an InvertibleConv1x1).  Nothing is copied: the library keeps the addresses, this object keeps the tensors alive.  ``learn_top``
-    is ignored (the top prior is the caller's).  ``ldj`` of ``forward`` EXCLUDES the log-determinants of the ``perm_w`` matrices."""
+    is ignored (the top prior is the caller's).  ``ldj`` of ``forward`` EXCLUDES the log-determinants of the ``perm_w`` matrices.
+
+    ``deterministic``: the weight gradients are flushed as per-slice partials and the log-det sums as per-wave slots, both added in
+    a fixed order (gbnf_image_trainer_set_deterministic): ``forward``, ``backward``, ``nll_step`` and the step of
+    ``boosted_nll_step`` are bit-reproducible for fixed inputs, parameters and batch size.  The workspaces grow; their sizes are
+    asked of the library on every call."""
 
     CONV_KEYS = ("w", "b", "an_bias", "an_logs", "logs")          # order of a convolution's arrays in the flat gradient buffer
 
-    def __init__(self, dev_spec):
+    def __init__(self, dev_spec, deterministic=False):
         self._tensors = []
         self._regions = []          # (path, offset, shape) in the order of the flat gradient buffer
         self._region_tensors = []   # the bound tensor of each
@@ -758,9 +766,36 @@ class NativeImageTrainer:
         self._step_ws = None
         self._boost_ws = None       # workspace of boosted_nll_step
         self._layout_step()
+        self._deterministic = False
+        if deterministic:
+            self.deterministic = True
 
     def key(self):
         return tuple(t.data_ptr() for t in self._tensors)
+
+    @property
+    def deterministic(self):
+        """Deterministic mode of the trainer (gbnf_image_trainer_get_deterministic / gbnf_image_trainer_set_deterministic)."""
+        on = C.c_int32()
+        _check(lib().gbnf_image_trainer_get_deterministic(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    @deterministic.setter
+    def deterministic(self, on):
+        _check(lib().gbnf_image_trainer_set_deterministic(self.handle, 1 if on else 0))
+        self._deterministic = bool(on)
+
+    def workspace_bytes(self, n):
+        """Bytes of the forward / backward workspace at a batch of n images (gbnf_image_trainer_workspace_bytes)."""
+        nb = C.c_int64()
+        _check(lib().gbnf_image_trainer_workspace_bytes(self.handle, int(n), C.byref(nb)))
+        return int(nb.value)
+
+    def step_workspace_bytes(self, n):
+        """Bytes of the workspace of ``nll_step`` at a batch of n images (gbnf_image_trainer_step_workspace_bytes)."""
+        nb = C.c_int64()
+        _check(lib().gbnf_image_trainer_step_workspace_bytes(self.handle, int(n), C.byref(nb)))
+        return int(nb.value)
 
     # ---- the one-call training step (gbnf_image_trainer_nll_step / _apply_update)
     def _layout_step(self):

@@ -480,8 +480,8 @@ int gbnf_trainer_backward(const gbnf_trainer* trainer, const float* x, int64_t n
  * returns GBNF_ERR_UNSUPPORTED with the reason and launches nothing.  (A GBNF_MATH_BF16X6 trainer has no per-step
  * kernels: a call it cannot serve is refused as ever, with its own reason, behind the launch that finds the scale of
  * the upstream gradient; it never gives an unordered result either.)  Nothing is promised across different n, tuning
- * keys, math modes or builds.  The image trainer (gbnf_image_trainer_*) has no such mode: its weight gradients and
- * log-det sums stay as documented there. */
+ * keys, math modes or builds.  The image trainer has a mode of its own, gbnf_image_trainer_set_deterministic (below):
+ * this call does not reach it. */
 int gbnf_trainer_set_deterministic(gbnf_trainer* trainer, int32_t on);
 int gbnf_trainer_get_deterministic(const gbnf_trainer* trainer, int32_t* on);
 
@@ -721,7 +721,8 @@ int gbnf_image_flow_inverse(const gbnf_image_flow* flow, const float* z, const f
 typedef struct gbnf_image_trainer gbnf_image_trainer;
 int gbnf_image_trainer_create(const gbnf_image_flow_desc* desc_device_params, gbnf_image_trainer** out);
 int gbnf_image_trainer_destroy(gbnf_image_trainer* trainer);
-/* Floats of the trace buffer / bytes of the workspace (forward and backward share one size) at a batch of n images. */
+/* Floats of the trace buffer / bytes of the workspace (forward and backward share one size; larger in deterministic mode,
+ * below) at a batch of n images. */
 int gbnf_image_trainer_trace_floats(const gbnf_image_trainer* trainer, int64_t n, int64_t* floats);
 int gbnf_image_trainer_workspace_bytes(const gbnf_image_trainer* trainer, int64_t n, int64_t* bytes);
 /* x, noise, z as gbnf_image_flow_forward (z may be NULL); the same values as a GBNF_MATH_F32 evaluation handle with ONE
@@ -740,10 +741,35 @@ int gbnf_image_trainer_grad_floats(const gbnf_image_trainer* trainer, int64_t* f
 /* trace: what gbnf_image_trainer_forward left at the same n, parameters unchanged since.  g_z (n,Cz,Hz,Wz) and g_ldj (n,)
  * may each be NULL, meaning zero.  ACCUMULATES into grads (the caller zeroes it).  The ActNorm2d `logs` gradients include
  * the H*W * sum_n g_ldj[n] term of their own log-determinant; the `perm_weight` gradient is the data path only, consistent
- * with the forward.  There is no gradient with respect to x.  Weight gradients are summed with float atomics: the last
- * bits depend on the order. */
+ * with the forward.  There is no gradient with respect to x.  By default the weight gradients are summed with float atomics
+ * across the (image, strip) slices of a layer: their last bits depend on the order; in deterministic mode (below) every slice
+ * stores its partial and the partials are added in slice order. */
 int gbnf_image_trainer_backward(gbnf_image_trainer* trainer, const float* trace, int64_t n, const float* g_z,
                                 const float* g_ldj, float* grads, void* workspace, int64_t workspace_bytes, void* stream);
+
+/* Deterministic mode of an image trainer, a property of the trainer like gbnf_trainer_set_deterministic of the tabular one
+ * (off at creation; with it off the kernels, the launches, the results and the workspace sizes are what they always were).
+ * While it is on, for a fixed trainer, fixed inputs, fixed parameter values, a fixed n and a fixed process environment
+ * (GBNF_IMG_WGRAD_ITEMS), these outputs are bit-identical on every call:
+ *   gbnf_image_trainer_forward:   z, ldj, trace;
+ *   gbnf_image_trainer_backward:  grads (it still ACCUMULATES into them);
+ *   gbnf_image_trainer_nll_step:  grads, the parameters, exp_avg, exp_avg_sq, stats_dev[0..3];
+ *   gbnf_image_boosted_nll_step:  the same, for the step it contains.
+ * How: slice y of a weight-gradient launch stores its dW' tile entries and db' rows to partials[y][..] in the workspace
+ * (plain stores, no atomics) and a second launch adds the partials of every entry in slice order; the slice count is a
+ * function of the layer's shape, of n and of GBNF_IMG_WGRAD_ITEMS only.  Every wave of a coupling / Split2d epilogue stores
+ * its log-det partial to a slot of its image, and a small launch adds an image's slots in slot order onto ldj[n].
+ * Everything else in those calls is ordered already.  There are no refusals: every geometry the trainer accepts runs in
+ * this mode.  Cost: the largest slices x (cout cin k^2 + cout) floats over the trainer's convolutions and a few dozen
+ * floats per image of workspace -- gbnf_image_trainer_workspace_bytes, gbnf_image_trainer_step_workspace_bytes and
+ * gbnf_image_boosted_step_workspace_bytes report the larger sizes while the mode is on (ask again after switching it), and
+ * a workspace sized before switching it on is refused with GBNF_ERR_INVALID ("workspace too small") before the first
+ * launch, never overrun.
+ * NOT covered: stats_dev[4..6] of gbnf_image_boosted_nll_step and everything gbnf_image_mixture_rho_step writes -- both
+ * come from evaluation handles (gbnf_image_flow_*), whose kernels keep their atomics; the evaluation path has no such mode.
+ * Nothing is promised across different n, environments, builds or devices. */
+int gbnf_image_trainer_set_deterministic(gbnf_image_trainer* trainer, int32_t on);
+int gbnf_image_trainer_get_deterministic(const gbnf_image_trainer* trainer, int32_t* on);
 
 /* ---- one image training step in one call: loss, 1x1 log-determinants, clip, AdamW / SGD -----------------------------------
  * Replaces: one iteration of image_experiment.py:378-419 for the component being trained -- the loss (:227-229)

@@ -4,13 +4,15 @@ BASELINE.json configs[3] (3 x 32 x 32, K = 8, L = 2, h = 256) at batch 64, LU-de
 dimension.
 
     python tools/bench_image_fused_step.py [--batch 64] [--steps 50] [--reps 5] [--warmup 5] [--K 8] [--hidden 256] [--only fused]
+                                           [--deterministic]
 
   module   the eager step around the library's forward / backward: model.component_forward(x, 0, noise) in train mode -> the
            reference's loss -> backward() -> clip_grad_norm_ -> torch.optim.AdamW.step()
   fused    model.training_step(x, noise=noise, lr=..., max_grad_norm=50, weight_decay=...): gbnf_image_trainer_nll_step
 Each line: median [min - max] over ``reps`` windows of ``steps`` steps, same warm-up, the discipline of tools/bench_image_train.py.
 Per-kernel times of the new launches: a run of its own under
-`rocprofv3 --kernel-trace --stats -- python tools/bench_image_fused_step.py --only fused --reps 1`."""
+`rocprofv3 --kernel-trace --stats -- python tools/bench_image_fused_step.py --only fused --reps 1`.
+``--deterministic``: both lines in the image trainer's deterministic mode."""
 import argparse
 import json
 import math
@@ -33,7 +35,7 @@ def build(a, sp, dev):
         num_flows=a.K, z_size=3072, density_evaluation=True, device=dev, cuda=True, component_type="glow", num_components=1,
         rho_init="decreasing", learn_top=True, y_classes=0, y_condition=False, sample_size=4, input_size=[3, 32, 32], h_size=a.hidden,
         num_blocks=a.L, actnorm_scale=1.0, flow_permutation="invconv", flow_coupling="affine", LU_decomposed=True,
-        num_dequant_blocks=0, coupling_network="tanh", coupling_network_depth=1, batch_norm=False)
+        num_dequant_blocks=0, coupling_network="tanh", coupling_network_depth=1, batch_norm=False, image_deterministic=bool(a.deterministic))
     m = BoostedFlow(args)
     glow = m.flows[0]
     steps = [st for lv in sp["levels"] for st in lv["steps"]]
@@ -73,6 +75,7 @@ def main():
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--lr", type=float, default=1e-5)
     ap.add_argument("--only", choices=("module", "fused"), default=None)
+    ap.add_argument("--deterministic", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     sp = synth.synth_image_glow_spec((3, 32, 32), h=a.hidden, K=a.K, L=a.L, seed=3)
@@ -80,7 +83,7 @@ def main():
     xd, nd = torch.from_numpy(x).to(dev), torch.from_numpy(noise).to(dev)
     per_dim = 1.0 / (math.log(2.0) * 3072)
     out = {"workload": f"image fused step 3x32x32 K={a.K} L={a.L} h={a.hidden} batch={a.batch} LU AdamW clip 50 bpd", "steps": a.steps,
-           "reps": a.reps, "warmup": a.warmup}
+           "reps": a.reps, "warmup": a.warmup, "deterministic": bool(a.deterministic)}
 
     if a.only != "fused":
         m = build(a, sp, dev)

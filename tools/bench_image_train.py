@@ -3,6 +3,7 @@
 batch 64.
 
     python tools/bench_image_train.py [--batch 64] [--steps 50] [--reps 5] [--warmup 5] [--K 8] [--hidden 256] [--skip-eager]
+                                      [--deterministic]
 
 Three lines, each the median / min / max over ``reps`` windows of ``steps`` steps, in this process order with the same warm-up:
   module   the user-facing step: BoostedFlow(args) in train mode, model.component_forward(x, 0, noise), nll = -mean(ll), nll.backward()
@@ -11,7 +12,9 @@ Three lines, each the median / min / max over ``reps`` windows of ``steps`` step
   library  native.NativeImageTrainer forward + backward alone with a hand-made seed (no 1x1 log-determinants, no prior, no autograd):
            the kernels' share of the module line, NOT comparable with the eager line
 plus the arithmetic floor (3 x the forward's multiply-adds at the 155 TF/s f32-MFMA peak).  Per-kernel times: run it under
-`rocprofv3 --kernel-trace --stats -- python tools/bench_image_train.py --skip-eager --reps 1` (a run of its own)."""
+`rocprofv3 --kernel-trace --stats -- python tools/bench_image_train.py --skip-eager --reps 1` (a run of its own).
+``--deterministic``: the module and library lines in the image trainer's deterministic mode (ordered weight-gradient and log-det sums);
+the output then also carries the forward / backward workspace bytes of both modes."""
 import argparse
 import json
 import os
@@ -58,6 +61,7 @@ def main():
     ap.add_argument("--L", type=int, default=2)
     ap.add_argument("--hidden", type=int, default=256)
     ap.add_argument("--skip-eager", action="store_true")
+    ap.add_argument("--deterministic", action="store_true")
     a = ap.parse_args()
     dev = torch.device("cuda:0")
     sp = synth.synth_image_glow_spec((3, 32, 32), h=a.hidden, K=a.K, L=a.L, seed=3)
@@ -65,13 +69,13 @@ def main():
     xd, nd = torch.from_numpy(x).to(dev), torch.from_numpy(noise).to(dev)
     macs = native.NativeImageFlow(sp, math="f32").macs_per_image
     out = {"workload": f"image train step 3x32x32 K={a.K} L={a.L} h={a.hidden} batch={a.batch}", "steps": a.steps, "reps": a.reps,
-           "warmup": a.warmup, "floor_ms": 1e3 * 3 * 2 * macs * a.batch / 155e12}
+           "warmup": a.warmup, "deterministic": bool(a.deterministic), "floor_ms": 1e3 * 3 * 2 * macs * a.batch / 155e12}
 
     args = argparse.Namespace(
         num_flows=a.K, z_size=3072, density_evaluation=True, device=dev, cuda=True, component_type="glow", num_components=1,
         rho_init="decreasing", learn_top=True, y_classes=0, y_condition=False, sample_size=4, input_size=[3, 32, 32], h_size=a.hidden,
         num_blocks=a.L, actnorm_scale=1.0, flow_permutation="invconv", flow_coupling="affine", LU_decomposed=False,
-        num_dequant_blocks=0, coupling_network="tanh", coupling_network_depth=1, batch_norm=False)
+        num_dequant_blocks=0, coupling_network="tanh", coupling_network_depth=1, batch_norm=False, image_deterministic=bool(a.deterministic))
     m = BoostedFlow(args)
     image_glow.load_image_spec(m.flows[0], sp)
     m.train()
@@ -94,7 +98,12 @@ def main():
         out["eager"]["images_per_s"] = 1e3 * a.batch / out["eager"]["ms_median"]
         out["module_over_eager"] = out["eager"]["ms_median"] / out["module"]["ms_median"]
 
-    tr = native.NativeImageTrainer(igo.dev_spec(sp, dev))
+    tr = native.NativeImageTrainer(igo.dev_spec(sp, dev), deterministic=a.deterministic)
+    if a.deterministic:
+        out["workspace_bytes"] = tr.workspace_bytes(a.batch)
+        tr.deterministic = False
+        out["workspace_bytes_default"] = tr.workspace_bytes(a.batch)
+        tr.deterministic = True
     g_ldj = torch.full((a.batch,), -1.0 / a.batch, device=dev)
     flat = torch.zeros(tr.grad_floats, device=dev)
 
