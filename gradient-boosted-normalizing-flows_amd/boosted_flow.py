@@ -493,6 +493,46 @@ class BoostedFlow(nn.Module):
         x, _ = self.component_inverse(z, c)
         return x
 
+    @torch.no_grad()
+    def sample(self, n=None, *, temperature=None, n_used=None, z=None, uniforms=None, generator=None, return_components=False,
+               return_log_prob=False):
+        """Rows of the MIXTURE ``log_prob`` evaluates: every row through a component of its own, drawn from ``rho[0:n_used]`` -- what the
+        TODO of models/boosted_flow.py:209-218 asks for, where ``decode`` sends all rows through ONE drawn component.  The draw is
+        ``_sample_component("1:c")``'s multinomial over rho[0:n_used] / sum, per row and on the caller's ``uniforms`` (n,) in [0,1)
+        (``native.resample_rows``' rule); the rows are partitioned by component on the device and each component's rows are one
+        ``component_inverse``-like launch (``native.mixture_sample``: one host read of the segment sizes).  Defaults follow ``decode``:
+        n = ``args.sample_size``, z = randn(n, z_size) * temperature, uniforms = rand(n) (both from ``generator``), n_used as ``log_prob``.
+        Returns x (n,d), then ``comp`` (n,) int32 with ``return_components`` and ``log_prob(x, n_used)`` with ``return_log_prob``."""
+        n_used = self._n_used(n_used)
+        dev = self.rho.device
+        if z is not None:
+            n = z.shape[0]
+        elif uniforms is not None and n is None:
+            n = uniforms.shape[0]
+        n = int(self.args.sample_size) if n is None else int(n)
+        if z is None:
+            t = 1.0 if temperature is None else float(temperature)
+            z = torch.randn(n, self.z_size, device=dev, dtype=torch.float32, generator=generator) * t
+        if uniforms is None:
+            uniforms = torch.rand(n, device=dev, dtype=torch.float32, generator=generator)
+        self._check_ready(z)
+        z = z.contiguous().float()
+        uniforms = uniforms.contiguous().float()
+        if z.dim() != 2 or z.shape != (n, self.z_size) or uniforms.shape != (n,):
+            raise ValueError(f"z must be ({n},{self.z_size}) and uniforms ({n},), got {tuple(z.shape)} and {tuple(uniforms.shape)}")
+        for c in range(n_used):
+            if not all(bool(l.actnorm.inited) for l in getattr(getattr(self.flows[c], "flow", None), "layers", [])):
+                raise ValueError("ActNorm not initiated: run a forward pass on data first (models/layers.py:473-475)")
+        with torch.cuda.device(z.device):
+            flows = [self.native_flow(c) for c in range(n_used)]
+            x, _, comp = native.mixture_sample(flows, self.rho.contiguous().float(), uniforms, z, n_used=n_used, want_ldj=False)
+        out = (x,)
+        if return_components:
+            out += (comp,)
+        if return_log_prob:
+            out += (self.log_prob(x, n_used),)
+        return out[0] if len(out) == 1 else out
+
     def forward(self, x=None, y_onehot=None, z=None, temperature=None, components=None, reverse=False):
         if reverse:
             return self.decode(z, y_onehot, temperature, components)

@@ -184,6 +184,11 @@ def main(argv=None):
     objs.append(boost_o)
     if args.force or not newer(boost_o, [boost_src, opt_hdr, hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", boost_src, "-o", boost_o])
+    # drawing from the mixture (per-row component draw, stable partition by component, gather / scatter around per-segment inverses): gbnf_sample.hip
+    sample_o, sample_src = os.path.join(OBJ, "gbnf_sample.o"), os.path.join(HERE, "gbnf_sample.hip")
+    objs.append(sample_o)
+    if args.force or not newer(sample_o, [sample_src, hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", sample_src, "-o", sample_o])
     # boosting for image components (one update_rho iteration, the boosted step with its fixed-mixture term): gbnf_image_boost.hip
     iboost_o, iboost_src = os.path.join(OBJ, "gbnf_image_boost.o"), os.path.join(HERE, "gbnf_image_boost.hip")
     objs.append(iboost_o)

@@ -169,6 +169,12 @@ int mixture_shape(const gbnf_mixture* mix, int* n_components, int* d) {
   return GBNF_OK;
 }
 
+int flow_features(const gbnf_flow* flow, int* d) {
+  if (!flow) return fail(GBNF_ERR_INVALID, "flow_features: flow is null");
+  *d = flow->d;
+  return GBNF_OK;
+}
+
 // ---- launch-policy knobs (gbnf_tuning_set / _get; initialised from the environment at first use)
 struct Tuning {
   std::atomic<int> force_nt{0}, wg_pairs{-1}, repair{1}, nt2_min_waves{1024}, check_every{256}, check_tolerance_e9{2500};

@@ -22,6 +22,8 @@ unsigned* training_saturation_counter();
 
 // How many components a mixture holds and their feature count, for the translation units that do not see the handle (gbnf_boost.hip)
 int mixture_shape(const gbnf_mixture* mix, int* n_components, int* d);
+// ... and one component's feature count (gbnf_sample.hip)
+int flow_features(const gbnf_flow* flow, int* d);
 
 // The tail of one update_rho iteration (gbnf_boost.hip: rho_partial_kernel + rho_finalize_kernel through the current device's
 // partial-sum buffer) on a (component + 1, n) DEVICE table of per-component log-likelihoods: what gbnf_mixture_rho_step and

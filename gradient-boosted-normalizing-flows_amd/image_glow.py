@@ -721,6 +721,51 @@ class BoostedImageFlow(nn.Module):
         with torch.cuda.device(z.device):
             return handle.inverse(z.contiguous().float(), eps, temperature)
 
+    @torch.no_grad()
+    def sample(self, n=None, *, temperature=1.0, n_used=None, e=None, eps=None, uniforms=None, generator=None, return_components=False):
+        """Images of the MIXTURE: every row through a component of its own, drawn from ``rho[0:n_used]`` per row on ``uniforms`` (n,)
+        (BoostedFlow.sample; the sample(model, args) of image_experiment.py:280-293 draws one component for all rows).  ``e``: the
+        standard-normal draws behind the top latents, (n,) + z_shape: rows of component c get z = mu_c + exp(lv_c) * temperature * e[rows],
+        ``decode``'s formula; ``eps``: the Split2d draws, one (n, ...) tensor per level as ``decode`` takes them.  The draw and the
+        partition run on the device (native.mixture_partition, one host read of the segment sizes); each component's rows are one
+        ``native_flow(c).inverse`` call, gathered and written back by torch indexing.  Defaults: n = ``sample_size``, e / eps / uniforms
+        from ``generator``, n_used = the trained components.  Returns x (n,C,H,W), and ``comp`` (n,) int32 with ``return_components``."""
+        if n_used is None:
+            n_used = self.num_components if self.all_trained else self.component + 1
+        n_used = int(n_used)
+        if not 1 <= n_used <= self.num_components:
+            raise ValueError(f"n_used={n_used} outside [1, {self.num_components}]")
+        temperature = 1.0 if temperature is None else float(temperature)
+        dev = self.rho.device
+        handles = [self.native_flow(c) for c in range(n_used)]
+        for given in (e, uniforms) + tuple(eps or ()):
+            if given is not None and n is None:
+                n = given.shape[0]
+        n = int(self.flows[0].sample_size) if n is None else int(n)
+        if e is None:
+            e = torch.randn((n,) + tuple(handles[0].z_shape), device=dev, dtype=torch.float32, generator=generator)
+        if eps is None:
+            eps = [torch.randn((n,) + sh, device=dev, dtype=torch.float32, generator=generator) for sh in handles[0].split_shapes()]
+        if uniforms is None:
+            uniforms = torch.rand(n, device=dev, dtype=torch.float32, generator=generator)
+        self._check(e)
+        if e.shape != (n,) + tuple(handles[0].z_shape) or uniforms.shape != (n,) or any(t.shape[0] != n for t in eps):
+            raise ValueError(f"e must be {(n,) + tuple(handles[0].z_shape)}, uniforms ({n},) and every eps tensor ({n}, ...)")
+        e = e.contiguous().float()
+        with torch.cuda.device(e.device):
+            comp, order, counts, _ = native.mixture_partition(self.rho.contiguous().float(), uniforms.contiguous().float(), n_used)
+            x = torch.empty((n,) + tuple(handles[0].input_size), dtype=torch.float32, device=e.device)
+            begin = 0
+            for c, m in enumerate(counts.cpu().tolist()):
+                if m == 0:
+                    continue
+                rows = order[begin:begin + m]
+                begin += m
+                mu, lv = self._prior_on(handles[c], e.device)
+                z_c = mu + torch.exp(lv) * temperature * e[rows]
+                x[rows] = handles[c].inverse(z_c.contiguous(), [t[rows].contiguous().float() for t in eps], temperature)
+        return (x, comp) if return_components else x
+
     def forward(self, x=None, y_onehot=None, z=None, temperature=None, components=None, reverse=False):
         if reverse:
             return self.decode(z, y_onehot, temperature, components)

@@ -52,6 +52,7 @@ ABI_SYMBOLS = (
     "gbnf_image_trainer_step_workspace_bytes", "gbnf_image_trainer_apply_update", "gbnf_image_trainer_nll_step",
     "gbnf_image_rho_step_workspace_bytes", "gbnf_image_mixture_rho_step",
     "gbnf_image_boosted_step_workspace_bytes", "gbnf_image_boosted_nll_step",
+    "gbnf_mixture_sample_workspace_bytes", "gbnf_mixture_sample_begin", "gbnf_mixture_sample_finish",
 )
 
 
@@ -246,6 +247,9 @@ def lib():
     L.gbnf_image_mixture_rho_step.argtypes = [C.POINTER(vp), i32, vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp]
     L.gbnf_image_boosted_step_workspace_bytes.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.gbnf_image_boosted_nll_step.argtypes = [vp, C.c_float, vp, vp, vp, i64, C.c_float, vp, vp, vp, C.POINTER(_OptHyper), vp, vp, i64, vp]
+    L.gbnf_mixture_sample_workspace_bytes.argtypes = [i32, i64, i32, C.POINTER(i64)]
+    L.gbnf_mixture_sample_begin.argtypes = [vp, i32, vp, vp, i64, i32, vp, vp, vp, vp, i64, vp]
+    L.gbnf_mixture_sample_finish.argtypes = [C.POINTER(vp), i32, C.POINTER(i64), vp, i64, vp, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -1815,3 +1819,74 @@ def resample_rows(w, u):
     _check(lib().gbnf_resample_rows(C.c_void_p(w.data_ptr()), w.numel(), C.c_void_p(u.data_ptr()), u.numel(),
                                     C.c_void_p(rows.data_ptr()), C.c_void_p(cdf.data_ptr()), nb.value, _stream_ptr()))
     return rows
+
+
+_sample_ws = {}        # device -> workspace of mixture_partition / mixture_sample (grown to the largest call so far)
+
+
+def _sample_workspace(n_flows, n, d, device):
+    import torch
+    nb = C.c_int64()
+    _check(lib().gbnf_mixture_sample_workspace_bytes(int(n_flows), int(n), int(d), C.byref(nb)))
+    ws = _sample_ws.get(str(device))
+    if ws is None or ws.numel() * 4 < nb.value:
+        ws = _sample_ws[str(device)] = torch.empty(nb.value // 4, dtype=torch.float32, device=device)
+    return ws, nb.value
+
+
+def mixture_partition(rho, u, n_used=None, z=None):
+    """The first phase of drawing from the mixture (gbnf_mixture_sample_begin): a component per row from ``rho[0:n_used]`` and the uniforms
+    ``u`` (n,) by the rule of ``resample_rows``, the rows partitioned by component -> (comp (n,) int32, order (n,) int64, counts (n_used,)
+    int64, workspace), all on the device and nothing read back.  ``order`` lists the rows of component 0 in ascending index, then those
+    of component 1, ...; with ``z`` (n,d) the workspace holds its rows in that order, segment by segment, for ``mixture_sample``."""
+    import torch
+    _require_device_f32(rho, "rho")
+    _require_device_f32(u, "u")
+    n_used = rho.numel() if n_used is None else int(n_used)
+    if rho.dim() != 1 or not 1 <= n_used <= rho.numel():
+        raise GbnfError(f"rho must be (C,) with 1 <= n_used <= C, got {tuple(rho.shape)} and n_used = {n_used}")
+    if u.dim() != 1 or u.numel() < 1:
+        raise GbnfError("u must be (n,) with n >= 1")
+    n, d = u.numel(), 1
+    if z is not None:
+        _require_device_f32(z, "z")
+        if z.dim() != 2 or z.shape[0] != n or z.shape[1] < 1:
+            raise GbnfError(f"z must be ({n},d), got {tuple(z.shape)}")
+        d = z.shape[1]
+    ws, nb = _sample_workspace(n_used, n, d, u.device)
+    comp = torch.empty(n, dtype=torch.int32, device=u.device)
+    order = torch.empty(n, dtype=torch.int64, device=u.device)
+    counts = torch.empty(n_used, dtype=torch.int64, device=u.device)
+    _check(lib().gbnf_mixture_sample_begin(C.c_void_p(rho.data_ptr()), n_used, C.c_void_p(u.data_ptr()),
+                                           C.c_void_p(z.data_ptr() if z is not None else 0), n, d, C.c_void_p(comp.data_ptr()),
+                                           C.c_void_p(order.data_ptr()), C.c_void_p(counts.data_ptr()), C.c_void_p(ws.data_ptr()), nb,
+                                           _stream_ptr()))
+    return comp, order, counts, ws
+
+
+def mixture_sample(flows, rho, u, z, n_used=None, want_ldj=True, out=None):
+    """Rows of the boosted MIXTURE from latent rows: row i goes backwards through the component drawn for it from ``rho[0:n_used]`` by
+    ``u[i]`` (the rule of ``resample_rows``) -> (x (n,d), log|det dx/dz| (n,) | None, comp (n,) int32).  ``flows``: the components'
+    ``NativeFlow`` handles, at least n_used of them; ``rho`` (C,), ``u`` (n,), ``z`` (n,d): float32 on the device.  ``out``: the x buffer
+    (it may be ``z`` itself).  gbnf_mixture_sample_begin, ONE host read of the n_used segment sizes (where the reference has the
+    ``.item()`` of its draw), gbnf_mixture_sample_finish: every component's rows are one ``gbnf_flow_inverse`` call."""
+    import torch
+    n_used = len(flows) if n_used is None else int(n_used)
+    if not 1 <= n_used <= len(flows):
+        raise GbnfError(f"n_used = {n_used} outside [1, {len(flows)}]")
+    if z is None:
+        raise GbnfError("z must be (n,d)")
+    comp, order, counts, ws = mixture_partition(rho, u, n_used, z)
+    n, d = z.shape
+    if any(f.d != d for f in flows[:n_used]):
+        raise GbnfError(f"every flow must have d = {d}")
+    x = torch.empty_like(z) if out is None else _require_device_f32(out, "out")
+    if tuple(x.shape) != (n, d):
+        raise GbnfError(f"out must be ({n},{d}), got {tuple(x.shape)}")
+    ldj = torch.empty(n, dtype=torch.float32, device=z.device) if want_ldj else None
+    handles = (C.c_void_p * n_used)(*[f.handle for f in flows[:n_used]])
+    host = (C.c_int64 * n_used)(*counts.cpu().tolist())
+    _check(lib().gbnf_mixture_sample_finish(handles, n_used, host, C.c_void_p(order.data_ptr()), n, C.c_void_p(x.data_ptr()),
+                                            C.c_void_p(ldj.data_ptr() if ldj is not None else 0), C.c_void_p(ws.data_ptr()),
+                                            ws.numel() * 4, _stream_ptr()))
+    return x, ldj, comp

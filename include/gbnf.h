@@ -873,6 +873,52 @@ int gbnf_image_boosted_nll_step(const gbnf_image_flow* fixed, float g_floor, gbn
                                 const gbnf_opt_hyper* hyper, float* stats_dev, void* workspace, int64_t workspace_bytes,
                                 void* stream);
 
+/* ---- drawing from the mixture ----------------------------------------------------------------------------------------------------
+ * Replaces: BoostedFlow.decode (models/boosted_flow.py:209-218), which sends ALL rows of a call through ONE component drawn on the
+ * host by _sample_component("1:c") (:61-96: torch.multinomial(rho[0:c] / sum, 1).item()) and says so itself ("rewrite this so that
+ * samples can be taking from all components, not just many samples from a randomly chosen component") -- and what a user writes in
+ * eager PyTorch to get samples of the density gbnf_mixture_log_prob evaluates: a per-row draw, a boolean-mask loop over the
+ * components, a scatter back.  Every row gets a component of its OWN, the rows are partitioned by component on the device, and each
+ * component's rows go through gbnf_flow_inverse as one contiguous batch: that call's math mode, repair pass and z -> x guard apply to
+ * a segment exactly as to a caller's batch of the same rows, and no flow kernel knows about any of this.
+ *
+ * The draw is gbnf_resample_rows on w = rho_dev[0:n_used] and the CALLER's uniforms u (n DEVICE floats in [0,1)):
+ *   cdf_c = sum_{k <= c} max(rho_k, 0) in double precision, in index order;  T = cdf_{n_used-1};
+ *   comp[i] = the smallest c with (double)u[i] * T < cdf_c.
+ * A component of zero weight is never drawn; out-of-contract u (>= 1, NaN) and T == 0 behave as documented there, so every comp[i]
+ * lies in [0, n_used).  The partition is a stable counting sort without float arithmetic (per-chunk integer histograms, a
+ * one-workgroup scan, ranks by wave ballot): comp, order and counts are bit-identical from run to run.
+ *
+ * Two phases, neither of which waits for the device (both can be captured): the segment sizes have to reach the HOST between them,
+ * because gbnf_flow_inverse takes its row count by value -- the one host read of the path, where the reference has its .item().
+ *
+ * gbnf_mixture_sample_begin   the draw, the partition and the gather.  Outputs, all DEVICE memory:
+ *     comp (n int32)        the component of row i;
+ *     order (n int64)       position -> caller's row: the rows of component 0 in ascending caller index, then those of component 1, ...
+ *                           (while the call runs, `order` also holds the draw's int64 result);
+ *     counts_dev (n_used int64)  rows per component.
+ *   z_or_null: (n,d) latent rows, copied into the workspace segment by segment; NULL skips that (the image path partitions with this
+ *   call and runs its own inverses): d then only sizes the workspace, 1 will do.
+ * gbnf_mixture_sample_finish  for every component with counts_host[c] > 0: gbnf_flow_inverse(flows[c]) on its segment; then the scatter,
+ *   x[order[q]] / ldj[order[q]] = the sorted rows.  counts_host: the HOST copy of counts_dev; order: as begin left it; the SAME
+ *   workspace, untouched in between; n_flows must equal begin's n_used (the first n_used handles): the workspace is laid out by it.
+ *   x may be the buffer z was (the gather has consumed it in stream order); ldj_or_null NULL: no log|det dx/dz|.
+ *
+ * Segment c starts at row start_c of the sorted buffers, start_0 = 0, start_c = roundup64(start_{c-1} + counts[c-1]): a 256-byte
+ * boundary for every d, what the flow kernels have always been handed.  Padding rows are never read back.
+ * workspace: gbnf_mixture_sample_workspace_bytes(n_flows, n, d) of DEVICE memory, 256-byte aligned: with R = n + 64 n_flows rows and
+ * B = ceil(n / 1024) chunks, in this order, each rounded up to 256 bytes:  sorted z (4 R d) | sorted x (4 R d) | sorted ldj (4 R) |
+ * chunk histograms (8 B n_flows) | the draw's cdf (8 n_flows; later the segments' padding).
+ * GBNF_ERR_INVALID (nothing launched): a null pointer (z_or_null / ldj_or_null excepted), n < 1, n_used < 1, n_flows < 1, d < 1,
+ * counts_host that do not sum to n (or hold a negative entry), flows whose d differ, a short workspace.  GBNF_ERR_UNSUPPORTED: more
+ * than 1024 components (the partition keeps one counter per component and wave in LDS). */
+int gbnf_mixture_sample_workspace_bytes(int32_t n_flows, int64_t n, int32_t d, int64_t* bytes);
+int gbnf_mixture_sample_begin(const float* rho_dev, int32_t n_used, const float* u, const float* z_or_null, int64_t n, int32_t d,
+                              int32_t* comp, int64_t* order, int64_t* counts_dev, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+int gbnf_mixture_sample_finish(gbnf_flow* const* flows, int32_t n_flows, const int64_t* counts_host, const int64_t* order, int64_t n,
+                               float* x, float* ldj_or_null, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
