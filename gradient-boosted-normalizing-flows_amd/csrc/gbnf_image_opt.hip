@@ -464,6 +464,18 @@ void image_step_state_destroy(ImageStepState* s) {
   delete s;
 }
 
+int image_step_compose(const gbnf_image_trainer* t, void* stream) {
+  const ImageStepState* st = t->step;
+  if (!st) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_actnorm_init: trainer is null");
+  if (st->lu.empty()) return GBNF_OK;
+  if (!st->ready) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_actnorm_init: the last bind call failed: bind again first");
+  if (mix_allow_lds() != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_image_trainer_actnorm_init: the 1x1 kernels' LDS opt-in failed");
+  MixLaunch mq{};
+  mq.steps = st->mix_dev; mq.n_mix = st->n_mix; mq.ld = ld_sums(st); mq.k = 1.0f;
+  hipLaunchKernelGGL((img_mix_logdet_kernel<0>), dim3((unsigned)st->n_mix), dim3(IOPT_THREADS), MIX_LDS_BYTES, (hipStream_t)stream, mq);
+  return GBNF_OK;
+}
+
 }  // namespace gbnf
 
 using namespace gbnf;

@@ -28,6 +28,9 @@ struct TConv {
 struct ImageStepState;
 int image_step_state_create(gbnf_image_trainer* t);
 void image_step_state_destroy(ImageStepState* s);
+// step 1 of gbnf_image_trainer_nll_step for gbnf_image_trainer_actnorm_init: with LU factors bound, the 1x1 matrices are composed
+// into their bound tensors on `stream` (the same launch); nothing bound: nothing launched
+int image_step_compose(const gbnf_image_trainer* t, void* stream);
 
 }  // namespace gbnf
 
@@ -42,6 +45,8 @@ struct gbnf_image_trainer {
   std::vector<int> step_convs;                 // convolutions of a step's net
   std::vector<int> split_entry;                // [level] -> entry or -1
   gbnf::TConv* table_dev = nullptr;
+  gbnf::TConv* ident_dev = nullptr;            // the table with every ActNorm2d behind a Conv2d taken out (null arrays): the identity tiles
+                                               // gbnf_image_trainer_actnorm_init packs for a layer it has yet to initialise
   float* blob_dev = nullptr;                   // packs; [zero_off, zero_off + 1024): zeros (bias of the adjoint launches, the prior)
   float* perm_dev = nullptr;                   // the 0/1 matrices of Permute2d steps
   int64_t blob_floats = 0, zero_off = 0, scratch_floats = 0, grad_floats = 0;

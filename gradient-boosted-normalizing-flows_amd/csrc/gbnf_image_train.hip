@@ -13,6 +13,10 @@
 //             transposed tiles: the adjoint of a stride-1 'same' convolution is one; its Hv / Wv masking keeps the outside of the map
 //             zero as the forward does).
 //   unfold    ONE launch maps (dW', db') of the folded convolutions and (dW_eff, db_eff) of the mixes to the descriptor's arrays.
+//   init      gbnf_image_trainer_actnorm_init: the data-dependent ActNorm2d initialisation of every layer in ONE walk of the forward.
+//             At a layer to initialise: (a coupling-net layer: its convolution once on identity tiles, store epilogue) -> per-channel
+//             sums and centred squares over chunks of images in f64 (img_train_an_stats_kernel, grid chunks x channels) -> the finish
+//             launch adds the chunks in order and writes bias / logs into the live tensors -> the pack kernel on that one entry.
 //
 // Weight gradient: dW'[o][i][tap] = sum_{n,p} G[o][n,p] A[i][n,p+tap] on v_mfma_f32_16x16x4_f32, contracting over pixels.  A workgroup
 // owns a block of (output tile, input tile) pairs of dW' and a slice of the (image, strip) items: per item it stages the gradient strip
@@ -225,6 +229,71 @@ __global__ void __launch_bounds__(256) img_train_wgrad_reduce_kernel(const float
   }
   for (; y < slices; ++y) acc += src[(int64_t)y * part_stride];
   dst[e] = acc;
+}
+
+// ---- data-dependent ActNorm2d initialisation (gbnf_image_trainer_actnorm_init; models/layers.py:473-486) ---------------------
+// Per-channel statistics over (n, the map proper) of a tensor t (n, C.., H, W), H x W = 16 x 16 | 8 x 8 storage: grid (chunks,
+// channels), a chunk = `per_chunk` consecutive images.  A wave reads whole channel maps, one float4 per lane: one 16 x 16 map or
+// four 8 x 8 maps (of four images) at a time, the four waves of the workgroup on consecutive groups of images.  Only rows < Hv,
+// columns < Wv count; nothing outside them is used.  Two passes, as the reference: PASS 0 the sums, PASS 1 the squares centred on
+// the mean every workgroup re-adds from PASS 0's partials.  All sums are doubles in a fixed order -- a lane over its images, the
+// xor tree of the wave, the four waves in order, the chunks in order (the consumer) --, every partial is a plain store.
+constexpr int AN_MAX_CHUNKS = 64;
+struct AnStats {
+  const float* t; int64_t t_img;     // first channel of image 0, floats between images
+  int64_t n;
+  int HW, W, Hv, Wv;
+  int per_chunk, chunks;
+  double* sum;                       // [channel][chunk]: PASS 0 writes, PASS 1 reads
+  double* sq;                        // [channel][chunk]: PASS 1 writes
+};
+
+template <int PASS>
+__global__ void __launch_bounds__(256) img_train_an_stats_kernel(const AnStats p) {
+  __shared__ double red[4];
+  const int chunk = blockIdx.x, c = blockIdx.y;
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int lpm = p.HW >> 2, mpw = 64 / lpm;                 // lanes of a map (64 | 16), maps a wave reads at a time (1 | 4)
+  const int sub = lane / lpm, e = (lane - sub * lpm) * 4;    // this lane's map of the group, its first element there
+  const int y = e / p.W, x0 = e - y * p.W;                   // (W is a multiple of 4: the four elements share a row)
+  double mean = 0.0;
+  if (PASS == 1) {
+    double s = 0.0;
+    for (int k = 0; k < p.chunks; ++k) s += p.sum[(int64_t)c * p.chunks + k];
+    mean = s / ((double)p.n * p.Hv * p.Wv);
+  }
+  const int64_t first = (int64_t)chunk * p.per_chunk, last = first + p.per_chunk < p.n ? first + p.per_chunk : p.n;
+  double acc = 0.0;
+  if (y < p.Hv) {
+    for (int64_t i = first + wave * mpw + sub; i < last; i += 4 * mpw) {
+      const f32x4 v = *reinterpret_cast<const f32x4*>(p.t + i * p.t_img + (int64_t)c * p.HW + e);
+#pragma unroll
+      for (int r = 0; r < 4; ++r) {
+        if (x0 + r < p.Wv) {
+          const double d = (double)v[r] - mean;              // (PASS 0: mean = 0)
+          acc += PASS == 0 ? d : d * d;
+        }
+      }
+    }
+  }
+#pragma unroll
+  for (int m = 1; m < 64; m <<= 1) acc += __shfl_xor(acc, m);
+  if (lane == 0) red[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) (PASS == 0 ? p.sum : p.sq)[(int64_t)c * p.chunks + chunk] = ((red[0] + red[1]) + red[2]) + red[3];
+}
+
+// one thread per channel: the chunks' partials in chunk order -> bias = -mean, logs = log(scale / (sqrt(var) + 1e-6)) into the live tensors
+__global__ void __launch_bounds__(256) img_train_an_finish_kernel(const double* __restrict__ sum, const double* __restrict__ sq, int chunks, int C,
+                                                                  double total, float scale, float* __restrict__ bias, float* __restrict__ logs) {
+  const int c = blockIdx.x * 256 + threadIdx.x;
+  if (c >= C) return;
+  double s = 0.0, q = 0.0;
+  for (int k = 0; k < chunks; ++k) s += sum[(int64_t)c * chunks + k];
+  for (int k = 0; k < chunks; ++k) q += sq[(int64_t)c * chunks + k];
+  const double mean = s / total, var = q / total;
+  bias[c] = (float)-mean;
+  logs[c] = (float)log((double)scale / (sqrt(var) + 1e-6));
 }
 
 // ---- unfold: grid (512 / 4, entries); one WAVE per output channel (mix: per input channel), lanes along the row: coalesced ------
@@ -462,6 +531,7 @@ int gbnf_image_trainer_get_deterministic(const gbnf_image_trainer* t, int32_t* o
 int gbnf_image_trainer_destroy(gbnf_image_trainer* t) {
   if (!t) return GBNF_OK;
   if (t->table_dev) (void)hipFree(t->table_dev);
+  if (t->ident_dev) (void)hipFree(t->ident_dev);
   if (t->blob_dev) (void)hipFree(t->blob_dev);
   if (t->perm_dev) (void)hipFree(t->perm_dev);
   image_step_state_destroy(t->step);
@@ -567,6 +637,13 @@ int gbnf_image_trainer_create(const gbnf_image_flow_desc* d, gbnf_image_trainer*
     }
     if (e == hipSuccess) e = hipMalloc((void**)&t->table_dev, t->table.size() * sizeof(TConv));
     if (e == hipSuccess) e = hipMemcpy(t->table_dev, t->table.data(), t->table.size() * sizeof(TConv), hipMemcpyHostToDevice);
+    if (e == hipSuccess) {
+      std::vector<TConv> ident(t->table);
+      for (TConv& c : ident)
+        if (!c.mix) c.an_bias = c.an_logs = nullptr;
+      e = hipMalloc((void**)&t->ident_dev, ident.size() * sizeof(TConv));
+      if (e == hipSuccess) e = hipMemcpy(t->ident_dev, ident.data(), ident.size() * sizeof(TConv), hipMemcpyHostToDevice);
+    }
     if (e == hipSuccess) e = hipMalloc((void**)&t->blob_dev, (size_t)t->blob_floats * 4);
     if (e == hipSuccess) e = hipMemset(t->blob_dev, 0, (size_t)t->blob_floats * 4);
     if (e == hipSuccess) e = img_allow_lds();
@@ -696,6 +773,140 @@ int gbnf_image_trainer_forward(gbnf_image_trainer* t, const float* x, const floa
   }
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_image_trainer_forward: %s", hipGetErrorString(e));
+  return GBNF_OK;
+}
+
+// ---- gbnf_image_trainer_actnorm_init ------------------------------------------------------------------------------------------
+// workspace: state S0 | S1 | hidden A0 | A1 (n images each) | a log-det sink (n; the epilogues add into it, nobody reads it) |
+// doubles: the statistics partials [2][widest layer][AN_MAX_CHUNKS]
+struct AnSpace {
+  float* S[2]; float* A[2]; float* ldj; double* part;
+  int64_t part_each;                 // doubles of one of the two partial arrays
+  int64_t bytes;
+};
+static AnSpace an_space(const gbnf_image_trainer* t, void* ws, int64_t n) {
+  AnSpace s{};
+  const int64_t hid = (int64_t)((t->hidden + 15) / 16 * 16) * 256 * n, st = t->state_img * n;
+  float* base = reinterpret_cast<float*>(((uintptr_t)ws + 255) & ~(uintptr_t)255);
+  float* p = base;
+  for (int k = 0; k < 2; ++k) { s.S[k] = p; p += (st + 63) / 64 * 64; }
+  for (int k = 0; k < 2; ++k) { s.A[k] = p; p += hid; }
+  s.ldj = p; p += (n + 63) / 64 * 64;
+  s.part = reinterpret_cast<double*>(p);
+  s.part_each = (int64_t)std::max(t->hidden, 64) * AN_MAX_CHUNKS;
+  s.bytes = (p - base) * 4 + 2 * s.part_each * 8 + 256;
+  return s;
+}
+
+// t (n, C.., H, W of lv) -> bias / logs (the live tensors): sums, centred squares, finish
+static void an_launch_stats(const gbnf_image_trainer::Level& lv, const float* tin, int64_t t_img, int C, int64_t n, float scale, const AnSpace& sp,
+                            const float* bias, const float* logs, hipStream_t s) {
+  AnStats p{};
+  p.t = tin; p.t_img = t_img; p.n = n; p.HW = lv.H * lv.W; p.W = lv.W; p.Hv = lv.Hv; p.Wv = lv.Wv;
+  const int64_t group = 4 * (256 / p.HW);                      // images the four waves of a workgroup read at a time
+  const int64_t want = std::min<int64_t>(AN_MAX_CHUNKS, (n + group - 1) / group);
+  p.per_chunk = (int)(((n + want - 1) / want + group - 1) / group * group);
+  p.chunks = (int)((n + p.per_chunk - 1) / p.per_chunk);       // (<= want: a function of n and the map's storage only)
+  p.sum = sp.part; p.sq = sp.part + sp.part_each;
+  const dim3 grid((unsigned)p.chunks, (unsigned)C), blk(256);
+  hipLaunchKernelGGL((img_train_an_stats_kernel<0>), grid, blk, 0, s, p);
+  hipLaunchKernelGGL((img_train_an_stats_kernel<1>), grid, blk, 0, s, p);
+  hipLaunchKernelGGL(img_train_an_finish_kernel, dim3((unsigned)((C + 255) / 256)), blk, 0, s, (const double*)p.sum, (const double*)p.sq, p.chunks, C,
+                     (double)n * lv.Hv * lv.Wv, scale, const_cast<float*>(bias), const_cast<float*>(logs));
+}
+
+int gbnf_image_trainer_actnorm_count(const gbnf_image_trainer* t, int32_t* count) {
+  if (!t || !count) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_actnorm_count: bad argument");
+  int total = 0;
+  for (const auto& lv : t->levels) total += lv.K * t->n_net;    // a step's own + one behind each Conv2d (all but the last convolution)
+  *count = total;
+  return GBNF_OK;
+}
+
+int gbnf_image_trainer_actnorm_init_workspace_bytes(const gbnf_image_trainer* t, int64_t n, int64_t* bytes) {
+  if (!t || !bytes || n < 0) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_actnorm_init_workspace_bytes: bad argument");
+  *bytes = an_space(t, nullptr, n).bytes;
+  return GBNF_OK;
+}
+
+int gbnf_image_trainer_actnorm_init(gbnf_image_trainer* t, const float* x, const float* noise, int64_t n, float scale, const uint8_t* skip,
+                                    void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* fn = "gbnf_image_trainer_actnorm_init";
+  if (!t || !x) return fail(GBNF_ERR_INVALID, "%s: trainer / x is null", fn);
+  if (n < 1) return fail(GBNF_ERR_INVALID, "%s: n = %lld < 1", fn, (long long)n);
+  if (!std::isfinite(scale) || !(scale > 0.0f)) return fail(GBNF_ERR_INVALID, "%s: scale must be finite and > 0", fn);
+  if (n > 65535) return fail(GBNF_ERR_UNSUPPORTED, "%s: at most 65535 images per call", fn);
+  const AnSpace sp = an_space(t, workspace, n);
+  if (!workspace || workspace_bytes < sp.bytes)
+    return fail(GBNF_ERR_INVALID, "%s: workspace too small (gbnf_image_trainer_actnorm_init_workspace_bytes)", fn);
+  hipStream_t s = (hipStream_t)stream;
+  if (const int rc = image_step_compose(t, stream)) return rc;
+  const int n_entries = (int)t->table.size();
+  hipLaunchKernelGGL(img_train_pack_kernel, dim3(64, (unsigned)n_entries), dim3(256), 0, s, (const TConv*)t->table_dev, t->blob_dev);
+  int count = 0, todo = 0, layer = 0;
+  for (const auto& lv : t->levels) count += lv.K * t->n_net;
+  for (int q = 0; q < count; ++q) todo += (skip == nullptr || !skip[q]) ? 1 : 0;       // (none: the pack above is all there is to do)
+  auto wanted = [&](int idx) { return skip == nullptr || !skip[idx]; };
+  auto pack_one = [&](const TConv* table, int entry) {
+    hipLaunchKernelGGL(img_train_pack_kernel, dim3(64, 1), dim3(256), 0, s, table + entry, t->blob_dev);
+  };
+  float* cur = sp.S[0];
+  float* oth = sp.S[1];
+  if (todo > 0) img_launch_pre(x, noise, cur, sp.ldj, t->C, t->H, t->W, t->Hi, t->Wi, t->bounds, (float)t->ld_const, n, s);
+  for (int l = 0; l < t->L && todo > 0; ++l) {
+    const auto& lv = t->levels[l];
+    const int64_t img = (int64_t)lv.C * lv.H * lv.W;
+    const int c1 = lv.C / 2;
+    for (int k = 0; k < lv.K; ++k) {
+      const int first = t->step_first[l][k];
+      const TConv& m = t->table[first];
+      if (wanted(layer)) {                                     // the step's own ActNorm2d: the state as it stands
+        an_launch_stats(lv, cur, img, lv.C, n, scale, sp, m.an_bias, m.an_logs, s);
+        pack_one(t->table_dev, first);
+      }
+      ++layer;
+      ConvLaunch p = conv_base(lv, sp.ldj);
+      p.in = cur; p.in_img = img; p.wp = t->blob_dev + m.fwd_off; p.bias = t->blob_dev + m.b_off; p.out = oth; p.out_img = img;
+      p.cin = lv.C; p.cout = lv.C; p.ks = 1;
+      img_launch_conv(EPI_STORE, p, (int)n, s);
+      std::swap(cur, oth);
+      const float* hin = cur;
+      int64_t hin_img = img;
+      for (int q = 0; q + 1 < t->n_net; ++q, ++layer) {
+        const int entry = first + 1 + q;
+        const TConv& c = t->table[entry];
+        ConvLaunch h = conv_base(lv, nullptr);
+        h.in = hin; h.in_img = hin_img; h.wp = t->blob_dev + c.fwd_off; h.bias = t->blob_dev + c.b_off;
+        h.out = sp.A[q & 1]; h.out_img = (int64_t)c.cout * lv.H * lv.W; h.cin = c.cin; h.cout = c.cout; h.ks = c.ks;
+        if (wanted(layer)) {
+          // the raw convolution on identity tiles, its statistics into the live tensors, the real tiles; relu(ActNorm2d(conv)) below
+          pack_one(t->ident_dev, entry);
+          img_launch_conv(EPI_STORE, h, (int)n, s);
+          an_launch_stats(lv, h.out, h.out_img, c.cout, n, scale, sp, c.an_bias, c.an_logs, s);
+          pack_one(t->table_dev, entry);
+        }
+        img_launch_conv(EPI_RELU, h, (int)n, s);
+        hin = h.out; hin_img = h.out_img;
+      }
+      const TConv& c = t->table[first + t->n_net];
+      ConvLaunch q = conv_base(lv, sp.ldj);
+      q.in = hin; q.in_img = hin_img; q.wp = t->blob_dev + c.fwd_off; q.bias = t->blob_dev + c.b_off;
+      q.st = cur + (int64_t)c1 * lv.H * lv.W; q.st_img = img; q.cin = c.cin; q.cout = c.cout; q.ks = c.ks;
+      img_launch_conv(t->additive ? EPI_COUPLE_ADD : EPI_COUPLE_AFFINE, q, (int)n, s);
+    }
+    if (l < t->L - 1) {
+      const TConv& c = t->table[t->split_entry[l]];
+      ConvLaunch p = conv_base(lv, sp.ldj);
+      p.in = cur; p.in_img = img; p.wp = t->blob_dev + c.fwd_off; p.bias = t->blob_dev + c.b_off;
+      p.st = cur + (int64_t)c1 * lv.H * lv.W; p.st_img = img; p.cin = c.cin; p.cout = c.cout; p.ks = c.ks;
+      img_launch_conv(EPI_SPLIT, p, (int)n, s);
+      const auto& nx = t->levels[l + 1];
+      img_launch_squeeze(cur, img, oth, c1, lv.H, lv.W, nx.H, nx.W, n, s);
+      std::swap(cur, oth);
+    }
+  }
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
   return GBNF_OK;
 }
 

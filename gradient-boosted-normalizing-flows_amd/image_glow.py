@@ -228,6 +228,12 @@ class ImageGlow(nn.Module):
             m.inited = True
 
 
+def actnorm_skip_flags(glow):
+    """The ``skip`` argument of native.NativeImageTrainer.actnorm_init for an ImageGlow: one flag per ActNorm2d in module order (per
+    FlowStep its own, then the one behind each Conv2d of its coupling net), true = initialised already, leave it alone."""
+    return [bool(m.inited) for m in glow._actnorms()]
+
+
 def _np(t):
     return np.ascontiguousarray(t.detach().cpu().numpy().astype(np.float32))
 
@@ -442,10 +448,11 @@ class BoostedImageFlow(nn.Module):
             trainer.deterministic = bool(self.image_deterministic)
         return trainer, bind
 
-    def _native_trainer(self, c):
+    def _native_trainer(self, c, allow_uninit=False):
+        """``allow_uninit``: for ``initialize_actnorms(fused=True)`` only, which binds the un-initialised layers in order to write them."""
         flow = self.flows[c]
         params, buffers, perms, actnorms = self._component_tensors(c)
-        if not all(bool(m.inited) for m in actnorms):
+        if not allow_uninit and not all(bool(m.inited) for m in actnorms):
             raise ValueError("ActNorm not initialised: call initialize_actnorms(x) (or load a checkpoint) before training")
         key = tuple(t.data_ptr() for t in params) + tuple(t.data_ptr() for t in buffers) + \
             tuple((m.indices_serial, int(m.indices._version)) for m in perms)
@@ -500,17 +507,22 @@ class BoostedImageFlow(nn.Module):
         self._trainers[c] = (key, trainer, bind)
         return trainer, bind
 
+    @staticmethod
+    def _row_major_1x1(flow):
+        """Contiguous float32 storage for every 1x1 tensor and buffer of the component (``_step_trainer``'s docstring)."""
+        for layer in flow.flow.layers:
+            inv = getattr(layer, "invconv", None)
+            for p in ([] if inv is None else ([inv.lower, inv.upper, inv.log_s, inv.p, inv.sign_s] if inv.LU_decomposed else [inv.weight])):
+                if not p.is_contiguous() or p.dtype != torch.float32:
+                    p.data = p.data.float().contiguous()
+
     def _step_trainer(self, c):
         """``native_trainer(c)`` for the fused step, which updates the bound tensors themselves: (trainer, bindings) with the live LU
         factors and ``learn_top_fn`` bound on top (once per trainer object).  A 1x1 tensor or buffer that is not row-major in memory
         (the constructor's QR / LU factors are column-major) gets contiguous storage first.  Only ``.data`` is re-set: the Parameter
         object, and so any torch optimiser holding it, is unchanged, and the library binds the module's own storage, never a copy."""
         flow = self.flows[c]
-        for layer in flow.flow.layers:
-            inv = getattr(layer, "invconv", None)
-            for p in ([] if inv is None else ([inv.lower, inv.upper, inv.log_s, inv.p, inv.sign_s] if inv.LU_decomposed else [inv.weight])):
-                if not p.is_contiguous() or p.dtype != torch.float32:
-                    p.data = p.data.float().contiguous()
+        self._row_major_1x1(flow)
         trainer, bind = self.native_trainer(c)
         if not getattr(trainer, "step_bound", False):
             with torch.cuda.device(trainer.device):
@@ -780,18 +792,54 @@ class BoostedImageFlow(nn.Module):
         return zz, prior[0].expand(shape), prior[1].expand(shape), ldj, None      # broadcast views: same values, no copies
 
     @torch.no_grad()
-    def initialize_actnorms(self, x, components=None, noise=None):
+    def _initialize_actnorms_fused(self, c, x, noise):
+        """One library call for component c (gbnf_image_trainer_actnorm_init) on the component's trainer, which stays cached."""
+        glow = self.flows[c]
+        acts = glow._actnorms()
+        skip = actnorm_skip_flags(glow)
+        if all(skip):
+            return
+        scales = {float(m.scale) for m in acts}
+        if len(scales) != 1:
+            raise native.GbnfError(f"component {c}: the ActNorm2d layers have different scales {sorted(scales)}; the one-pass "
+                                   "initialisation takes one (use fused=False)")
+        self._row_major_1x1(glow)
+        with torch.cuda.device(x.device):
+            trainer, bind = self._native_trainer(c, allow_uninit=True)
+            if trainer._deterministic != bool(self.image_deterministic):
+                trainer.deterministic = bool(self.image_deterministic)
+            for _, obj, persistent in bind:                  # the composed 1x1 matrices, as _component_forward_train brings them up to date
+                if persistent is not None:
+                    persistent.copy_(obj.composed_weight_tensor())
+            if trainer.actnorm_count() != len(acts):
+                raise native.GbnfError(f"component {c} has {len(acts)} ActNorm2d layers, the library counted {trainer.actnorm_count()}")
+            trainer.actnorm_init(x, noise, scale=scales.pop(), skip=skip)
+        written = [m for m, s in zip(acts, skip) if not s]
+        for m in written:
+            m.inited = True
+        # the kernels wrote the parameters behind autograd's back (training_step does the same)
+        torch.autograd.graph.increment_version([t for m in written for t in (m.bias, m.logs)])
+
+    @torch.no_grad()
+    def initialize_actnorms(self, x, components=None, noise=None, fused=False):
         """The data-dependent initialisation of every ActNorm2d of a component (the step's own and the ones behind the coupling
         nets' Conv2d layers) from the batch ``x``: what the reference's FIRST forward in training mode does, layer by layer
         (models/layers.py:473-486: bias = -mean, logs = log(scale / (sqrt(mean((x + bias)^2)) + 1e-6)) over (N, H, W), each layer
         seeing the outputs of the layers initialised before it).  The statistics come from the library
         (gbnf_image_flow_actnorm_stats, exact-f32 kernels); layers already initialised are left alone.  ``components``: an index,
-        a list, or None = all.  ``noise``: the dequantisation noise (None: drawn once, as the reference's forward would)."""
+        a list, or None = all.  ``noise``: the dequantisation noise (None: drawn once, as the reference's forward would).
+
+        ``fused=True``: the whole component in ONE library call on its trainer's live tensors (gbnf_image_trainer_actnorm_init: one
+        walk of the forward, statistics in f64 in a fixed order, bias / logs written on the device, no host round trip per layer);
+        the trainer stays cached for the ``training_step`` that follows.  Every ActNorm2d of the component must have one ``scale``."""
         self._check(x)
         x = x.contiguous().float()
         noise = torch.rand_like(x) if noise is None else noise.contiguous().float()
         comps = range(self.num_components) if components is None else ([int(components)] if isinstance(components, int) else list(components))
         for c in comps:
+            if fused:
+                self._initialize_actnorms_fused(int(c), x, noise)
+                continue
             glow = self.flows[c]
             acts = glow._actnorms()
             for idx, m in enumerate(acts):

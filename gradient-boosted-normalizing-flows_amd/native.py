@@ -48,6 +48,7 @@ ABI_SYMBOLS = (
     "gbnf_image_trainer_create", "gbnf_image_trainer_destroy", "gbnf_image_trainer_trace_floats", "gbnf_image_trainer_workspace_bytes",
     "gbnf_image_trainer_forward", "gbnf_image_trainer_grad_floats", "gbnf_image_trainer_backward",
     "gbnf_image_trainer_set_deterministic", "gbnf_image_trainer_get_deterministic",
+    "gbnf_image_trainer_actnorm_count", "gbnf_image_trainer_actnorm_init_workspace_bytes", "gbnf_image_trainer_actnorm_init",
     "gbnf_image_trainer_bind_lu", "gbnf_image_trainer_bind_top", "gbnf_image_trainer_step_grad_floats",
     "gbnf_image_trainer_step_workspace_bytes", "gbnf_image_trainer_apply_update", "gbnf_image_trainer_nll_step",
     "gbnf_image_rho_step_workspace_bytes", "gbnf_image_mixture_rho_step",
@@ -236,6 +237,9 @@ def lib():
     L.gbnf_image_trainer_backward.argtypes = [vp, vp, i64, vp, vp, vp, vp, i64, vp]
     L.gbnf_image_trainer_set_deterministic.argtypes = [vp, i32]
     L.gbnf_image_trainer_get_deterministic.argtypes = [vp, C.POINTER(i32)]
+    L.gbnf_image_trainer_actnorm_count.argtypes = [vp, C.POINTER(i32)]
+    L.gbnf_image_trainer_actnorm_init_workspace_bytes.argtypes = [vp, i64, C.POINTER(i64)]
+    L.gbnf_image_trainer_actnorm_init.argtypes = [vp, vp, vp, i64, C.c_float, vp, vp, i64, vp]
     L.gbnf_image_trainer_bind_lu.argtypes = [vp, i32, i32, vp, vp, vp, vp, vp]
     L.gbnf_image_trainer_bind_top.argtypes = [vp, vp, vp, vp]
     L.gbnf_image_trainer_step_grad_floats.argtypes = [vp, C.POINTER(i64)]
@@ -800,6 +804,48 @@ class NativeImageTrainer:
         nb = C.c_int64()
         _check(lib().gbnf_image_trainer_step_workspace_bytes(self.handle, int(n), C.byref(nb)))
         return int(nb.value)
+
+    # ---- data-dependent ActNorm2d initialisation in one pass (gbnf_image_trainer_actnorm_init)
+    def actnorm_count(self):
+        """ActNorm2d layers of the component in module order: per FlowStep its own, then one behind each Conv2d of its coupling net."""
+        k = C.c_int32()
+        _check(lib().gbnf_image_trainer_actnorm_count(self.handle, C.byref(k)))
+        return int(k.value)
+
+    def actnorm_init_workspace_bytes(self, n):
+        nb = C.c_int64()
+        _check(lib().gbnf_image_trainer_actnorm_init_workspace_bytes(self.handle, int(n), C.byref(nb)))
+        return int(nb.value)
+
+    def actnorm_init(self, x, noise, scale=1.0, skip=None, workspace=None):
+        """The reference's first training-mode forward for every ActNorm2d at once: bias = -mean, logs = log(scale / (sqrt(var) + 1e-6))
+        of the tensor that reaches each layer, written INTO the bound tensors in forward order, on the current stream, with no host
+        read.  ``skip``: a sequence of ``actnorm_count()`` flags, true = leave that layer alone (it is initialised); None = all.
+        ``workspace``: a device tensor of at least ``actnorm_init_workspace_bytes(n)`` bytes (None: allocated here; its contents
+        on entry do not matter).  Returns nothing: run ``forward`` afterwards."""
+        import torch
+        _require_device_f32(x, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
+            raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        n = x.shape[0]
+        flags = None
+        if skip is not None:
+            flags = np.ascontiguousarray([1 if s else 0 for s in skip], dtype=np.uint8)
+            if flags.size != self.actnorm_count():
+                raise GbnfError(f"skip has {flags.size} entries, the component has {self.actnorm_count()} ActNorm2d layers")
+        nb = self.actnorm_init_workspace_bytes(max(n, 1))
+        if workspace is None:
+            workspace = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+        elif not workspace.is_cuda or not workspace.is_contiguous():
+            raise GbnfError("workspace must be a contiguous device tensor")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_image_trainer_actnorm_init(self.handle, ptr(x), ptr(noise), n, float(scale),
+                                                     C.c_void_p(flags.ctypes.data) if flags is not None else C.c_void_p(0), ptr(workspace),
+                                                     workspace.numel() * workspace.element_size(), _stream_ptr()))
 
     # ---- the one-call training step (gbnf_image_trainer_nll_step / _apply_update)
     def _layout_step(self):

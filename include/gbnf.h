@@ -771,6 +771,33 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* trainer, const float* trace,
 int gbnf_image_trainer_set_deterministic(gbnf_image_trainer* trainer, int32_t on);
 int gbnf_image_trainer_get_deterministic(const gbnf_image_trainer* trainer, int32_t* on);
 
+/* ---- data-dependent ActNorm2d initialisation of the whole component in ONE pass, on the live tensors ------------------------
+ * Replaces: what the reference's FIRST training-mode forward does to every ActNorm2d (models/layers.py:473-486 reached through
+ * models/glow.py:92-110), for all layers at once -- gbnf_image_flow_actnorm_stats (above) answers one layer per call on a packed
+ * copy and stays as it is.
+ * Layers are numbered in module order, as there: per FlowStep its own ActNorm2d, then the one behind each Conv2d of its
+ * coupling net (Conv2dZeros, Split2d and the top prior have none); gbnf_image_trainer_actnorm_count gives their number.
+ * skip_or_null: a HOST array of `count` bytes, non-zero = this layer is initialised already: its live values are used and
+ * not written; NULL = every layer is initialised here.
+ * The call walks the forward once on `stream` (x, noise, perm_weight as gbnf_image_trainer_forward reads them; with LU
+ * factors bound the matrices are composed first, as step 1 of gbnf_image_trainer_nll_step does).  At a layer to initialise
+ * it takes t = the tensor that reaches the layer with every earlier layer as it NOW stands -- a step's own ActNorm2d: the
+ * step's input state; a coupling-net layer: the raw output of its convolution, the layer itself treated as the identity
+ * whatever its tensors hold --, mean_c and var_c = mean((t - mean_c)^2) over (n, the map proper), and writes
+ *   bias_c = -mean_c,   logs_c = log(scale / (sqrt(var_c) + 1e-6))
+ * INTO THE LIVE TENSORS, re-derives that layer's weight tiles and goes on with the initialised layer.  The sums are taken in
+ * double precision in a fixed order (lane, wave, workgroup, chunk of images; per-chunk partials are stored and added in chunk
+ * order, no float atomics): the result is bit-identical from run to run, in and out of deterministic mode.  No z, ldj or
+ * trace comes back (run a forward afterwards); the trainer's tiles are left packed for the new values.  No host read, no
+ * synchronisation, no allocation.  workspace: caller-owned DEVICE scratch of gbnf_image_trainer_actnorm_init_workspace_bytes(n)
+ * bytes; nothing is assumed about what it holds on entry.
+ * GBNF_ERR_INVALID (nothing launched): a null trainer / x / count / bytes, n < 1, a scale that is not finite or not > 0, a
+ * workspace that is null or too small.  GBNF_ERR_UNSUPPORTED: more than 65535 images. */
+int gbnf_image_trainer_actnorm_count(const gbnf_image_trainer* trainer, int32_t* count);
+int gbnf_image_trainer_actnorm_init_workspace_bytes(const gbnf_image_trainer* trainer, int64_t n, int64_t* bytes);
+int gbnf_image_trainer_actnorm_init(gbnf_image_trainer* trainer, const float* x, const float* noise, int64_t n, float scale,
+                                    const uint8_t* skip_or_null, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* ---- one image training step in one call: loss, 1x1 log-determinants, clip, AdamW / SGD -----------------------------------
  * Replaces: one iteration of image_experiment.py:378-419 for the component being trained -- the loss (:227-229)
  *   nll_i = -(log_normal_diag(z, z_mu, z_var) + logdet),  loss = loss_scale * mean_i(nll_i)   (the reference: 1 / (ln 2 C H W)),
