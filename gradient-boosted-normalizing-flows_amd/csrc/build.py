@@ -215,7 +215,8 @@ def main(argv=None):
             jobs.append([HIPCC] + FLAGS + extra + ["-DGBNF_V_ARGS=" + ",".join(str(a) for a in vargs), "-c", vsrc, "-o", o])
     img_o, img_src = os.path.join(OBJ, "gbnf_image.o"), os.path.join(HERE, "gbnf_image.hip")
     objs.append(img_o)
-    if args.force or not newer(img_o, [img_src, os.path.join(HERE, "gbnf_image_hx3.hip.h"), os.path.join(HERE, "gbnf_image_net.h"), hdr[2], hdr[3]]):
+    if args.force or not newer(img_o, [img_src, os.path.join(HERE, "gbnf_image_hx3.hip.h"), os.path.join(HERE, "gbnf_image_net.h"),
+                                       os.path.join(HERE, "gbnf_image_ycond.h"), hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", img_src, "-o", img_o])
     # the fused image coupling-net kernel: its own unit, MFMA accumulators in VGPRs (the relu + split epilogues read them directly)
     net_o, net_src = os.path.join(OBJ, "gbnf_image_net.o"), os.path.join(HERE, "gbnf_image_net.hip")
@@ -232,8 +233,14 @@ def main(argv=None):
     # one image training step in one call (1x1 log-dets and LU chain, loss seed, top prior; the update is gbnf_opt.hip's): gbnf_image_opt.hip
     imgo_o, imgo_src = os.path.join(OBJ, "gbnf_image_opt.o"), os.path.join(HERE, "gbnf_image_opt.hip")
     objs.append(imgo_o)
-    if args.force or not newer(imgo_o, [imgo_src, imgt_hdr, opt_hdr, hdr[2], hdr[3]]):
+    yc_hdr = os.path.join(HERE, "gbnf_image_ycond.h")
+    if args.force or not newer(imgo_o, [imgo_src, imgt_hdr, opt_hdr, yc_hdr, hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", imgo_src, "-o", imgo_o])
+    # the class-conditional top of an image component (per-image prior, class head, cross-entropy and their gradients): gbnf_image_ycond.hip
+    yc_o, yc_src = os.path.join(OBJ, "gbnf_image_ycond.o"), os.path.join(HERE, "gbnf_image_ycond.hip")
+    objs.append(yc_o)
+    if args.force or not newer(yc_o, [yc_src, yc_hdr]):
+        jobs.append([HIPCC] + FLAGS + ["-c", yc_src, "-o", yc_o])
     comm_o, comm_src = os.path.join(OBJ, "gbnf_comm.o"), os.path.join(HERE, "gbnf_comm.hip")
     objs.append(comm_o)
     if args.force or not newer(comm_o, [comm_src, hdr[2], hdr[3]]):

@@ -33,6 +33,7 @@
 #include "../../include/gbnf.h"
 #include "gbnf_internal.h"
 #include "gbnf_image_net.h"
+#include "gbnf_image_ycond.h"
 
 namespace gbnf {
 
@@ -879,6 +880,10 @@ struct gbnf_image_flow {
   RepairOp* ops_dev = nullptr;               // the exact-f32 sequence of ONE image as recorded ops: forward [0, n_ops_fwd), then z -> x
   int n_ops_fwd = 0, n_ops_inv = 0;
   size_t repair_lds_fwd = 0, repair_lds_inv = 0;
+  // gbnf_image_flow_set_ycond: project_ycond [2Cz Y | 2Cz | 2Cz] then project_class [Y Cz | Y | Y] (absent without a class head)
+  int y_classes = 0;
+  bool y_head = false;
+  float* ycond_dev = nullptr;
   bool on_data_demoted() const {
     volatile unsigned* w = (volatile unsigned*)host_words;
     return w != nullptr && (w[3] != 0u || w[6] != 0u);
@@ -1397,6 +1402,7 @@ int gbnf_image_flow_destroy(gbnf_image_flow* f) {
   if (f->host_words) (void)hipHostFree(f->host_words);
   if (f->dev_state) (void)hipFree(f->dev_state);
   if (f->ops_dev) (void)hipFree(f->ops_dev);
+  if (f->ycond_dev) (void)hipFree(f->ycond_dev);
   delete f;
   return GBNF_OK;
 }
@@ -1412,6 +1418,7 @@ int gbnf_image_flow_info(const gbnf_image_flow* f, int32_t* z_channels, int32_t*
 
 int gbnf_image_flow_prior(const gbnf_image_flow* f, float* host) {
   if (!f || !host) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_prior: null argument");
+  if (f->y_classes > 0) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_prior: the handle is class-conditional: its prior needs y (gbnf_image_flow_prior_y)");
   const hipError_t e = hipMemcpy(host, f->blob_dev + f->prior_off, 2 * (size_t)f->zC * 4, hipMemcpyDeviceToHost);
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_image_flow_prior: %s", hipGetErrorString(e));
   return GBNF_OK;
@@ -1429,11 +1436,19 @@ static int64_t image_state_floats(const gbnf_image_flow* f, int64_t n) {
 static int64_t image_repair_workgroups(int64_t n) { return n < IMG_REPAIR_WGS ? n : IMG_REPAIR_WGS; }
 static int64_t image_mark_floats(int64_t n) { return (n + 63) / 64 * 64; }
 
-int gbnf_image_flow_workspace_bytes(const gbnf_image_flow* f, int64_t n, int64_t* bytes) {
-  if (!f || !bytes || n < 0) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_workspace_bytes: bad argument");
+// floats of a plain forward call's workspace; a class-conditional handle's calls keep a compact z and a scratch ll behind them
+static int64_t image_plain_floats(const gbnf_image_flow* f, int64_t n) {
   int64_t floats = image_state_floats(f, n);
   if (f->math_mode == GBNF_MATH_F16X3) floats += 2 * image_mark_floats(n) + 64 + image_repair_workgroups(n) * image_state_floats(f, 1);
-  *bytes = floats * 4 + 256;
+  return floats;
+}
+static int64_t image_plain_bytes(const gbnf_image_flow* f, int64_t n) { return image_plain_floats(f, n) * 4 + 256; }
+static int64_t image_ycond_z_floats(const gbnf_image_flow* f, int64_t n) { return (n * f->zC * f->zH * f->zW + 63) / 64 * 64; }
+
+int gbnf_image_flow_workspace_bytes(const gbnf_image_flow* f, int64_t n, int64_t* bytes) {
+  if (!f || !bytes || n < 0) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_workspace_bytes: bad argument");
+  *bytes = image_plain_bytes(f, n);
+  if (f->y_classes > 0) *bytes += (image_ycond_z_floats(f, n) + image_mark_floats(n)) * 4 + 256;       // [z | ll] behind the plain call's
   return GBNF_OK;
 }
 
@@ -1681,15 +1696,116 @@ static void launch_repair(const gbnf_image_flow* f, bool inverse, RepairArgs a, 
   else hipLaunchKernelGGL((img_repair_kernel<false>), grid, blk, f->repair_lds_fwd, s, a);
 }
 
+// the launches of gbnf_image_flow_forward, every argument checked by the caller
+static int image_forward_launch(const char* fn, const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj,
+                                float* ll, void* workspace, void* stream);
+
 int gbnf_image_flow_forward(const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj,
                             float* ll, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!f) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: flow is null");
+  if (f->y_classes > 0) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: the handle is class-conditional: it needs y (gbnf_image_flow_forward_y)");
   if (n < 0) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: n < 0");
   if (n == 0) return GBNF_OK;
   if (!x || !ldj || !workspace) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: x / ldj / workspace is null");
   int64_t need = 0;
   gbnf_image_flow_workspace_bytes(f, n, &need);
   if (workspace_bytes < need) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: workspace of %lld bytes < %lld", (long long)workspace_bytes, (long long)need);
+  return image_forward_launch("gbnf_image_flow_forward", f, x, noise, n, z, ldj, ll, workspace, stream);
+}
+
+// The handle's conditioning as the kernels of gbnf_image_ycond.hip take it
+static YCond image_ycond(const gbnf_image_flow* f) {
+  YCond c{};
+  const int64_t P = 2 * (int64_t)f->zC, Y = f->y_classes;
+  const float* q = f->ycond_dev;
+  c.top_h = f->blob_dev + f->prior_off;
+  c.cond_w = q; c.cond_b = q + P * Y; c.cond_logs = c.cond_b + P;
+  if (f->y_head) { c.class_w = c.cond_logs + P; c.class_b = c.class_w + Y * f->zC; c.class_logs = c.class_b + Y; }
+  c.Y = (int)Y; c.Cz = f->zC; c.HW = f->zH * f->zW;
+  return c;
+}
+
+int gbnf_image_flow_set_ycond(gbnf_image_flow* f, int32_t y_classes, const float* cond_w, const float* cond_b, const float* cond_logs,
+                              const float* class_w, const float* class_b, const float* class_logs) {
+  const char* fn = "gbnf_image_flow_set_ycond";
+  if (!f) return fail(GBNF_ERR_INVALID, "%s: flow is null", fn);
+  if (y_classes < 1) return fail(GBNF_ERR_INVALID, "%s: y_classes = %d (must be >= 1)", fn, (int)y_classes);
+  if (y_classes > YC_MAX_CLASSES) return fail(GBNF_ERR_UNSUPPORTED, "%s: y_classes = %d > %d", fn, (int)y_classes, YC_MAX_CLASSES);
+  if (f->zC > YC_MAX_CZ) return fail(GBNF_ERR_UNSUPPORTED, "%s: %d top channels > %d", fn, f->zC, YC_MAX_CZ);
+  if (!cond_w || !cond_b || !cond_logs) return fail(GBNF_ERR_INVALID, "%s: a project_ycond array is null", fn);
+  const bool head = class_w != nullptr;
+  if (head && (!class_b || !class_logs)) return fail(GBNF_ERR_INVALID, "%s: project_class needs weight, bias and logs", fn);
+  const size_t P = 2 * (size_t)f->zC, Y = (size_t)y_classes;
+  std::vector<float> host;
+  host.insert(host.end(), cond_w, cond_w + P * Y);
+  host.insert(host.end(), cond_b, cond_b + P);
+  host.insert(host.end(), cond_logs, cond_logs + P);
+  if (head) {
+    host.insert(host.end(), class_w, class_w + Y * f->zC);
+    host.insert(host.end(), class_b, class_b + Y);
+    host.insert(host.end(), class_logs, class_logs + Y);
+  }
+  float* dev = nullptr;
+  hipError_t e = hipMalloc((void**)&dev, host.size() * 4);
+  if (e == hipSuccess) e = hipMemcpy(dev, host.data(), host.size() * 4, hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    if (dev) (void)hipFree(dev);
+    return fail(GBNF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+  }
+  if (f->ycond_dev) (void)hipFree(f->ycond_dev);
+  f->ycond_dev = dev; f->y_classes = y_classes; f->y_head = head;
+  return GBNF_OK;
+}
+
+int gbnf_image_flow_y_classes(const gbnf_image_flow* f, int32_t* y_classes) {
+  if (!f || !y_classes) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_y_classes: bad argument");
+  *y_classes = f->y_classes;
+  return GBNF_OK;
+}
+
+int gbnf_image_flow_forward_y(const gbnf_image_flow* f, const float* x, const float* noise, const float* y, int64_t n, float* z, float* ldj,
+                              float* ll, float* y_logits, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* fn = "gbnf_image_flow_forward_y";
+  if (!f) return fail(GBNF_ERR_INVALID, "%s: flow is null", fn);
+  if (f->y_classes == 0) return fail(GBNF_ERR_INVALID, "%s: no conditioning set (gbnf_image_flow_set_ycond)", fn);
+  if (n < 0) return fail(GBNF_ERR_INVALID, "%s: n < 0", fn);
+  if (n == 0) return GBNF_OK;
+  if (!x || !y || !ldj || !workspace) return fail(GBNF_ERR_INVALID, "%s: x / y / ldj / workspace is null", fn);
+  if (y_logits && !f->y_head) return fail(GBNF_ERR_INVALID, "%s: y_logits asked of a handle without a class head", fn);
+  int64_t need = 0;
+  gbnf_image_flow_workspace_bytes(f, n, &need);
+  if (workspace_bytes < need) return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld", fn, (long long)workspace_bytes, (long long)need);
+  // The plain forward with the handle's y-free prior (the range marks, the same-call repair and the on-data check act on its ll as on
+  // any call's), kept in scratch; then ONE launch, behind the repair in stream order, gives ll under the image's own prior and the logits.
+  float* zs = reinterpret_cast<float*>((char*)workspace + image_plain_bytes(f, n));
+  float* ll0 = zs + image_ycond_z_floats(f, n);
+  float* zc = z ? z : zs;
+  if (const int rc = image_forward_launch(fn, f, x, noise, n, zc, ldj, ll0, workspace, stream)) return rc;
+  if (ll != nullptr || y_logits != nullptr) {
+    ycond_launch_eval(image_ycond(f), zc, ldj, y, n, ll ? ll : ll0, y_logits, (hipStream_t)stream);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+  }
+  return GBNF_OK;
+}
+
+int gbnf_image_flow_prior_y(const gbnf_image_flow* f, const float* y, int64_t n, const float* e, float temperature, float* mean_logvar,
+                            float* z_out, void* stream) {
+  const char* fn = "gbnf_image_flow_prior_y";
+  if (!f) return fail(GBNF_ERR_INVALID, "%s: flow is null", fn);
+  if (f->y_classes == 0) return fail(GBNF_ERR_INVALID, "%s: no conditioning set (gbnf_image_flow_set_ycond)", fn);
+  if (n < 0) return fail(GBNF_ERR_INVALID, "%s: n < 0", fn);
+  if (!y) return fail(GBNF_ERR_INVALID, "%s: y is null", fn);
+  if (z_out && !e) return fail(GBNF_ERR_INVALID, "%s: z_out needs e", fn);
+  if (n == 0 || (!mean_logvar && !z_out)) return GBNF_OK;
+  ycond_launch_prior(image_ycond(f), y, n, e, temperature, mean_logvar, z_out, (hipStream_t)stream);
+  const hipError_t err = hipGetLastError();
+  if (err != hipSuccess) return fail(GBNF_ERR_HIP, "%s: %s", fn, hipGetErrorString(err));
+  return GBNF_OK;
+}
+
+static int image_forward_launch(const char* fn, const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj,
+                                float* ll, void* workspace, void* stream) {
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   // exact f32: the handle's mode, or a split-f16 handle whose on-data check has failed (pinned word, no synchronisation)
@@ -1697,7 +1813,7 @@ int gbnf_image_flow_forward(const gbnf_image_flow* f, const float* x, const floa
   if (image_repair_mode() == 0) return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, nullptr);
   // ---- split-f16 pass with range marks; the on-data check (first launch, every check_every-th); the marked images on exact f32
   const RepairSpace r = repair_space(f, ws, n);
-  if (hipMemsetAsync(r.mark, 0, (size_t)n * 4, s) != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_image_flow_forward: memset failed");
+  if (hipMemsetAsync(r.mark, 0, (size_t)n * 4, s) != hipSuccess) return fail(GBNF_ERR_HIP, "%s: memset failed", fn);
   const int rc = image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, r.mark);
   if (rc) return rc;
   int32_t every = 256, tol_e9 = 2500;
@@ -1715,7 +1831,7 @@ int gbnf_image_flow_forward(const gbnf_image_flow* f, const float* x, const floa
   a.check = 0; a.list = r.list; a.count = r.count;
   launch_repair(f, false, a, n, s);
   const hipError_t e = hipGetLastError();
-  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_image_flow_forward (repair): %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s (repair): %s", fn, hipGetErrorString(e));
   return GBNF_OK;
 }
 

@@ -73,8 +73,9 @@ __global__ void __launch_bounds__(G_THREADS) g_finalize_kernel(const double* __r
 }
 
 // behind the trained component's step: the reference's nll = g_nll - G_nll (unscaled, in nats)
-__global__ void boosted_stat_kernel(float* __restrict__ stats) {
-  if (threadIdx.x == 0 && blockIdx.x == 0) stats[5] = stats[0] - stats[4];
+// (g: where the G term's three floats start: 4, or 8 in the class-conditional call's 12-float layout)
+__global__ void boosted_stat_kernel(float* __restrict__ stats, int g) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) stats[g + 1] = stats[0] - stats[g];
 }
 
 // the caller's workspace of one boosted image step, in 256-byte aligned pieces
@@ -160,6 +161,13 @@ int gbnf_image_mixture_rho_step(const gbnf_image_flow* const* flows, int32_t com
   if (n < 1) return fail(GBNF_ERR_INVALID, "%s: n = %lld (must be >= 1)", fn, (long long)n);
   const int n_flows = (int)component + 1;
   if (const int rc = check_image_flows(fn, flows, n_flows)) return rc;
+  for (int c = 0; c < n_flows; ++c) {    // refused HERE, before the first component's launches
+    int32_t y_classes = 0;
+    if (const int rc = gbnf_image_flow_y_classes(flows[c], &y_classes)) return rc;
+    if (y_classes != 0)
+      return fail(GBNF_ERR_INVALID, "%s: flows[%d] is class-conditional (%d classes) and needs y: the rho update has no such call", fn, c,
+                  (int)y_classes);
+  }
   int64_t flow_bytes = 0, total = 0;
   if (const int rc = image_rho_layout(flows, n_flows, n, &flow_bytes, &total)) return rc;
   if (workspace_bytes < total)
@@ -182,16 +190,25 @@ int gbnf_image_boosted_step_workspace_bytes(const gbnf_image_flow* fixed, const 
   return GBNF_OK;
 }
 
-int gbnf_image_boosted_nll_step(const gbnf_image_flow* fixed, float g_floor, gbnf_image_trainer* trainer, const float* x, const float* noise,
-                                int64_t n, float loss_scale, float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper,
-                                float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream) {
-  const char* fn = "gbnf_image_boosted_nll_step";
+// the plain call (y null) and the class-conditional one (y (n, Y): the fixed component through gbnf_image_flow_forward_y, the step
+// through gbnf_image_trainer_nll_step_y, the G term's floats at stats[8..10])
+static int image_boosted_step(const char* fn, const gbnf_image_flow* fixed, float g_floor, gbnf_image_trainer* trainer, const float* x,
+                              const float* noise, const float* y, bool want_y, int64_t n, float loss_scale, float y_weight, float* grads,
+                              float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper, float* stats_dev, void* workspace,
+                              int64_t workspace_bytes, void* stream) {
   // everything gbnf_image_trainer_nll_step refuses is refused HERE, before the fixed component's launches
   if (!trainer || !x || !grads || !stats_dev || !workspace)
     return fail(GBNF_ERR_INVALID, "%s: trainer / x / grads / stats_dev / workspace is null", fn);
+  if (want_y && !y) return fail(GBNF_ERR_INVALID, "%s: y is null", fn);
   if (n < 1 || n > 65535) return fail(GBNF_ERR_INVALID, "%s: n = %lld (1 to 65535 images per call)", fn, (long long)n);
   int64_t step_floats = 0;
   if (const int rc = gbnf_image_trainer_step_grad_floats(trainer, &step_floats)) return rc;      // (a failed bind call)
+  int32_t y_trainer = 0, y_fixed = 0;
+  if (const int rc = gbnf_image_trainer_y_classes(trainer, &y_trainer)) return rc;
+  if (const int rc = fixed ? gbnf_image_flow_y_classes(fixed, &y_fixed) : GBNF_OK) return rc;
+  if (want_y ? (y_trainer < 1 || y_fixed != y_trainer) : (y_trainer != 0 || y_fixed != 0))
+    return fail(GBNF_ERR_INVALID, "%s: the trainer has %d classes bound, the fixed component %d: %s", fn, (int)y_trainer, (int)y_fixed,
+                want_y ? "both must be conditioned on the same classes" : "class-conditional components need y (the _y call)");
   if (const int rc = check_hyper(fn, hyper, exp_avg, exp_avg_sq)) return rc;
   if (const int rc = check_fixed_image(fn, fixed, trainer)) return rc;
   ImageBoostLayout L;
@@ -205,22 +222,56 @@ int gbnf_image_boosted_nll_step(const gbnf_image_flow* fixed, float g_floor, gbn
   float* ll = (float*)(ws + L.ll);
   double* part_sum = (double*)(ws + L.part);
   double* part_bad = part_sum + G_MAX_PARTIALS;
-  int rc = gbnf_image_flow_forward(fixed, x, noise, n, nullptr, ldj, ll, ws + L.flow, L.flow_bytes, stream);
+  int rc = want_y ? gbnf_image_flow_forward_y(fixed, x, noise, y, n, nullptr, ldj, ll, nullptr, ws + L.flow, L.flow_bytes, stream)
+                  : gbnf_image_flow_forward(fixed, x, noise, n, nullptr, ldj, ll, ws + L.flow, L.flow_bytes, stream);
   if (rc) return rc;
+  const int g_at = want_y ? 8 : 4;
   int64_t nb = (n + 4 * G_THREADS - 1) / (4 * G_THREADS);
   if (nb > G_MAX_PARTIALS) nb = G_MAX_PARTIALS;
   hipLaunchKernelGGL(g_partial_kernel, dim3((unsigned)nb), dim3(G_THREADS), 0, s, (const float*)ll, n, g_floor, part_sum, part_bad);
   hipLaunchKernelGGL(g_finalize_kernel, dim3(1), dim3(G_THREADS), 0, s, (const double*)part_sum, (const double*)part_bad, (int)nb, n,
-                     stats_dev);
+                     stats_dev + (g_at - 4));
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s launch: %s", fn, hipGetErrorString(e));
-  rc = gbnf_image_trainer_nll_step(trainer, x, noise, n, loss_scale, grads, exp_avg, exp_avg_sq, hyper, stats_dev, ws + L.step, L.step_bytes,
-                                   stream);
+  rc = want_y ? gbnf_image_trainer_nll_step_y(trainer, x, noise, y, n, loss_scale, y_weight, grads, exp_avg, exp_avg_sq, hyper, stats_dev,
+                                              ws + L.step, L.step_bytes, stream)
+              : gbnf_image_trainer_nll_step(trainer, x, noise, n, loss_scale, grads, exp_avg, exp_avg_sq, hyper, stats_dev, ws + L.step,
+                                            L.step_bytes, stream);
   if (rc) return rc;
-  hipLaunchKernelGGL(boosted_stat_kernel, dim3(1), dim3(64), 0, s, stats_dev);
+  hipLaunchKernelGGL(boosted_stat_kernel, dim3(1), dim3(64), 0, s, stats_dev, g_at);
   e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s launch: %s", fn, hipGetErrorString(e));
   return GBNF_OK;
+}
+
+int gbnf_image_boosted_nll_step(const gbnf_image_flow* fixed, float g_floor, gbnf_image_trainer* trainer, const float* x, const float* noise,
+                                int64_t n, float loss_scale, float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper,
+                                float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream) {
+  return image_boosted_step("gbnf_image_boosted_nll_step", fixed, g_floor, trainer, x, noise, nullptr, false, n, loss_scale, 0.0f, grads,
+                            exp_avg, exp_avg_sq, hyper, stats_dev, workspace, workspace_bytes, stream);
+}
+
+int gbnf_image_boosted_step_workspace_bytes_y(const gbnf_image_flow* fixed, const gbnf_image_trainer* trainer, int64_t n, int64_t* bytes) {
+  const char* fn = "gbnf_image_boosted_step_workspace_bytes_y";
+  if (!bytes || n < 1) return fail(GBNF_ERR_INVALID, "%s: bad argument", fn);
+  if (const int rc = check_fixed_image(fn, fixed, trainer)) return rc;
+  int32_t y_trainer = 0, y_fixed = 0;
+  if (const int rc = gbnf_image_trainer_y_classes(trainer, &y_trainer)) return rc;
+  if (const int rc = gbnf_image_flow_y_classes(fixed, &y_fixed)) return rc;
+  if (y_trainer < 1 || y_fixed != y_trainer)
+    return fail(GBNF_ERR_INVALID, "%s: the trainer has %d classes bound, the fixed component %d", fn, (int)y_trainer, (int)y_fixed);
+  ImageBoostLayout L;
+  if (const int rc = image_boost_layout(fixed, trainer, n, &L)) return rc;
+  *bytes = L.total;
+  return GBNF_OK;
+}
+
+int gbnf_image_boosted_nll_step_y(const gbnf_image_flow* fixed, float g_floor, gbnf_image_trainer* trainer, const float* x, const float* noise,
+                                  const float* y, int64_t n, float loss_scale, float y_weight, float* grads, float* exp_avg,
+                                  float* exp_avg_sq, const gbnf_opt_hyper* hyper, float* stats_dev, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+  return image_boosted_step("gbnf_image_boosted_nll_step_y", fixed, g_floor, trainer, x, noise, y, true, n, loss_scale, y_weight, grads,
+                            exp_avg, exp_avg_sq, hyper, stats_dev, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

@@ -26,6 +26,7 @@
 #include "gbnf_internal.h"
 #include "gbnf_opt.h"
 #include "gbnf_image_train.h"
+#include "gbnf_image_ycond.h"
 
 namespace gbnf {
 
@@ -308,6 +309,10 @@ struct ImageStepState {
   float* top_bias = nullptr;
   float* top_logs = nullptr;
   int64_t g_top_w = -1, g_top_bias = -1, g_top_logs = -1;
+  // gbnf_image_trainer_bind_ycond: project_ycond / project_class (live tensors) and their regions behind the top prior's
+  int y_classes = 0;
+  float* yc[6] = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};      // cond weight, bias, logs, class weight, bias, logs
+  int64_t g_yc[6] = {-1, -1, -1, -1, -1, -1};
   int64_t step_grad_floats = 0;
   int n_mix = 0, n_regions = 0;
   bool ready = false;                          // the device tables below match the bindings (false after a failed rebuild: every step call refuses)
@@ -350,6 +355,11 @@ int rebuild(gbnf_image_trainer* t) {
     if (s->top_weight != nullptr) { s->g_top_w = off; off += top_c * top_c * 9; }
     s->g_top_bias = off; off += top_c;
     s->g_top_logs = off; off += top_c;
+  }
+  const int64_t yc_len[6] = {top_c * s->y_classes, top_c, top_c, (int64_t)s->y_classes * t->zC, s->y_classes, s->y_classes};
+  for (int k = 0; k < 6; ++k) {
+    s->g_yc[k] = -1;
+    if (s->y_classes > 0) { s->g_yc[k] = off; off += yc_len[k]; }
   }
   s->step_grad_floats = off;
 
@@ -398,6 +408,7 @@ int rebuild(gbnf_image_trainer* t) {
   region(s->top_weight, s->g_top_w, top_c * top_c * 9);
   region(s->top_bias, s->g_top_bias, top_c);
   region(s->top_logs, s->g_top_logs, top_c);
+  for (int k = 0; k < 6; ++k) region(s->yc[k], s->g_yc[k], yc_len[k]);
   s->n_mix = (int)mix.size();
   s->n_regions = (int)regions.size();
 
@@ -427,7 +438,7 @@ double* update_partials(const ImageStepState* s) { return s->sums_dev + align256
 
 // the caller's workspace of one whole step, in 256-byte aligned pieces
 struct ImageStepLayout {
-  int64_t z, ldj, trace, g_z, g_ldj, ws, ws_bytes, partials, total;
+  int64_t z, ldj, trace, g_z, g_ldj, ws, ws_bytes, partials, yterms, total;
 };
 int image_step_layout(const gbnf_image_trainer* t, int64_t n, ImageStepLayout* L) {
   int64_t trace_floats = 0, ws_bytes = 0;
@@ -443,6 +454,8 @@ int image_step_layout(const gbnf_image_trainer* t, int64_t n, ImageStepLayout* L
   L->g_ldj = off; off += nn;
   L->ws = off; L->ws_bytes = ws_bytes; off += align256(ws_bytes);
   L->partials = off; off += align256(4 * OPT_MAX_PARTIALS * (int64_t)sizeof(double));    // loss | prior mean | prior log-var | norm
+  L->yterms = off;                                            // the per-image terms of a conditioned trainer's step (gbnf_image_ycond.hip)
+  if (t->step->y_classes > 0) off += align256(ycond_terms_bytes(n, t->step->y_classes, t->zC));
   L->total = off;
   return GBNF_OK;
 }
@@ -533,13 +546,39 @@ int gbnf_image_trainer_apply_update(gbnf_image_trainer* t, const float* grads, f
                            stream);
 }
 
-int gbnf_image_trainer_nll_step(gbnf_image_trainer* t, const float* x, const float* noise, int64_t n, float loss_scale, float* grads,
-                                float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* h, float* stats_dev, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-  const char* fn = "gbnf_image_trainer_nll_step";
+int gbnf_image_trainer_bind_ycond(gbnf_image_trainer* t, int32_t y_classes, float* cond_w, float* cond_b, float* cond_logs, float* class_w,
+                                  float* class_b, float* class_logs) {
+  const char* fn = "gbnf_image_trainer_bind_ycond";
+  if (!t || !t->step) return fail(GBNF_ERR_INVALID, "%s: trainer is null", fn);
+  if (y_classes < 1) return fail(GBNF_ERR_INVALID, "%s: y_classes = %d (must be >= 1)", fn, (int)y_classes);
+  if (y_classes > YC_MAX_CLASSES) return fail(GBNF_ERR_UNSUPPORTED, "%s: y_classes = %d > %d", fn, (int)y_classes, YC_MAX_CLASSES);
+  if (t->zC > YC_MAX_CZ) return fail(GBNF_ERR_UNSUPPORTED, "%s: %d top channels > %d", fn, t->zC, YC_MAX_CZ);
+  if (!cond_w || !cond_b || !cond_logs || !class_w || !class_b || !class_logs)
+    return fail(GBNF_ERR_INVALID, "%s: a project_ycond / project_class tensor is null", fn);
+  ImageStepState* s = t->step;
+  s->y_classes = y_classes;
+  s->yc[0] = cond_w; s->yc[1] = cond_b; s->yc[2] = cond_logs; s->yc[3] = class_w; s->yc[4] = class_b; s->yc[5] = class_logs;
+  return rebuild(t);
+}
+
+int gbnf_image_trainer_y_classes(const gbnf_image_trainer* t, int32_t* y_classes) {
+  if (!t || !t->step || !y_classes) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_y_classes: bad argument");
+  *y_classes = t->step->y_classes;
+  return GBNF_OK;
+}
+
+// gbnf_image_trainer_nll_step (y null: refused on a conditioned trainer) and gbnf_image_trainer_nll_step_y (y non-null)
+static int image_nll_step(const char* fn, bool want_y, gbnf_image_trainer* t, const float* x, const float* noise, const float* y, int64_t n,
+                          float loss_scale, float y_weight, float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* h,
+                          float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!t || !t->step || !x || !grads || !stats_dev || !workspace)
     return fail(GBNF_ERR_INVALID, "%s: trainer / x / grads / stats_dev / workspace is null", fn);
   if (!t->step->ready) return fail(GBNF_ERR_INVALID, "%s: the last bind call failed: bind again first", fn);
+  if (!want_y && t->step->y_classes > 0)
+    return fail(GBNF_ERR_INVALID, "%s: the trainer is class-conditional: it needs y (gbnf_image_trainer_nll_step_y)", fn);
+  if (want_y && t->step->y_classes == 0)
+    return fail(GBNF_ERR_INVALID, "%s: no conditioning bound (gbnf_image_trainer_bind_ycond)", fn);
+  if (want_y && !y) return fail(GBNF_ERR_INVALID, "%s: y is null", fn);
   // (with these checks gbnf_image_trainer_forward / _backward below have nothing left to refuse: their own refusals are a null x /
   // ldj / trace, n outside [1, 65535] and a workspace below gbnf_image_trainer_workspace_bytes, which the step layout contains)
   if (n < 1 || n > 65535) return fail(GBNF_ERR_INVALID, "%s: n = %lld (1 to 65535 images per call)", fn, (long long)n);
@@ -577,20 +616,52 @@ int gbnf_image_trainer_nll_step(gbnf_image_trainer* t, const float* x, const flo
   sq.bpc = (int)std::max<int64_t>(1, std::min<int64_t>(OPT_MAX_PARTIALS / sq.Cz, per_channel));
   sq.kn = (float)((double)loss_scale / (double)n);
   sq.g_z = g_z; sq.g_ldj = g_ldj; sq.nll_part = nll_part; sq.mu_part = mu_part; sq.lv_part = lv_part;
-  hipLaunchKernelGGL(img_nll_seed_kernel, dim3((unsigned)sq.bpc, (unsigned)sq.Cz), dim3(IOPT_THREADS), 0, s, sq);
+  YCond yc{};
+  YCondTerms yt{};
+  if (want_y) {
+    // the per-image prior, the class head and the cross-entropy: one workgroup per image leaves the seed and the image's terms
+    yc.top_bias = st->top_bias; yc.top_logs = st->top_logs;
+    yc.cond_w = st->yc[0]; yc.cond_b = st->yc[1]; yc.cond_logs = st->yc[2]; yc.class_w = st->yc[3]; yc.class_b = st->yc[4]; yc.class_logs = st->yc[5];
+    yc.Y = st->y_classes; yc.Cz = t->zC; yc.HW = sq.HW;
+    yt = ycond_terms(ws + L.yterms, n, yc.Y, yc.Cz);
+    ycond_launch_seed(yc, z, ldj, ld_sums(st), st->n_mix, y, n, sq.kn, (float)((double)y_weight / (double)n), g_z, g_ldj, yt, s);
+  } else {
+    hipLaunchKernelGGL(img_nll_seed_kernel, dim3((unsigned)sq.bpc, (unsigned)sq.Cz), dim3(IOPT_THREADS), 0, s, sq);
+  }
   hipError_t e = hipMemsetAsync(grads, 0, (size_t)st->step_grad_floats * 4, s);
   if (e == hipSuccess) e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s launch: %s", fn, hipGetErrorString(e));
   rc = gbnf_image_trainer_backward(t, trace, n, g_z, g_ldj, grads, ws + L.ws, L.ws_bytes, stream);
   if (rc) return rc;
-  const bool top = st->top_bias != nullptr;
+  const bool top = st->top_bias != nullptr && !want_y;        // (conditioned: the top prior's gradient has per-image terms, below)
   if (st->n_mix > 0 || top) {
-    mq.top = TopPrior{st->top_bias, st->top_logs, st->g_top_bias, st->g_top_logs, t->zC};
+    mq.top = TopPrior{top ? st->top_bias : nullptr, st->top_logs, st->g_top_bias, st->g_top_logs, t->zC};
     mq.mu_part = mu_part; mq.lv_part = lv_part; mq.bpc = sq.bpc;
     hipLaunchKernelGGL((img_mix_logdet_kernel<1>), dim3((unsigned)(st->n_mix + (top ? 1 : 0))), dim3(IOPT_THREADS), MIX_LDS_BYTES, s, mq);
   }
+  if (want_y) {
+    const YCondRegions yr{st->top_bias ? st->g_top_bias : -1, st->g_top_logs, st->g_yc[0], st->g_yc[1], st->g_yc[2], st->g_yc[3], st->g_yc[4],
+                          st->g_yc[5]};
+    ycond_launch_reduce(yc, y, n, yt, yr, grads, nll_part, stats_dev, s);
+    return opt_launch_update(fn, update_view(t), grads, exp_avg, exp_avg_sq, h, stats_dev, grad_part, nll_part, 1, 1.0 / (double)n, 0.0,
+                             stream);
+  }
   return opt_launch_update(fn, update_view(t), grads, exp_avg, exp_avg_sq, h, stats_dev, grad_part, nll_part, sq.bpc * sq.Cz,
                            1.0 / (double)n, 0.0, stream);
+}
+
+int gbnf_image_trainer_nll_step(gbnf_image_trainer* t, const float* x, const float* noise, int64_t n, float loss_scale, float* grads,
+                                float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* h, float* stats_dev, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  return image_nll_step("gbnf_image_trainer_nll_step", false, t, x, noise, nullptr, n, loss_scale, 0.0f, grads, exp_avg, exp_avg_sq, h,
+                        stats_dev, workspace, workspace_bytes, stream);
+}
+
+int gbnf_image_trainer_nll_step_y(gbnf_image_trainer* t, const float* x, const float* noise, const float* y, int64_t n, float loss_scale,
+                                  float y_weight, float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* h, float* stats_dev,
+                                  void* workspace, int64_t workspace_bytes, void* stream) {
+  return image_nll_step("gbnf_image_trainer_nll_step_y", true, t, x, noise, y, n, loss_scale, y_weight, grads, exp_avg, exp_avg_sq, h,
+                        stats_dev, workspace, workspace_bytes, stream);
 }
 
 }  // extern "C"

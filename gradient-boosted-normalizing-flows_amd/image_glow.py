@@ -8,7 +8,9 @@ reference checkpoint loads with ``load_state_dict``; every call that computes go
 Reference anchors: Glow (models/glow.py:12-110), FlowNet image branch (:192-252), FlowStep (:264-342), ActNorm2d /
 Conv2d / Conv2dZeros / Permute2d / Split2d / SqueezeLayer / InvertibleConv1x1 (models/layers.py:548-796), BoostedFlow
 (models/boosted_flow.py), the image likelihood ll = log_normal_diag(z, z_mu, z_var) + logdet (image_experiment.py:227).
-Not on the path: y_condition, learned dequantisation flows.  In train mode with gradients enabled a component's forward runs on the
+Class conditioning (``args.y_condition``: a per-image prior from ``project_ycond`` and the class head ``project_class``,
+models/glow.py:36-39, 79-82, 105-106) runs in the library too (gbnf_image_ycond.hip); the boosted wrapper passes ``y_onehot`` on to the
+component, which the reference's ``BoostedFlow.encode`` forgets.  Not on the path: learned dequantisation flows.  In train mode with gradients enabled a component's forward runs on the
 live parameters and is differentiable (``native.NativeImageTrainer``: HIP forward and backward, exact f32; ``torch.optim`` on the
 resulting ``.grad`` is the supported step).  An un-initialised model (fresh from the constructor)
 is initialised from data with ``BoostedImageFlow.initialize_actnorms(x)`` -- what the reference's first training-mode forward
@@ -59,6 +61,21 @@ class Conv2dZeros(nn.Module):
         self.logscale_factor = logscale_factor
         self.logs = nn.Parameter(torch.zeros(out_dim, 1, 1))
     forward = _no_eager
+
+
+class LinearZeros(nn.Module):
+    """models/layers.py:560-574: (x W^T + b) exp(3 logs), zero at construction."""
+
+    def __init__(self, in_dim, out_dim, logscale_factor=3):
+        super().__init__()
+        self.linear = nn.Linear(in_dim, out_dim)
+        self.linear.weight.data.zero_()
+        self.linear.bias.data.zero_()
+        self.logscale_factor = logscale_factor
+        self.logs = nn.Parameter(torch.zeros(out_dim))
+
+    def forward(self, sample):          # (tiny, and only on the autograd path of a class-conditional component)
+        return self.linear(sample) * torch.exp(self.logs * self.logscale_factor)
 
 
 class ConvNet(nn.Module):
@@ -203,11 +220,11 @@ class ImageGlow(nn.Module):
 
     def __init__(self, args):
         super().__init__()
-        if getattr(args, "y_condition", False):
-            raise NotImplementedError("y_condition is not on the supported path")
         if getattr(args, "num_dequant_blocks", 0) > 0:
             raise NotImplementedError("learned dequantisation flows are not on the supported path")
-        self.learn_top, self.y_condition, self.y_classes = bool(args.learn_top), False, args.y_classes
+        self.learn_top, self.y_condition, self.y_classes = bool(args.learn_top), bool(getattr(args, "y_condition", False)), args.y_classes
+        if self.y_condition and not 1 <= int(self.y_classes) <= 256:
+            raise NotImplementedError(f"y_condition with y_classes={self.y_classes}: the class-conditional kernels take 1 to 256 classes")
         self.sample_size, self.image_input = args.sample_size, True
         self.input_size = [int(v) for v in args.input_size]
         self.hidden = int(args.h_size)
@@ -215,6 +232,9 @@ class ImageGlow(nn.Module):
         Cz, Hz, Wz = self.flow.output_shapes[-1][1:]
         if self.learn_top:
             self.learn_top_fn = Conv2dZeros(Cz * 2, Cz * 2)
+        if self.y_condition:
+            self.project_ycond = LinearZeros(int(self.y_classes), 2 * Cz)
+            self.project_class = LinearZeros(Cz, int(self.y_classes))
         self.register_buffer("prior_h", torch.zeros([1, Cz * 2, Hz, Wz]))
         self.register_buffer("bounds", torch.tensor([0.9], dtype=torch.float32))
         self.dequant_flows = None
@@ -268,9 +288,19 @@ def image_spec_from_glow_module(glow):
             levels.append({"steps": steps, "split": _conv_spec(layer.conv)})
             steps = []
     levels.append({"steps": steps, "split": None})
-    return {"kind": "glow_image", "input_size": list(glow.input_size), "hidden": glow.hidden, "coupling": coupling,
+    spec = {"kind": "glow_image", "input_size": list(glow.input_size), "hidden": glow.hidden, "coupling": coupling,
             "bounds": float(glow.bounds.item()), "levels": levels,
             "learn_top": _conv_spec(glow.learn_top_fn) if glow.learn_top else None}
+    if getattr(glow, "y_condition", False):          # (the key is absent from an unconditional component's spec)
+        spec["ycond"] = _ycond_spec(glow)
+    return spec
+
+
+def _ycond_spec(glow):
+    """project_ycond / project_class of a class-conditional ImageGlow -> the spec's "ycond" entry (native.NativeImageFlow.set_ycond)."""
+    pc, pk = glow.project_ycond, glow.project_class
+    return {"cond_w": _np(pc.linear.weight), "cond_b": _np(pc.linear.bias), "cond_logs": _np(pc.logs),
+            "class_w": _np(pk.linear.weight), "class_b": _np(pk.linear.bias), "class_logs": _np(pk.logs)}
 
 
 def _put(dst, src):
@@ -318,6 +348,16 @@ def load_image_spec(glow, spec):
             pi += 1
     if spec["learn_top"] is not None:
         _load_conv(glow.learn_top_fn, spec["learn_top"])
+    yc = spec.get("ycond")
+    if (yc is not None) != bool(getattr(glow, "y_condition", False)):
+        raise ValueError("the spec and the module disagree about y_condition")
+    if yc is not None:
+        if yc.get("class_w") is None:
+            raise ValueError("a module's class-conditional component has a class head: the spec's ycond entry needs class_w / class_b / class_logs")
+        for lin, pre in ((glow.project_ycond, "cond"), (glow.project_class, "class")):
+            _put(lin.linear.weight, yc[pre + "_w"])
+            _put(lin.linear.bias, yc[pre + "_b"])
+            _put(lin.logs, yc[pre + "_logs"])
 
 
 class _ImageFlowFunction(torch.autograd.Function):
@@ -428,6 +468,19 @@ class BoostedImageFlow(nn.Module):
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
             raise native.GbnfError("x must live on the MI355X (cuda) device: this module has no CPU path")
 
+    def _y(self, c, y_onehot, n=None):
+        """``y_onehot`` as component c's kernels take it: (n, y_classes) contiguous float32 on the device; None for an unconditional
+        component (which ignores the argument, as the reference does).  A class-conditional one refuses None (the reference asserts)."""
+        flow = self.flows[c]
+        if not flow.y_condition:
+            return None
+        if y_onehot is None:
+            raise ValueError("this model is class-conditional (y_condition): y_onehot is required")
+        self._check(y_onehot)
+        if y_onehot.dim() != 2 or y_onehot.shape[1] != int(flow.y_classes) or (n is not None and y_onehot.shape[0] != n):
+            raise ValueError(f"y_onehot must be ({'n' if n is None else n}, {int(flow.y_classes)}), got {tuple(y_onehot.shape)}")
+        return y_onehot.contiguous().float()
+
     def _recording(self, c):
         """Train mode with gradients enabled: the component's forward is recorded for autograd."""
         return self.training and torch.is_grad_enabled() and any(p.requires_grad for p in self._component_tensors(c)[0])
@@ -533,6 +586,13 @@ class BoostedImageFlow(nn.Module):
                 if flow.learn_top:
                     top = flow.learn_top_fn
                     trainer.bind_top(top.conv.weight.detach(), top.conv.bias.detach(), top.logs.detach())
+                if flow.y_condition:
+                    pc, pk = flow.project_ycond, flow.project_class
+                    for t in (pc.linear.weight, pc.linear.bias, pc.logs, pk.linear.weight, pk.linear.bias, pk.logs):
+                        if not t.is_contiguous() or t.dtype != torch.float32:
+                            t.data = t.data.float().contiguous()
+                    trainer.bind_ycond(pc.linear.weight.detach(), pc.linear.bias.detach(), pc.logs.detach(), pk.linear.weight.detach(),
+                                       pk.linear.bias.detach(), pk.logs.detach())
             trainer.step_bound = True
         return trainer, bind
 
@@ -555,6 +615,11 @@ class BoostedImageFlow(nn.Module):
             top = flow.learn_top_fn
             names.update({("learn_top", "w"): ids[id(top.conv.weight)], ("learn_top", "b"): ids[id(top.conv.bias)],
                           ("learn_top", "logs"): ids[id(top.logs)]})
+        if flow.y_condition:
+            pc, pk = flow.project_ycond, flow.project_class
+            for key, t in zip(native.NativeImageTrainer.YCOND_KEYS,
+                              (pc.linear.weight, pc.linear.bias, pc.logs, pk.linear.weight, pk.linear.bias, pk.logs)):
+                names[("ycond", key)] = ids[id(t)]
         return names
 
     def step_parameters(self, c):
@@ -576,7 +641,7 @@ class BoostedImageFlow(nn.Module):
         return st
 
     def training_step(self, x, *, lr, weight_decay=0.0, max_grad_norm=0.0, optimizer="adamw", betas=(0.9, 0.999), eps=1e-8,
-                      noise=None, bits_per_dim=True, want_grads=False, fixed=None, g_floor=-10.0):
+                      noise=None, bits_per_dim=True, want_grads=False, fixed=None, g_floor=-10.0, y_onehot=None, y_weight=0.01):
         """The body of one iteration of the reference's image training loop (image_experiment.py:378-419) for ``self.component`` in one
         library call (gbnf_image_trainer_nll_step): the loss ``mean(-(log_normal_diag(z, z_mu, z_var) + logdet))`` -- divided by
         ``ln 2 * C*H*W`` with ``bits_per_dim`` (:227-229) --, ``loss.backward()``, ``clip_grad_norm_`` (``max_grad_norm`` > 0) and the
@@ -595,7 +660,13 @@ class BoostedImageFlow(nn.Module):
         return.  ``fixed="sample"``: the reference's draw, ``_sample_component('-c' if all_trained else '1:c-1')`` (a host read of
         ``rho`` with more than one candidate); for the FIRST component this is the trained component itself, as in the reference, whose
         evaluation handle is then re-packed every step because its parameters move: ``fixed=None`` is recommended there.  ``fixed=int``:
-        that component."""
+        that component.
+
+        ``y_onehot`` (n, y_classes), required by a class-conditional model: the loss gains ``y_weight`` * mean cross-entropy of the
+        class head against argmax(y_onehot) (image_experiment.py:231-239, the cross_entropy branch; the reference's y_weight is 0.01),
+        the prior is per image, and the six tensors of ``project_ycond`` / ``project_class`` are updated too
+        (gbnf_image_trainer_nll_step_y).  The result gains ``loss_classes`` (the mean cross-entropy, unweighted) and ``class_correct``
+        (rows whose largest logit is at argmax y).  A ``fixed`` component is evaluated with the same ``y_onehot``."""
         self._check(x)
         if x.requires_grad:
             raise NotImplementedError("the image training path has no gradient with respect to x")
@@ -612,6 +683,13 @@ class BoostedImageFlow(nn.Module):
                 raise ValueError(f"fixed={fixed!r} is no component of this model (0 .. {self.num_components - 1})")
         x = x.contiguous().float()
         noise = torch.rand_like(x) if noise is None else noise.contiguous().float()
+        y = self._y(c, y_onehot, x.shape[0])
+        if y is not None:
+            if fc is not None and not self.flows[fc].y_condition:
+                raise ValueError("the fixed component of a class-conditional step must be class-conditional too")
+            hyper_y = dict(y=y, y_weight=float(y_weight))
+        else:
+            hyper_y = {}
         with torch.cuda.device(x.device):
             trainer, bind = self._step_trainer(c)
             state = self.opt_state(c, optimizer, trainer)
@@ -619,22 +697,28 @@ class BoostedImageFlow(nn.Module):
             hyper = dict(loss_scale=per_dim if bits_per_dim else 1.0, lr=lr, weight_decay=weight_decay, max_grad_norm=max_grad_norm,
                          betas=betas, eps=eps)
             if fixed is None:
-                stats, flat = trainer.nll_step(x, noise, state, **hyper)
+                stats, flat = trainer.nll_step(x, noise, state, **hyper, **hyper_y)
             else:
-                stats, flat = trainer.boosted_nll_step(self.native_flow(fc), x, noise, state, g_floor=g_floor, **hyper)
+                stats, flat = trainer.boosted_nll_step(self.native_flow(fc), x, noise, state, g_floor=g_floor, **hyper, **hyper_y)
         # the kernels wrote the parameters behind autograd's back: move their version counters (host only, no launch) so that the
         # packed evaluation copy keyed on them (native_flow) is rebuilt
         torch.autograd.graph.increment_version(self._component_tensors(c)[0])
         out = {"nll": stats[0], "bpd": stats[0] * per_dim, "grad_norm": stats[1], "clip_coef": stats[2]}
+        g = 8 if y is not None else 4                    # (the class-conditional calls keep the G term behind the class statistics)
+        if y is not None:
+            out.update({"loss_classes": stats[4], "class_correct": stats[5]})
         if fc is not None:
-            out.update({"G_nll": stats[4], "boosted_nll": stats[5], "boosted_bpd": stats[5] * per_dim, "fixed_component": fc})
+            out.update({"G_nll": stats[g], "boosted_nll": stats[g + 1], "boosted_bpd": stats[g + 1] * per_dim, "fixed_component": fc})
         if want_grads:
             views = trainer.step_views(flat)
             out["grads"] = {name: views[path] for path, name in self._step_names(c, bind).items()}
         return out
 
-    def _component_forward_train(self, x, c, noise):
-        """Differentiable (z, z_mu, z_var, ldj, None) of component c on its live parameters (models/glow.py:92-110)."""
+    def _component_forward_train(self, x, c, noise, y=None):
+        """Differentiable (z, z_mu, z_var, ldj, y_logits) of component c on its live parameters (models/glow.py:92-110).  y_logits is
+        None for an unconditional component; a class-conditional one forms its per-image prior and its logits from the live
+        ``project_ycond`` / ``project_class`` with torch ops on (n, 2Cz) and (n, Y) tensors, so the reference's own
+        ``loss.backward()`` loop reaches all six tensors."""
         if x.requires_grad:
             raise NotImplementedError("the image training path has no gradient with respect to x")
         flow = self.flows[c]
@@ -665,23 +749,39 @@ class BoostedImageFlow(nn.Module):
             h = top.conv.bias * torch.exp(top.logs.view(-1) * top.logscale_factor) + 0.0 * top.conv.weight.sum()
             z_mu, z_var = h[:Cz].view(1, -1, 1, 1).expand(z.shape), h[Cz:].view(1, -1, 1, 1).expand(z.shape)
         else:
+            h = None
             z_mu = z_var = torch.zeros((), dtype=z.dtype, device=z.device).expand(z.shape)
-        return z, z_mu, z_var, ldj, None
+        if not flow.y_condition:
+            return z, z_mu, z_var, ldj, None
+        yp = flow.project_ycond(y)                       # (n, 2Cz), models/glow.py:79-82
+        hy = yp if h is None else h.view(1, -1) + yp
+        z_mu, z_var = hy[:, :Cz].view(-1, Cz, 1, 1).expand(z.shape), hy[:, Cz:].view(-1, Cz, 1, 1).expand(z.shape)
+        return z, z_mu, z_var, ldj, flow.project_class(z.mean(2).mean(2))
 
-    def component_forward(self, x, c, noise=None, want_z=True):
+    def component_forward(self, x, c, noise=None, want_z=True, y_onehot=None):
         """x (N,C,H,W) in [0,1] -> z, ldj, ll of component c.  ``noise``: the U(0,1) dequantisation noise
         (models/glow.py:135); drawn on the device when None.  In train mode with gradients enabled: the differentiable
-        (z, z_mu, z_var, ldj, None) of ``forward`` on the live parameters instead."""
+        (z, z_mu, z_var, ldj, y_logits) of ``forward`` on the live parameters instead.  A class-conditional component needs
+        ``y_onehot`` (n, y_classes) and returns the reference's five values in evaluation mode too:
+        (z, z_mu, z_var, ldj, y_logits) with the (n,Cz,1,1) priors expanded as views -- its ll under that prior is
+        ``component_log_prob``'s."""
         self._check(x)
+        y = self._y(int(c), y_onehot, x.shape[0])
         if self._recording(int(c)):
             xx = x if x.requires_grad else x.contiguous().float()
             nn_ = torch.rand_like(xx) if noise is None else noise.contiguous().float()
-            return self._component_forward_train(xx, int(c), nn_)
+            return self._component_forward_train(xx, int(c), nn_, y)
         x = x.contiguous().float()
         if noise is None:
             noise = torch.rand_like(x)
         with torch.cuda.device(x.device):
-            return self.native_flow(int(c)).forward(x, noise.contiguous().float(), want_z=want_z)
+            handle = self.native_flow(int(c))
+            if y is None:
+                return handle.forward(x, noise.contiguous().float(), want_z=want_z)
+            z, ldj, _, logits = handle.forward(x, noise.contiguous().float(), want_z=True, y=y)
+            mu, lv, _ = handle.prior_y(y)
+        cz = z.shape[1]
+        return z, mu.view(-1, cz, 1, 1).expand(z.shape), lv.view(-1, cz, 1, 1).expand(z.shape), ldj, logits
 
     def numerics_status(self, n_used=None, direction="forward"):
         """State of the image path's numerics protocol over the first n_used components (no synchronisation), with the keys of
@@ -715,15 +815,24 @@ class BoostedImageFlow(nn.Module):
             handle.__dict__["_prior_dev"] = prior
         return prior
 
-    def decode(self, z, y_onehot=None, temperature=1.0, components="c", eps=None):
+    def decode(self, z, y_onehot=None, temperature=1.0, components="c", eps=None, e=None):
         """models/boosted_flow.py:208-218 -> Glow.decode (models/glow.py:112-123) of one component (the reference's own
         BoostedFlow.decode dies on a misspelt keyword; the component-level decode is the parity target,
         fixtures g16_*).  z None: ``sample_size`` draws from the top prior, z = Normal(z_mu, exp(z_var) * temperature) as the
-        reference writes it.  ``eps``: the standard-normal draws of the Split2d levels (native.NativeImageFlow.inverse)."""
+        reference writes it.  ``eps``: the standard-normal draws of the Split2d levels (native.NativeImageFlow.inverse).
+        A class-conditional component with z None draws ``y_onehot.shape[0]`` images, row i from the prior of ``y_onehot[i]``
+        (gbnf_image_flow_prior_y; ``e``: the standard-normal draws behind the top latents, (n,) + z_shape, drawn when None) -- the
+        reference's Glow.decode(z=None, y_onehot=y) dies on ``data.shape[0]`` of a None (models/glow.py:82)."""
         c = self._sample_component(components) if isinstance(components, str) else int(components)
         handle = self.native_flow(c)
         temperature = 1.0 if temperature is None else float(temperature)
-        if z is None:
+        if z is None and self.flows[c].y_condition:
+            y = self._y(c, y_onehot)
+            with torch.cuda.device(y.device):
+                if e is None:
+                    e = torch.randn((y.shape[0],) + tuple(handle.z_shape), device=y.device, dtype=torch.float32)
+                z = handle.prior_y(y, e.contiguous().float(), temperature, want_prior=False)[2]
+        elif z is None:
             dev = self.rho.device
             mu, lv = self._prior_on(handle, dev)
             n = int(self.flows[c].sample_size)
@@ -734,14 +843,16 @@ class BoostedImageFlow(nn.Module):
             return handle.inverse(z.contiguous().float(), eps, temperature)
 
     @torch.no_grad()
-    def sample(self, n=None, *, temperature=1.0, n_used=None, e=None, eps=None, uniforms=None, generator=None, return_components=False):
+    def sample(self, n=None, *, temperature=1.0, n_used=None, e=None, eps=None, uniforms=None, generator=None, return_components=False,
+               y_onehot=None):
         """Images of the MIXTURE: every row through a component of its own, drawn from ``rho[0:n_used]`` per row on ``uniforms`` (n,)
         (BoostedFlow.sample; the sample(model, args) of image_experiment.py:280-293 draws one component for all rows).  ``e``: the
         standard-normal draws behind the top latents, (n,) + z_shape: rows of component c get z = mu_c + exp(lv_c) * temperature * e[rows],
         ``decode``'s formula; ``eps``: the Split2d draws, one (n, ...) tensor per level as ``decode`` takes them.  The draw and the
         partition run on the device (native.mixture_partition, one host read of the segment sizes); each component's rows are one
         ``native_flow(c).inverse`` call, gathered and written back by torch indexing.  Defaults: n = ``sample_size``, e / eps / uniforms
-        from ``generator``, n_used = the trained components.  Returns x (n,C,H,W), and ``comp`` (n,) int32 with ``return_components``."""
+        from ``generator``, n_used = the trained components.  Returns x (n,C,H,W), and ``comp`` (n,) int32 with ``return_components``.
+        A class-conditional model needs ``y_onehot`` (n, y_classes): row i is drawn from its component's prior of ``y_onehot[i]``."""
         if n_used is None:
             n_used = self.num_components if self.all_trained else self.component + 1
         n_used = int(n_used)
@@ -750,7 +861,8 @@ class BoostedImageFlow(nn.Module):
         temperature = 1.0 if temperature is None else float(temperature)
         dev = self.rho.device
         handles = [self.native_flow(c) for c in range(n_used)]
-        for given in (e, uniforms) + tuple(eps or ()):
+        y = self._y(0, y_onehot)
+        for given in (e, uniforms, y) + tuple(eps or ()):
             if given is not None and n is None:
                 n = given.shape[0]
         n = int(self.flows[0].sample_size) if n is None else int(n)
@@ -761,6 +873,8 @@ class BoostedImageFlow(nn.Module):
         if uniforms is None:
             uniforms = torch.rand(n, device=dev, dtype=torch.float32, generator=generator)
         self._check(e)
+        if y is not None and y.shape[0] != n:
+            raise ValueError(f"y_onehot must have {n} rows, got {y.shape[0]}")
         if e.shape != (n,) + tuple(handles[0].z_shape) or uniforms.shape != (n,) or any(t.shape[0] != n for t in eps):
             raise ValueError(f"e must be {(n,) + tuple(handles[0].z_shape)}, uniforms ({n},) and every eps tensor ({n}, ...)")
         e = e.contiguous().float()
@@ -773,8 +887,11 @@ class BoostedImageFlow(nn.Module):
                     continue
                 rows = order[begin:begin + m]
                 begin += m
-                mu, lv = self._prior_on(handles[c], e.device)
-                z_c = mu + torch.exp(lv) * temperature * e[rows]
+                if y is not None:
+                    z_c = handles[c].prior_y(y[rows].contiguous(), e[rows].contiguous(), temperature, want_prior=False)[2]
+                else:
+                    mu, lv = self._prior_on(handles[c], e.device)
+                    z_c = mu + torch.exp(lv) * temperature * e[rows]
                 x[rows] = handles[c].inverse(z_c.contiguous(), [t[rows].contiguous().float() for t in eps], temperature)
         return (x, comp) if return_components else x
 
@@ -783,8 +900,8 @@ class BoostedImageFlow(nn.Module):
             return self.decode(z, y_onehot, temperature, components)
         c = self._sample_component(components) if isinstance(components, str) else int(components)
         self._check(x)
-        if self._recording(c):
-            return self.component_forward(x, c)
+        if self._recording(c) or self.flows[c].y_condition:
+            return self.component_forward(x, c, y_onehot=y_onehot)
         zz, ldj, _ = self.component_forward(x, c)
         handle = self.native_flow(c)
         prior = self._prior_on(handle, x.device)
@@ -863,12 +980,20 @@ class BoostedImageFlow(nn.Module):
                 m.inited = True
         self._handles.clear()
 
-    def component_log_prob(self, x, n_used=None, noise=None):
+    def component_log_prob(self, x, n_used=None, noise=None, y_onehot=None):
         """(N, C_used): ll_c = log_normal_diag(z, z_mu, z_var) + logdet (image_experiment.py:227); the SAME noise for every
-        component unless the caller passes one per call."""
+        component unless the caller passes one per call.  A class-conditional model needs ``y_onehot`` (N, y_classes): ll_c is
+        taken under component c's prior of each row's y."""
         n_used = self.num_components if n_used is None else int(n_used)
         if noise is None:
             noise = torch.rand_like(x.float())
+        y = self._y(0, y_onehot, x.shape[0])
+        if y is not None:                                # (one chain after the other on the current stream)
+            self._check(x)
+            x, noise = x.contiguous().float(), noise.contiguous().float()
+            with torch.cuda.device(x.device):
+                return torch.stack([self.native_flow(c).forward(x, noise, want_z=False, y=y, want_logits=False)[2] for c in range(n_used)],
+                                   dim=1)
         if n_used == 1:
             return self.component_forward(x, 0, noise, want_z=False)[2].unsqueeze(1)
         # the components are independent until the recursion and a component is a chain of ~50 latency-bound launches:
@@ -903,6 +1028,9 @@ class BoostedImageFlow(nn.Module):
         launch sequence and are counted on the device, so a replay repairs an out-of-range image exactly like a stream call; when
         an on-data check has demoted a handle, ``f`` re-captures so that the graph runs the exact-f32 kernels directly instead of
         the split-f16 pass + full repair.)"""
+        if self.flows[0].y_condition:
+            raise NotImplementedError("graphed_log_prob of a class-conditional model is not built: the captured graph has no y input "
+                                      "(use log_prob(x, y_onehot=...))")
         n_used = self.num_components if n_used is None else int(n_used)
         dev = self.rho.device
         state = {}
@@ -942,9 +1070,10 @@ class BoostedImageFlow(nn.Module):
 
         return f
 
-    def log_prob(self, x, n_used=None, noise=None):
-        """(N,): log mixture density with the reference's recursion over rho (density_experiment.py:561-573)."""
-        ll = self.component_log_prob(x, n_used, noise)
+    def log_prob(self, x, n_used=None, noise=None, y_onehot=None):
+        """(N,): log mixture density with the reference's recursion over rho (density_experiment.py:561-573); ``y_onehot`` as
+        ``component_log_prob``."""
+        ll = self.component_log_prob(x, n_used, noise, y_onehot)
         with torch.cuda.device(x.device):
             return native.mixture_lse(ll.t().contiguous(), self.rho)
 
@@ -985,6 +1114,9 @@ class BoostedImageFlow(nn.Module):
             return
         if getattr(self.args, "rho_iters", 0) == 0:
             return
+        if self.flows[0].y_condition:
+            raise NotImplementedError("update_rho of a class-conditional model is not built: gbnf_image_mixture_rho_step takes no y "
+                                      "(the reference's rho_iters default is 0: the update is skipped there)")
         self.eval()
         c = int(self.component)
         rho = self.rho

@@ -54,6 +54,9 @@ ABI_SYMBOLS = (
     "gbnf_image_rho_step_workspace_bytes", "gbnf_image_mixture_rho_step",
     "gbnf_image_boosted_step_workspace_bytes", "gbnf_image_boosted_nll_step",
     "gbnf_mixture_sample_workspace_bytes", "gbnf_mixture_sample_begin", "gbnf_mixture_sample_finish",
+    "gbnf_image_flow_set_ycond", "gbnf_image_flow_y_classes", "gbnf_image_flow_forward_y", "gbnf_image_flow_prior_y",
+    "gbnf_image_trainer_bind_ycond", "gbnf_image_trainer_y_classes", "gbnf_image_trainer_nll_step_y",
+    "gbnf_image_boosted_step_workspace_bytes_y", "gbnf_image_boosted_nll_step_y",
 )
 
 
@@ -254,6 +257,16 @@ def lib():
     L.gbnf_mixture_sample_workspace_bytes.argtypes = [i32, i64, i32, C.POINTER(i64)]
     L.gbnf_mixture_sample_begin.argtypes = [vp, i32, vp, vp, i64, i32, vp, vp, vp, vp, i64, vp]
     L.gbnf_mixture_sample_finish.argtypes = [C.POINTER(vp), i32, C.POINTER(i64), vp, i64, vp, vp, vp, i64, vp]
+    L.gbnf_image_flow_set_ycond.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.gbnf_image_flow_y_classes.argtypes = [vp, C.POINTER(i32)]
+    L.gbnf_image_flow_forward_y.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
+    L.gbnf_image_flow_prior_y.argtypes = [vp, vp, i64, vp, C.c_float, vp, vp, vp]
+    L.gbnf_image_trainer_bind_ycond.argtypes = [vp, i32, vp, vp, vp, vp, vp, vp]
+    L.gbnf_image_trainer_y_classes.argtypes = [vp, C.POINTER(i32)]
+    L.gbnf_image_trainer_nll_step_y.argtypes = [vp, vp, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp, C.POINTER(_OptHyper), vp, vp, i64, vp]
+    L.gbnf_image_boosted_step_workspace_bytes_y.argtypes = [vp, vp, i64, C.POINTER(i64)]
+    L.gbnf_image_boosted_nll_step_y.argtypes = [vp, C.c_float, vp, vp, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp, C.POINTER(_OptHyper),
+                                                vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -478,6 +491,9 @@ class NativeImageFlow:
     """One packed image Glow component (gbnf_image_flow).  ``spec``: the image flow spec of ``synth.synth_image_glow_spec``
     / ``spec.image_spec_from_glow_module`` (numpy arrays)."""
 
+    y_classes = 0               # (class defaults: a plain handle, also for an object wrapped around a raw handle without __init__)
+    has_class_head = False
+
     def __init__(self, spec, math="default"):
         desc, keep = image_flow_desc_from_spec(spec)
         h = C.c_void_p()
@@ -493,6 +509,65 @@ class NativeImageFlow:
         self.z_shape = (zc.value, zh.value, zw.value)
         self.macs_per_image = macs.value
         self._ws = None
+        self.y_classes = 0
+        self.has_class_head = False
+        if spec.get("ycond") is not None:
+            self.set_ycond(spec["ycond"])
+
+    def set_ycond(self, yc):
+        """gbnf_image_flow_set_ycond: make the handle class-conditional.  ``yc``: the spec's ``"ycond"`` entry -- ``cond_w`` (2Cz, Y),
+        ``cond_b``, ``cond_logs`` (2Cz,) of project_ycond and ``class_w`` (Y, Cz), ``class_b``, ``class_logs`` (Y,) of project_class
+        (``class_w`` None: no class head), numpy arrays."""
+        keep = _Keep()
+        cz = self.z_shape[0]
+        cond_w = np.asarray(yc["cond_w"], dtype=np.float32)
+        if cond_w.ndim != 2 or cond_w.shape[0] != 2 * cz:
+            raise GbnfError(f"ycond cond_w must be (2*{cz}, Y), got {cond_w.shape}")
+        y = int(cond_w.shape[1])
+        want = {"cond_b": (2 * cz,), "cond_logs": (2 * cz,)}
+        head = yc.get("class_w") is not None
+        if head:
+            want.update({"class_w": (y, cz), "class_b": (y,), "class_logs": (y,)})
+        ptrs = {"cond_w": keep.f32(cond_w)}
+        for key, shape in want.items():
+            a = np.asarray(yc[key], dtype=np.float32)
+            if a.size != int(np.prod(shape)):
+                raise GbnfError(f"ycond {key} must have shape {shape}, got {a.shape}")
+            ptrs[key] = keep.f32(a.reshape(-1))
+        null = C.c_void_p(0)
+        as_vp = lambda k: C.cast(ptrs[k], C.c_void_p) if k in ptrs else null
+        _check(lib().gbnf_image_flow_set_ycond(self.handle, y, as_vp("cond_w"), as_vp("cond_b"), as_vp("cond_logs"), as_vp("class_w"),
+                                               as_vp("class_b"), as_vp("class_logs")))
+        del keep
+        self.y_classes, self.has_class_head = y, head
+
+    def _check_y(self, y, n):
+        _require_device_f32(y, "y")
+        if y.dim() != 2 or tuple(y.shape) != (n, self.y_classes):
+            raise GbnfError(f"y must be ({n},{self.y_classes}), got {tuple(y.shape)}")
+        return y.contiguous()
+
+    def prior_y(self, y, e=None, temperature=1.0, want_prior=True):
+        """gbnf_image_flow_prior_y: y (n, Y) -> (mean (n,Cz), log-variance (n,Cz)) of the per-image prior and, with standard-normal
+        ``e`` (n,Cz,Hz,Wz), the top latent z = mean + exp(log-variance) * temperature * e of a class-conditional draw
+        (models/glow.py:116 as written).  Returns (mean, logvar, z | None); current stream."""
+        import torch
+        n = y.shape[0] if y is not None and hasattr(y, "shape") else 0
+        y = self._check_y(y, n)
+        cz = self.z_shape[0]
+        ml = torch.empty((n, 2 * cz), dtype=torch.float32, device=y.device) if want_prior else None
+        z = None
+        if e is not None:
+            _require_device_f32(e, "e")
+            if tuple(e.shape) != (n,) + self.z_shape:
+                raise GbnfError(f"e must be {(n,) + self.z_shape}, got {tuple(e.shape)}")
+            e = e.contiguous()
+            z = torch.empty_like(e)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_image_flow_prior_y(self.handle, ptr(y), n, ptr(e), float(temperature), ptr(ml), ptr(z), _stream_ptr()))
+        if ml is None:
+            return None, None, z
+        return ml[:, :cz], ml[:, cz:], z
 
     def numerics(self):
         """gbnf_image_flow_numerics: math mode the handle runs in, the create-time probe's verdict (worst_rel_err, demoted),
@@ -547,9 +622,13 @@ class NativeImageFlow:
         a = np.frombuffer(buf, dtype=np.float32).copy()
         return a[: self.z_shape[0]], a[self.z_shape[0]:]
 
-    def forward(self, x, noise=None, want_z=True):
-        """x (n,C,H,W) in [0,1] (+ dequantisation noise) -> (z | None, ldj (n,), ll (n,)); current stream."""
+    def forward(self, x, noise=None, want_z=True, y=None, want_logits=None):
+        """x (n,C,H,W) in [0,1] (+ dequantisation noise) -> (z | None, ldj (n,), ll (n,)); current stream.  A class-conditional
+        handle needs ``y`` (n, Y) (gbnf_image_flow_forward_y) and returns (z | None, ldj, ll, y_logits (n, Y) | None): the logits
+        when the handle has a class head (``want_logits`` False: not asked for)."""
         import torch
+        if y is not None or self.y_classes > 0:
+            return self._forward_y(x, noise, want_z, y, want_logits)
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
@@ -570,6 +649,34 @@ class NativeImageFlow:
             _check(lib().gbnf_image_flow_forward(self.handle, ptr(x), ptr(noise), n, ptr(z), ptr(ldj), ptr(ll),
                                                  ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         return z, ldj, ll
+
+    def _forward_y(self, x, noise, want_z, y, want_logits):
+        import torch
+        _require_device_f32(x, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
+            raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        n = x.shape[0]
+        if y is not None and self.y_classes > 0:
+            y = self._check_y(y, n)
+        if want_logits is None:
+            want_logits = self.has_class_head
+        z = torch.empty((n,) + self.z_shape, dtype=torch.float32, device=x.device) if want_z else None
+        ldj = torch.empty(n, dtype=torch.float32, device=x.device)
+        ll = torch.empty(n, dtype=torch.float32, device=x.device)
+        logits = torch.empty((n, self.y_classes), dtype=torch.float32, device=x.device) if want_logits else None
+        nb = C.c_int64()
+        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
+        if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
+            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        # (a null y, a handle without conditioning: the library refuses, nothing launched)
+        _check(lib().gbnf_image_flow_forward_y(self.handle, ptr(x), ptr(noise), ptr(y), n, ptr(z), ptr(ldj), ptr(ll), ptr(logits),
+                                               ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+        return z, ldj, ll, logits
 
     def split_shapes(self):
         """(C_l/2, H_l, W_l) of the half each Split2d level drops (and re-draws on the way back), first level first."""
@@ -690,6 +797,8 @@ class NativeImageTrainer:
         self._region_tensors = []   # the bound tensor of each
         self._lu = {}               # (level, step) -> the LU factors bound there (bind_lu), in bind order
         self._top = None            # (weight | None, bias, logs) of learn_top_fn (bind_top)
+        self._ycond = None          # the six tensors of project_ycond / project_class (bind_ycond)
+        self.y_classes = 0
         self._off = 0
         fp = C.POINTER(C.c_float)
         keep = _Keep()
@@ -869,6 +978,11 @@ class NativeImageTrainer:
                     regions.append((("learn_top", name), off, tuple(t.shape)))
                     tensors.append(t)
                     off += t.numel()
+        if self._ycond is not None:
+            for name, t in zip(self.YCOND_KEYS, self._ycond):
+                regions.append((("ycond", name), off, tuple(t.shape)))
+                tensors.append(t)
+                off += t.numel()
         nf = C.c_int64()
         _check(lib().gbnf_image_trainer_step_grad_floats(self.handle, C.byref(nf)))
         if nf.value != off:
@@ -910,9 +1024,40 @@ class NativeImageTrainer:
         self._top = (weight, bias, logs)
         self._layout_step()
 
+    YCOND_KEYS = ("cond_w", "cond_b", "cond_logs", "class_w", "class_b", "class_logs")     # order of the conditioning's regions
+
+    def bind_ycond(self, cond_w, cond_b, cond_logs, class_w, class_b, class_logs):
+        """The live tensors of project_ycond ((2Cz, Y), (2Cz,), (2Cz,)) and project_class ((Y, Cz), (Y,), (Y,))
+        (gbnf_image_trainer_bind_ycond): the trainer becomes class-conditional -- ``nll_step`` and ``boosted_nll_step`` need ``y`` --
+        and the STEP layout gains their six regions behind the top prior's."""
+        cz = self.z_shape[0]
+        _require_device_f32(cond_w, "cond_w")
+        if cond_w.dim() != 2 or cond_w.shape[0] != 2 * cz:
+            raise GbnfError(f"bind_ycond: cond_w has shape {tuple(cond_w.shape)}, expected (2*{cz}, Y)")
+        y = int(cond_w.shape[1])
+        ts = (cond_w, cond_b, cond_logs, class_w, class_b, class_logs)
+        for name, t, numel in zip(self.YCOND_KEYS, ts, (2 * cz * y, 2 * cz, 2 * cz, y * cz, y, y)):
+            _require_device_f32(t, name)
+            if t.numel() != numel:
+                raise GbnfError(f"bind_ycond: {name} has {t.numel()} elements, expected {numel}")
+        ptr = lambda t: C.c_void_p(t.data_ptr())
+        _check(lib().gbnf_image_trainer_bind_ycond(self.handle, y, *[ptr(t) for t in ts]))
+        self._tensors += list(ts)
+        self._ycond = ts
+        self.y_classes = y
+        self._layout_step()
+
+    def _check_y(self, y, n):
+        if self.y_classes == 0:
+            raise GbnfError("the trainer has no conditioning bound (bind_ycond): it takes no y")
+        _require_device_f32(y, "y")
+        if tuple(y.shape) != (n, self.y_classes):
+            raise GbnfError(f"y must be ({n},{self.y_classes}), got {tuple(y.shape)}")
+        return y.contiguous()
+
     def step_views(self, flat):
         """{path: view} of a flat buffer in the STEP layout: the paths of ``backward`` plus (..., "lower" | "upper" | "log_s") of the
-        bound LU steps and ("learn_top", "w" | "b" | "logs")."""
+        bound LU steps, ("learn_top", "w" | "b" | "logs") and ("ycond", one of ``YCOND_KEYS``)."""
         if flat.numel() != self.step_grad_floats:
             raise GbnfError(f"flat has {flat.numel()} elements, expected {self.step_grad_floats}")
         return {path: flat[off: off + int(np.prod(shape))].view(shape) for path, off, shape in self._step_regions}
@@ -936,11 +1081,14 @@ class NativeImageTrainer:
         state.step += 1
         return stats
 
-    def nll_step(self, x, noise, state, loss_scale=1.0, **hyper):
+    def nll_step(self, x, noise, state, loss_scale=1.0, y=None, y_weight=0.01, **hyper):
         """One whole training step of this component on the device (gbnf_image_trainer_nll_step): 1x1 log-dets (LU matrices composed) ->
         forward on the live parameters -> loss_scale * mean nll and its seed -> backward -> log-det / LU / top-prior gradients -> clip ->
         optimiser update, no host read in between.  -> (stats (4,) device tensor: mean nll in nats (unscaled), norm of the scaled
-        gradient, clip coefficient, 0; the flat unclipped scaled gradient in the STEP layout)."""
+        gradient, clip coefficient, 0; the flat unclipped scaled gradient in the STEP layout).
+        With ``y`` (n, Y) on a trainer with conditioning bound (gbnf_image_trainer_nll_step_y): the loss is loss_scale * mean nll under
+        the per-image prior + ``y_weight`` * mean cross-entropy of the class head against argmax y, and stats has 8 floats: [4] the
+        mean cross-entropy, [5] the rows classified correctly, [6] [7] 0."""
         import torch
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
@@ -950,6 +1098,8 @@ class NativeImageTrainer:
             if noise.shape != x.shape:
                 raise GbnfError("noise must have the shape of x")
         n = x.shape[0]
+        if y is not None:
+            y = self._check_y(y, n)
         state.check(self)
         h = self._hyper(state, **hyper)
         nb = C.c_int64()
@@ -957,20 +1107,28 @@ class NativeImageTrainer:
         if self._step_ws is None or self._step_ws.numel() * 4 < nb.value or self._step_ws.device != x.device:
             self._step_ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
         flat = torch.empty(self.step_grad_floats, dtype=torch.float32, device=x.device)
-        stats = torch.zeros(4, dtype=torch.float32, device=x.device)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        if y is not None:
+            stats = torch.zeros(8, dtype=torch.float32, device=x.device)
+            _check(lib().gbnf_image_trainer_nll_step_y(self.handle, ptr(x), ptr(noise), ptr(y), n, float(loss_scale), float(y_weight),
+                                                       ptr(flat), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h), ptr(stats),
+                                                       ptr(self._step_ws), self._step_ws.numel() * 4, _stream_ptr()))
+            state.step += 1
+            return stats, flat
+        stats = torch.zeros(4, dtype=torch.float32, device=x.device)
         _check(lib().gbnf_image_trainer_nll_step(self.handle, ptr(x), ptr(noise), n, float(loss_scale), ptr(flat), ptr(state.exp_avg),
                                                  ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(self._step_ws),
                                                  self._step_ws.numel() * 4, _stream_ptr()))
         state.step += 1
         return stats, flat
 
-    def boosted_nll_step(self, fixed, x, noise, state, *, g_floor=-10.0, loss_scale=1.0, **hyper):
+    def boosted_nll_step(self, fixed, x, noise, state, *, g_floor=-10.0, loss_scale=1.0, y=None, y_weight=0.01, **hyper):
         """``nll_step`` with the fixed-mixture term of the boosted image loss (gbnf_image_boosted_nll_step): the forward of ``fixed`` (a
         ``NativeImageFlow`` of the same input size) on the same ``(x, noise)``, G_nll = mean(-max(ll_G, g_floor)) (``g_floor``
         = -inf: no clamp), then the step of this component, unchanged -- the G term is never differentiated.  -> (stats (8,) device
         tensor: [0..3] as ``nll_step``, [4] G_nll in nats, [5] nll - G_nll, [6] rows below the floor or non-finite, [7] 0; the flat
-        unclipped scaled gradient in the STEP layout)."""
+        unclipped scaled gradient in the STEP layout).  With ``y`` (gbnf_image_boosted_nll_step_y; ``fixed`` and this trainer both
+        class-conditional): stats (12,): [0..7] as ``nll_step`` with y, [8] G_nll, [9] nll - G_nll, [10] that row count, [11] 0."""
         import torch
         if not isinstance(fixed, NativeImageFlow) or not fixed.handle:
             raise GbnfError("fixed must be an open NativeImageFlow")
@@ -984,14 +1142,25 @@ class NativeImageTrainer:
         n = x.shape[0]
         state.check(self)
         h = self._hyper(state, **hyper)
+        if y is not None:
+            y = self._check_y(y, n)
         nb = C.c_int64()
-        _check(lib().gbnf_image_boosted_step_workspace_bytes(fixed.handle, self.handle, n, C.byref(nb)))
+        query = lib().gbnf_image_boosted_step_workspace_bytes_y if y is not None else lib().gbnf_image_boosted_step_workspace_bytes
+        _check(query(fixed.handle, self.handle, n, C.byref(nb)))
         if self._boost_ws is None or self._boost_ws.numel() * 4 < nb.value or self._boost_ws.device != x.device:
             self._boost_ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
         ws = self._boost_ws
         flat = torch.empty(self.step_grad_floats, dtype=torch.float32, device=x.device)
-        stats = torch.zeros(8, dtype=torch.float32, device=x.device)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        if y is not None:
+            stats = torch.zeros(12, dtype=torch.float32, device=x.device)
+            _check(lib().gbnf_image_boosted_nll_step_y(fixed.handle, float(g_floor), self.handle, ptr(x), ptr(noise), ptr(y), n,
+                                                       float(loss_scale), float(y_weight), ptr(flat), ptr(state.exp_avg),
+                                                       ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(ws), ws.numel() * 4,
+                                                       _stream_ptr()))
+            state.step += 1
+            return stats, flat
+        stats = torch.zeros(8, dtype=torch.float32, device=x.device)
         _check(lib().gbnf_image_boosted_nll_step(fixed.handle, float(g_floor), self.handle, ptr(x), ptr(noise), n, float(loss_scale),
                                                  ptr(flat), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(ws),
                                                  ws.numel() * 4, _stream_ptr()))

@@ -182,10 +182,11 @@ def _conv(rng, out_ch, in_ch, k, std, bias=False, actnorm=False, zeros_logs=Fals
 
 
 def synth_image_glow_spec(input_size=(3, 32, 32), h=32, K=2, L=2, depth=1, coupling="affine", permutation="invconv",
-                          learn_top=True, seed=0, gain=1.0, trained_like=False):
+                          learn_top=True, seed=0, gain=1.0, trained_like=False, y_classes=0):
     """One image Glow component (models/glow.py:192-233 FlowNet image branch: L x [squeeze, K FlowSteps, Split2d])
     with synthetic parameters.  ``permutation``: "invconv" (a random well-conditioned C x C matrix: what
-    InvertibleConv1x1.get_weight returns for either parameterisation), "shuffle" or "reverse"."""
+    InvertibleConv1x1.get_weight returns for either parameterisation), "shuffle" or "reverse".  ``y_classes`` > 0: a
+    class-conditional component: the spec gains a "ycond" entry (``synth_ycond``); with 0 the spec is what it always was."""
     rng = np.random.RandomState(seed)
     C, H, W = input_size
     levels = []
@@ -227,8 +228,24 @@ def synth_image_glow_spec(input_size=(3, 32, 32), h=32, K=2, L=2, depth=1, coupl
     top = None
     if learn_top:
         top = _conv(rng, 2 * C, 2 * C, 3, 0.05, bias=True, zeros_logs=True)
-    return {"kind": "glow_image", "input_size": [int(v) for v in input_size], "hidden": int(h), "coupling": coupling,
+    spec = {"kind": "glow_image", "input_size": [int(v) for v in input_size], "hidden": int(h), "coupling": coupling,
             "bounds": 0.9, "levels": levels, "learn_top": top}
+    if y_classes:
+        spec["ycond"] = synth_ycond(C, int(y_classes), seed)
+    return spec
+
+
+def synth_ycond(Cz, Y, seed=0):
+    """project_ycond / project_class (LinearZeros, models/layers.py:560-574) of a class-conditional Glow with Cz top channels and Y
+    classes as plain data, NON-zero (the modules start at zero, which would exercise nothing).  Drawn from a generator of their own:
+    the rest of a spec does not depend on whether it is conditioned."""
+    rng = np.random.RandomState(77_000 + int(seed))
+    return {"cond_w": (0.3 * rng.standard_normal((2 * Cz, Y))).astype(np.float32),
+            "cond_b": (0.1 * rng.standard_normal(2 * Cz)).astype(np.float32),
+            "cond_logs": (0.1 * rng.standard_normal(2 * Cz)).astype(np.float32),
+            "class_w": (0.5 * rng.standard_normal((Y, Cz))).astype(np.float32),
+            "class_b": (0.1 * rng.standard_normal(Y)).astype(np.float32),
+            "class_logs": (0.1 * rng.standard_normal(Y)).astype(np.float32)}
 
 
 def synth_image_batch(N, input_size=(3, 32, 32), seed=0):

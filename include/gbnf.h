@@ -628,7 +628,10 @@ typedef struct gbnf_image_flow gbnf_image_flow;
  * <= 64 channels per level; coupling ConvNets of hidden width <= 512 with 2 .. 5 convolutions (coupling_network_depth 0 .. 3);
  * the split-f16 kernels serve depth 1 at every hidden width (above 256 the fused kernel works in two halves of the hidden
  * channels), depth 0 and 2 to hidden width 256 (round 6), and <= 24 input channels of the first 3 x 3 (the 48-channel third level of a
- * 3 x 32 x 32 input); everything else runs on the exact-f32 convolution kernels.  Not built: y-conditioning, learned dequantisation flows. */
+ * 3 x 32 x 32 input); everything else runs on the exact-f32 convolution kernels.  Class conditioning (`--y_condition`) is the
+ * gbnf_image_flow_set_ycond family below: at most 256 classes, the cross_entropy branch of the reference's class loss only (its
+ * `multi_class` branch is reachable from no option of the reference and applies a sigmoid twice: left out).  Not built: learned
+ * dequantisation flows. */
 int gbnf_image_flow_create(const gbnf_image_flow_desc* desc, gbnf_image_flow** out);
 /* ... with an explicit GBNF_MATH_* mode: DEFAULT (what gbnf_image_flow_create does: split-f16 coupling nets if the create-time
  * probe passes), F32 (exact-f32 convolutions everywhere, no probe), F16X3. */
@@ -646,6 +649,36 @@ int gbnf_image_flow_forward(const gbnf_image_flow* flow, const float* x, const f
                             float* ldj, float* ll, void* workspace, int64_t workspace_bytes, void* stream);
 /* The top prior per channel: mean (Cz,) then log-variance (Cz,) into a HOST buffer of 2 Cz floats. */
 int gbnf_image_flow_prior(const gbnf_image_flow* flow, float* mean_logvar_host);
+/* ---- class-conditional components (Glow with y_condition, models/glow.py:36-39, 62-84, 105-106) --------------------------------
+ * Y = y_classes, (Cz, Hz, Wz) the top latent, HW = Hz * Wz (the map proper), top_h = what gbnf_image_flow_prior returns.
+ *   prior:  u = y W_c^T + b_c (n, 2Cz);  h_i = top_h + u_i exp(3 l_c);  z_mu[i,c] = h_i[c], z_var[i,c] = h_i[Cz + c], constant over the map;
+ *           ll_i = sum -0.5 (lv + (z - mu)^2 e^-lv) + ldj_i  (no 2 pi term, as everywhere on the image path);
+ *   head:   zbar[i,c] = mean of z[i,c] over the map;  y_logits_i = (zbar_i W_k^T + b_k) exp(3 l_k)  (n, Y).
+ * y (n, Y) is used as given: its rows need not be one-hot.
+ * gbnf_image_flow_set_ycond: project_ycond (cond_w (2Cz, Y), cond_b (2Cz,), cond_logs (2Cz,)) and project_class (class_w (Y, Cz),
+ * class_b (Y,), class_logs (Y,); all three NULL: no class head, no logits) as HOST pointers, copied at the call (it allocates and
+ * may be repeated).  1 <= Y <= 256 (GBNF_ERR_UNSUPPORTED above).  From then on the handle is class-conditional:
+ * gbnf_image_flow_forward and gbnf_image_flow_prior answer GBNF_ERR_INVALID ("needs y"), as do the calls built on them
+ * (gbnf_image_mixture_rho_step, gbnf_image_boosted_nll_step), and gbnf_image_flow_workspace_bytes reports a larger size (a compact z
+ * and a scratch ll behind the plain call's workspace).  gbnf_image_flow_inverse is unchanged: it starts from z.
+ * gbnf_image_flow_forward_y: x, noise, z, ldj as gbnf_image_flow_forward; y (n, Y) DEVICE; ll (n,) and y_logits (n, Y) may be NULL
+ * (y_logits on a handle without a class head: GBNF_ERR_INVALID).  The plain forward runs first with the y-free prior, its ll kept in
+ * the workspace, so the numerics protocol (range marks, the same-call repair launch, the on-data check) acts exactly as on a plain
+ * call; ONE more launch behind the repair launch in stream order then computes ll under the image's own prior and the logits from
+ * the (repaired) z and ldj: one workgroup per image, sums in double precision in a fixed order, no atomics.  No host read, no
+ * synchronisation, no allocation.
+ * gbnf_image_flow_prior_y: mean_logvar (n, 2Cz) DEVICE (mean half, log-variance half per image) and / or, with e (n, Cz, Hz, Wz)
+ * standard-normal draws, the top latent of a class-conditional sample z_out = mu + exp(lv) * temperature * e -- the reference's
+ * torch.normal(z_mu, exp(z_var) * temperature) as written (models/glow.py:116; note exp(lv), not exp(lv / 2)).  Either output may be
+ * NULL; z_out needs e.  gbnf_image_flow_y_classes: 0 for a plain handle. */
+int gbnf_image_flow_set_ycond(gbnf_image_flow* flow, int32_t y_classes, const float* cond_w, const float* cond_b,
+                              const float* cond_logs, const float* class_w_or_null, const float* class_b, const float* class_logs);
+int gbnf_image_flow_y_classes(const gbnf_image_flow* flow, int32_t* y_classes);
+int gbnf_image_flow_forward_y(const gbnf_image_flow* flow, const float* x, const float* noise, const float* y_dev, int64_t n,
+                              float* z, float* ldj, float* ll, float* y_logits_or_null, void* workspace, int64_t workspace_bytes,
+                              void* stream);
+int gbnf_image_flow_prior_y(const gbnf_image_flow* flow, const float* y_dev, int64_t n, const float* e_or_null, float temperature,
+                            float* mean_logvar_dev_or_null, float* z_out_or_null, void* stream);
 /* State of the image path's numerics protocol (the tabular one: gbnf_flow_numerics).  The coupling nets run on
  * split-f16 MFMA (GBNF_MATH_F16X3) when the create-time probe -- 4 synthetic images through both arithmetic paths --
  * agrees with the exact-f32 kernels to `tolerance` (worst_rel_err = what it measured), else the handle runs on exact f32
@@ -844,6 +877,33 @@ int gbnf_image_trainer_apply_update(gbnf_image_trainer* trainer, const float* gr
 int gbnf_image_trainer_nll_step(gbnf_image_trainer* trainer, const float* x, const float* noise, int64_t n, float loss_scale,
                                 float* grads, float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper,
                                 float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream);
+/* ---- the class-conditional step (image_experiment.py:227-239 with args.y_condition; the cross_entropy branch) ---------------------
+ *   loss = loss_scale * mean_i(nll_i) + y_weight * mean_i CE(y_logits_i, t_i),  t_i = the index of the largest entry of y_i (the
+ *   lowest index on a tie), nll_i under the per-image prior and y_logits as at gbnf_image_flow_set_ycond.
+ * gbnf_image_trainer_bind_ycond names the six live tensors of project_ycond and project_class (DEVICE pointers, all required,
+ * 1 <= Y <= 256) and rebuilds the tables as gbnf_image_trainer_bind_top does.  The STEP gradient layout gains, behind the top
+ * prior's regions and all subject to the update:
+ *   [cond weight 2Cz*Y] [cond bias 2Cz] [cond logs 2Cz] [class weight Y*Cz] [class bias Y] [class logs Y].
+ * From then on gbnf_image_trainer_nll_step answers GBNF_ERR_INVALID ("needs y"), gbnf_image_trainer_step_workspace_bytes reports a
+ * larger size (the per-image terms), and a workspace sized before binding is refused before the first launch.
+ * gbnf_image_trainer_nll_step_y: the eight steps of gbnf_image_trainer_nll_step with y (n, Y) DEVICE, used as given by the prior.
+ * Steps 3 + 4 are one launch, one workgroup per image: the prior, the head, a max-subtracted log-softmax, nll_i, CE_i, the seed
+ *   g_z = kn (z - mu) e^-lv + ((gl_i * e^{3 l_k}) W_k) / HW,  g_ldj = -kn,  kn = loss_scale / n,  gl_i = (y_weight / n)(softmax - onehot(t_i)),
+ * and the image's terms of the gradients of the top prior (now a sum over per-image priors), project_ycond and project_class.  Step 7
+ * gains one launch, one thread per parameter entry, that adds those terms in image order in double precision and WRITES the
+ * regions.  Neither launch uses an atomic: these regions, stats[4] and stats[5] are bit-identical from run to run in and out of
+ * deterministic mode; deterministic mode covers the whole call as it covers gbnf_image_trainer_nll_step.
+ * stats_dev (8 floats): [0] mean nll in nats, unscaled, under the y-conditioned prior; [1] [2] norm and clip coefficient of the whole
+ * scaled gradient; [3] 0; [4] mean cross-entropy, unweighted; [5] rows whose largest logit (f32, lowest index on a tie) is at t_i;
+ * [6] [7] 0.  GBNF_ERR_INVALID (nothing launched): what gbnf_image_trainer_nll_step refuses, a null y, a trainer without
+ * conditioning bound. */
+int gbnf_image_trainer_bind_ycond(gbnf_image_trainer* trainer, int32_t y_classes, float* cond_w, float* cond_b, float* cond_logs,
+                                  float* class_w, float* class_b, float* class_logs);
+int gbnf_image_trainer_y_classes(const gbnf_image_trainer* trainer, int32_t* y_classes);
+int gbnf_image_trainer_nll_step_y(gbnf_image_trainer* trainer, const float* x, const float* noise, const float* y_dev, int64_t n,
+                                  float loss_scale, float y_weight, float* grads, float* exp_avg, float* exp_avg_sq,
+                                  const gbnf_opt_hyper* hyper, float* stats_dev, void* workspace, int64_t workspace_bytes,
+                                  void* stream);
 
 /* ---- boosting for image components: the mixture weight of a component, and the boosted step's fixed-mixture term -----------------
  * Replaces: ONE iteration of BoostedFlow.update_rho (models/boosted_flow.py:119-207, the approximate branch) for image components --
@@ -868,7 +928,8 @@ int gbnf_image_trainer_nll_step(gbnf_image_trainer* trainer, const float* x, con
  * workspace: caller-owned DEVICE scratch of gbnf_image_rho_step_workspace_bytes(flows, component + 1, n) bytes -- the largest
  * gbnf_image_flow_workspace_bytes of the handles and the call's ldj accumulator, each 256-byte aligned.  GBNF_ERR_INVALID (nothing
  * launched): a null flows / x / rho_dev / ll_workspace / stats_dev / workspace or a null entry of flows, component < 1, n < 1, handles
- * whose input shape (channels, height, width) differs, a short workspace.  The partial sums live in the per-device buffer of
+ * whose input shape (channels, height, width) differs, a class-conditional handle anywhere in flows (the update has no y call), a
+ * short workspace.  The partial sums live in the per-device buffer of
  * gbnf_mixture_rho_step: two rho calls on one device must not run concurrently. */
 int gbnf_image_rho_step_workspace_bytes(const gbnf_image_flow* const* flows, int32_t n_flows, int64_t n, int64_t* bytes);
 int gbnf_image_mixture_rho_step(const gbnf_image_flow* const* flows, int32_t component, const float* x, const float* noise,
@@ -899,6 +960,16 @@ int gbnf_image_boosted_nll_step(const gbnf_image_flow* fixed, float g_floor, gbn
                                 const float* noise, int64_t n, float loss_scale, float* grads, float* exp_avg, float* exp_avg_sq,
                                 const gbnf_opt_hyper* hyper, float* stats_dev, void* workspace, int64_t workspace_bytes,
                                 void* stream);
+/* The class-conditional form: gbnf_image_flow_forward_y of `fixed` in step 1, gbnf_image_trainer_nll_step_y in step 3; both must be
+ * conditioned on the same number of classes (GBNF_ERR_INVALID otherwise; the plain call refuses conditioned ones).
+ * stats_dev: 12 DEVICE floats: [0..7] as gbnf_image_trainer_nll_step_y writes them; [8] G_nll; [9] stats[0] - stats[8]; [10] the row
+ * count of step 2; [11] 0 -- what the plain call keeps at [4..7]. */
+int gbnf_image_boosted_step_workspace_bytes_y(const gbnf_image_flow* fixed, const gbnf_image_trainer* trainer, int64_t n,
+                                              int64_t* bytes);
+int gbnf_image_boosted_nll_step_y(const gbnf_image_flow* fixed, float g_floor, gbnf_image_trainer* trainer, const float* x,
+                                  const float* noise, const float* y_dev, int64_t n, float loss_scale, float y_weight, float* grads,
+                                  float* exp_avg, float* exp_avg_sq, const gbnf_opt_hyper* hyper, float* stats_dev, void* workspace,
+                                  int64_t workspace_bytes, void* stream);
 
 /* ---- drawing from the mixture ----------------------------------------------------------------------------------------------------
  * Replaces: BoostedFlow.decode (models/boosted_flow.py:209-218), which sends ALL rows of a call through ONE component drawn on the
