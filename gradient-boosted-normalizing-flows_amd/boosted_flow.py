@@ -356,6 +356,13 @@ def image_deterministic_from(args, env=None):
     return _flag_from(args, env, "image_deterministic", "GBNF_IMAGE_DETERMINISTIC")
 
 
+def image_eval_deterministic_from(args, env=None):
+    """The deterministic-mode flag of an IMAGE module's evaluation handles (image_glow.BoostedImageFlow.image_eval_deterministic):
+    ``args.image_eval_deterministic``, else the environment variable GBNF_IMAGE_EVAL_DETERMINISTIC; the rules of
+    ``deterministic_from``.  A flag of its own: it reads neither of the other two and they do not read it."""
+    return _flag_from(args, env, "image_eval_deterministic", "GBNF_IMAGE_EVAL_DETERMINISTIC")
+
+
 def _flag_from(args, env, attr, var):
     given = getattr(args, attr, None)
     if given is not None:

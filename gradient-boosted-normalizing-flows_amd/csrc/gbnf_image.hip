@@ -347,9 +347,21 @@ __device__ __forceinline__ void img_conv_body(const ConvLaunch& p, const int n, 
   if constexpr (EPI == EPI_COUPLE_AFFINE_ORD || EPI == EPI_SPLIT_ORD) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) ld += __shfl_xor(ld, m);
-    const int slots = p.n_strips * p.o_split * IMG_WAVES;
+    const int slots = p.ldj_stride > 0 ? p.ldj_stride : p.n_strips * p.o_split * IMG_WAVES;
     if (lane == 0) p.ldj[(int64_t)n * slots + (strip * p.o_split + osp) * IMG_WAVES + wave] = ld;
   }
+}
+
+// The evaluation handle's deterministic mode: ldj[i] += the sum of the first `slots` floats of image i's row of the chain's
+// (n, stride) slot array, in slot order (every log-det-carrying launch of the component owns a run of the row)
+__global__ void __launch_bounds__(256) img_ldj_chain_reduce_kernel(const float* __restrict__ part, int stride, int slots, float* __restrict__ ldj,
+                                                                   int64_t n) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const float* src = part + i * stride;
+  float s = 0.0f;
+  for (int k = 0; k < slots; ++k) s += src[k];
+  ldj[i] += s;
 }
 
 // ldj[i] += the sum of image i's log-det slots of one EPI_*_ORD launch, in slot order
@@ -660,7 +672,7 @@ struct RepairOp {
   int kind, epi, pt, ks;
   ConvLaunch p;           // ROP_CONV: workspace pointers relative to IMG_REC_BASE, parameter pointers absolute
   int64_t a, b, c;        // the other ops: float offsets into the private workspace (source, destination, log-det slot)
-  int i[8];
+  int i[8];               // (ROP_FINAL of the deterministic programme: i[5] ordered log-det slots at offset b)
   float f[2];
   const float* prior;     // ROP_FINAL
   int64_t eps_img, eps_lvl;   // ROP_UNSQUEEZE: eps of this level = eps + eps_lvl * n_batch + image * eps_img (0 / 0: none)
@@ -757,6 +769,8 @@ __global__ void __launch_bounds__(64 * IMG_WAVES) img_repair_kernel(const Repair
             else if (op.epi == EPI_STORE) img_repair_conv<EPI_STORE>(p, op.pt, op.ks);
             else if (op.epi == EPI_COUPLE_AFFINE) img_repair_conv<EPI_COUPLE_AFFINE>(p, op.pt, op.ks);
             else if (op.epi == EPI_COUPLE_ADD) img_repair_conv<EPI_COUPLE_ADD>(p, op.pt, op.ks);
+            else if (op.epi == EPI_COUPLE_AFFINE_ORD) img_repair_conv<EPI_COUPLE_AFFINE_ORD>(p, op.pt, op.ks);     // (the deterministic
+            else if (op.epi == EPI_SPLIT_ORD) img_repair_conv<EPI_SPLIT_ORD>(p, op.pt, op.ks);                     //  mode's programme)
             else img_repair_conv<EPI_SPLIT>(p, op.pt, op.ks);
           } else {
             if (op.epi == EPI_RELU) img_repair_conv<EPI_RELU>(p, op.pt, op.ks);
@@ -780,7 +794,15 @@ __global__ void __launch_bounds__(64 * IMG_WAVES) img_repair_kernel(const Repair
             float* zo = (a.check || a.z == nullptr) ? nullptr : a.z + img * a.zsz;
             const float r = img_final_body(wsb + op.a, op.prior, zo, op.i[0], op.i[1], op.i[2], op.i[3], op.i[4]);
             if (threadIdx.x == 0) {
-              const float ldv = __hip_atomic_load(wsb + op.c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), llv = r + ldv;
+              float ldv = __hip_atomic_load(wsb + op.c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              if (op.i[5] > 0) {
+                // the deterministic mode's programme: the image's op.i[5] log-det slots at wsb + op.b, added as
+                // img_ldj_chain_reduce_kernel adds an exact-f32 handle's -- the same slots in the same order
+                float sum = 0.0f;
+                for (int q = 0; q < op.i[5]; ++q) sum += __hip_atomic_load(wsb + op.b + q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                ldv += sum;
+              }
+              const float llv = r + ldv;
               if (!a.check) {
                 a.ldj[img] = ldv;
                 if (a.ll) a.ll[img] = llv;
@@ -879,7 +901,13 @@ struct gbnf_image_flow {
   unsigned* dev_state = nullptr;
   RepairOp* ops_dev = nullptr;               // the exact-f32 sequence of ONE image as recorded ops: forward [0, n_ops_fwd), then z -> x
   int n_ops_fwd = 0, n_ops_inv = 0;
+  int n_ops_det = 0;                         // ... then the forward sequence of the deterministic mode (ordered log-det epilogues)
   size_t repair_lds_fwd = 0, repair_lds_inv = 0;
+  // gbnf_image_flow_set_deterministic: the forward direction's log-det partials go to per-image slots that one thread adds in slot
+  // order.  ldj_stride: floats of one image's slot row -- every log-det-carrying launch of the component at its LARGEST slot count
+  // over the kernels that may run it (fused, two-kernel, exact f32), a function of the geometry only.
+  int deterministic = 0;
+  int ldj_stride = 0;
   // gbnf_image_flow_set_ycond: project_ycond [2Cz Y | 2Cz | 2Cz] then project_class [Y Cz | Y | Y] (absent without a class head)
   int y_classes = 0;
   bool y_head = false;
@@ -1148,7 +1176,7 @@ struct ActNormStats;
 static int image_record_repair_ops(gbnf_image_flow* f);
 static int image_forward_impl(const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj, float* ll,
                               float* workspace, hipStream_t s, bool force_f32, unsigned* mark, ActNormStats* stats = nullptr,
-                              Recorder* rec = nullptr);
+                              Recorder* rec = nullptr, float* slots = nullptr);
 
 static int image_probe(gbnf_image_flow* f) {
   constexpr int PN = 4;
@@ -1328,6 +1356,7 @@ int gbnf_image_flow_create_mode(const gbnf_image_flow_desc* d, int32_t math_mode
         }
       }
       f->net.push_back(net);
+      if (!f->additive) f->ldj_stride += std::max(H / IMG_R * IMG_WAVES, img_net_hx3_ldj_slots(W, f->chp));
       f->depth = st.n_convs - 2;
       f->macs += (double)C * C * Hv * Wv;
     }
@@ -1339,6 +1368,7 @@ int gbnf_image_flow_create_mode(const gbnf_image_flow_desc* d, int32_t math_mode
       if (rc) break;
       if (C % 2) { rc = fail(GBNF_ERR_UNSUPPORTED, "Split2d on an odd channel count"); break; }
       f->split.push_back(pack_conv(P, *lv.split_prior));
+      f->ldj_stride += H / IMG_R * IMG_WAVES;
       f->macs += (double)(C / 2) * C * 9 * Hv * Wv;
       C /= 2;
     }
@@ -1364,6 +1394,8 @@ int gbnf_image_flow_create_mode(const gbnf_image_flow_desc* d, int32_t math_mode
     if (e == hipSuccess) e = allow_lds<EPI_COUPLE_AFFINE>();
     if (e == hipSuccess) e = allow_lds<EPI_COUPLE_ADD>();
     if (e == hipSuccess) e = allow_lds<EPI_SPLIT>();
+    if (e == hipSuccess) e = allow_lds<EPI_COUPLE_AFFINE_ORD>();
+    if (e == hipSuccess) e = allow_lds<EPI_SPLIT_ORD>();
     if (e == hipSuccess) e = allow_lds<EPI_COUPLE_AFFINE_INV>();
     if (e == hipSuccess) e = allow_lds<EPI_COUPLE_ADD_INV>();
     if (e == hipSuccess) e = allow_lds<EPI_SPLIT_INV>();
@@ -1437,19 +1469,56 @@ static int64_t image_repair_workgroups(int64_t n) { return n < IMG_REPAIR_WGS ? 
 static int64_t image_mark_floats(int64_t n) { return (n + 63) / 64 * 64; }
 
 // floats of a plain forward call's workspace; a class-conditional handle's calls keep a compact z and a scratch ll behind them
-static int64_t image_plain_floats(const gbnf_image_flow* f, int64_t n) {
+// Deterministic mode: a row of log-det slots per image -- behind each repair workgroup's private workspace, and the batch's (n, row)
+// array at the end of the plain call's workspace.  det: the mode the size is asked for.
+static int64_t image_slot_floats(const gbnf_image_flow* f, bool det) { return det ? ((int64_t)f->ldj_stride + 63) / 64 * 64 : 0; }
+static int64_t image_private_floats(const gbnf_image_flow* f, bool det) { return image_state_floats(f, 1) + image_slot_floats(f, det); }
+static int64_t image_plain_floats(const gbnf_image_flow* f, int64_t n, bool det) {
   int64_t floats = image_state_floats(f, n);
-  if (f->math_mode == GBNF_MATH_F16X3) floats += 2 * image_mark_floats(n) + 64 + image_repair_workgroups(n) * image_state_floats(f, 1);
-  return floats;
+  if (f->math_mode == GBNF_MATH_F16X3) floats += 2 * image_mark_floats(n) + 64 + image_repair_workgroups(n) * image_private_floats(f, det);
+  return floats + n * image_slot_floats(f, det);
+}
+static int64_t image_plain_floats(const gbnf_image_flow* f, int64_t n) { return image_plain_floats(f, n, f->deterministic != 0); }
+// the batch's slot array inside a workspace of the handle's current mode (null with the mode off)
+static float* image_batch_slots(const gbnf_image_flow* f, float* ws, int64_t n) {
+  return f->deterministic ? ws + image_plain_floats(f, n) - n * image_slot_floats(f, true) : nullptr;
 }
 static int64_t image_plain_bytes(const gbnf_image_flow* f, int64_t n) { return image_plain_floats(f, n) * 4 + 256; }
 static int64_t image_ycond_z_floats(const gbnf_image_flow* f, int64_t n) { return (n * f->zC * f->zH * f->zW + 63) / 64 * 64; }
+// bytes of a call's workspace with the deterministic mode on / off ([z | ll] of a class-conditional handle behind the plain call's)
+static int64_t image_workspace_bytes_mode(const gbnf_image_flow* f, int64_t n, bool det) {
+  int64_t bytes = image_plain_floats(f, n, det) * 4 + 256;
+  if (f->y_classes > 0) bytes += (image_ycond_z_floats(f, n) + image_mark_floats(n)) * 4 + 256;
+  return bytes;
+}
 
 int gbnf_image_flow_workspace_bytes(const gbnf_image_flow* f, int64_t n, int64_t* bytes) {
   if (!f || !bytes || n < 0) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_workspace_bytes: bad argument");
-  *bytes = image_plain_bytes(f, n);
-  if (f->y_classes > 0) *bytes += (image_ycond_z_floats(f, n) + image_mark_floats(n)) * 4 + 256;       // [z | ll] behind the plain call's
+  *bytes = image_workspace_bytes_mode(f, n, f->deterministic != 0);     // (the larger size while the mode is on: ask again after switching)
   return GBNF_OK;
+}
+
+int gbnf_image_flow_set_deterministic(gbnf_image_flow* f, int32_t on) {
+  if (!f) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_set_deterministic: flow is null");
+  f->deterministic = on ? 1 : 0;
+  return GBNF_OK;
+}
+
+int gbnf_image_flow_get_deterministic(const gbnf_image_flow* f, int32_t* on) {
+  if (!f || !on) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_get_deterministic: null argument");
+  *on = f->deterministic;
+  return GBNF_OK;
+}
+
+// the workspace check of a call: short -> GBNF_ERR_INVALID before anything is launched, naming the mode where it is what asks for more
+static int image_check_workspace(const char* fn, const gbnf_image_flow* f, int64_t n, int64_t workspace_bytes) {
+  int64_t need = 0;
+  gbnf_image_flow_workspace_bytes(f, n, &need);
+  if (workspace_bytes >= need) return GBNF_OK;
+  if (f->deterministic)
+    return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld (deterministic mode is on: ask gbnf_image_flow_workspace_bytes again after switching)",
+                fn, (long long)workspace_bytes, (long long)need);
+  return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld", fn, (long long)workspace_bytes, (long long)need);
 }
 
 // One pass of the launch sequence over n images.  force_f32: every convolution on the exact-f32 kernels (the repair pass and
@@ -1464,8 +1533,20 @@ struct ActNormStats {
   int channels;      // out: channels of that ActNorm2d (-1: index past the last one)
 };
 static int image_forward_impl(const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj, float* ll,
-                              float* workspace, hipStream_t s, bool force_f32, unsigned* mark, ActNormStats* stats, Recorder* rec) {
+                              float* workspace, hipStream_t s, bool force_f32, unsigned* mark, ActNormStats* stats, Recorder* rec, float* slots) {
   const int64_t chw = f->state_img;
+  // slots (deterministic mode; null = the atomic form): the (n, f->ldj_stride) log-det slot array of this pass.  Every launch that
+  // carries a log-det takes the next run of each image's row (slot_off: fixed by the launches in front of it, i.e. by the handle's
+  // geometry and the kernels its math mode runs) and STORES one partial per wave; one thread per image adds the row in slot order
+  // in front of img_final_kernel.
+  int slot_off = 0;
+  auto take_slots = [&](int count) -> float* {
+    if (slots == nullptr || slot_off + count > f->ldj_stride) return nullptr;
+    float* q = slots + slot_off;
+    slot_off += count;
+    return q;
+  };
+  const char* const slots_short = "gbnf_image_flow_forward: internal: the log-det slot row is too short for this launch sequence";
   int an_index = 0;                       // ActNorm2d counter (stats)
   if (stats != nullptr) stats->channels = -1;
   const int64_t hid = (int64_t)f->chp * (f->H / 2) * (f->W / 2);
@@ -1535,6 +1616,10 @@ static int image_forward_impl(const gbnf_image_flow* f, const float* x, const fl
           q.wp3 = reinterpret_cast<const unsigned*>(blob + net[NC - 1].x_off); q.bias3 = blob + net[NC - 1].b_off;
           q.st = cur + (int64_t)c1 * H * W; q.st_img = img; q.ldj = ldj;
           q.hid = net[0].cout; q.chp = f->chp; q.cout = net[NC - 1].cout; q.H = H; q.Hv = Hv; q.Wv = Wv;
+          if (slots != nullptr && !f->additive) {
+            q.ldj = take_slots(img_net_hx3_ldj_slots(W, f->chp)); q.ldj_stride = f->ldj_stride;
+            if (q.ldj == nullptr) return fail(GBNF_ERR_INVALID, "%s", slots_short);
+          }
           q.sat = reinterpret_cast<unsigned long long*>(gbnf::saturation_counter());
           q.mark = mark; q.only = nullptr;
 #ifdef GBNF_IMG_STAMPS
@@ -1575,6 +1660,10 @@ static int image_forward_impl(const gbnf_image_flow* f, const float* x, const fl
         m2.h2 = reinterpret_cast<const unsigned*>(H1); m2.wp = reinterpret_cast<const unsigned*>(blob + net[2].x_off);
         m2.bias = blob + net[2].b_off; m2.st = cur + (int64_t)c1 * H * W; m2.st_img = img; m2.ldj = ldj;
         m2.chp = f->chp; m2.cout = net[2].cout; m2.H = H; m2.n_strips = n_strips;
+        if (slots != nullptr && !f->additive) {
+          m2.ldj = take_slots(n_strips * IMG_WAVES); m2.ldj_stride = f->ldj_stride;
+          if (m2.ldj == nullptr) return fail(GBNF_ERR_INVALID, "%s", slots_short);
+        }
         const size_t lds2 = std::max((size_t)(IMG_R + 2) * (W + 2) * pixb, (size_t)IMG_WAVES * (IMG_WAVES - 1) * PT * 64 * 16);
         const dim3 g2((unsigned)(n * n_strips));
         if (f->additive) {
@@ -1624,8 +1713,16 @@ static int image_forward_impl(const gbnf_image_flow* f, const float* x, const fl
       const PackedConv& c = net.back();
       p.in = hin; p.in_img = hin_img; p.wp = blob + c.w_off; p.bias = blob + c.b_off; p.out = nullptr;
       p.st = cur + (int64_t)c1 * H * W; p.st_img = img; p.cin = c.cin; p.cout = c.cout; p.ks = c.ks;
-      if (f->additive) launch_conv<EPI_COUPLE_ADD>(p, (int)n, s, rec);
-      else launch_conv<EPI_COUPLE_AFFINE>(p, (int)n, s, rec);
+      if (f->additive) {
+        launch_conv<EPI_COUPLE_ADD>(p, (int)n, s, rec);
+      } else if (slots != nullptr) {
+        // (a log-det-carrying launch has at most 64 output channels -- 4 tiles: conv_o_split keeps it at one workgroup per strip)
+        p.ldj = take_slots(n_strips * IMG_WAVES); p.ldj_stride = f->ldj_stride;
+        if (p.ldj == nullptr) return fail(GBNF_ERR_INVALID, "%s", slots_short);
+        launch_conv<EPI_COUPLE_AFFINE_ORD>(p, (int)n, s, rec);
+      } else {
+        launch_conv<EPI_COUPLE_AFFINE>(p, (int)n, s, rec);
+      }
     }
     if (l < f->L - 1) {
       ConvLaunch p{};
@@ -1633,7 +1730,13 @@ static int image_forward_impl(const gbnf_image_flow* f, const float* x, const fl
       p.H = H; p.W = W; p.Hv = Hv; p.Wv = Wv; p.n_strips = n_strips; p.ldj = ldj;
       p.in = cur; p.in_img = img; p.wp = blob + c.w_off; p.bias = blob + c.b_off;
       p.st = cur + (int64_t)c1 * H * W; p.st_img = img; p.cin = c.cin; p.cout = c.cout; p.ks = c.ks;
-      launch_conv<EPI_SPLIT>(p, (int)n, s, rec);
+      if (slots != nullptr) {
+        p.ldj = take_slots(n_strips * IMG_WAVES); p.ldj_stride = f->ldj_stride;
+        if (p.ldj == nullptr) return fail(GBNF_ERR_INVALID, "%s", slots_short);
+        launch_conv<EPI_SPLIT_ORD>(p, (int)n, s, rec);
+      } else {
+        launch_conv<EPI_SPLIT>(p, (int)n, s, rec);
+      }
       const int Hn = H / 2 < 8 ? 8 : H / 2, Wn = W / 2 < 8 ? 8 : W / 2;      // storage of the next level (at least 8 wide)
       if (rec != nullptr) {
         RepairOp& op = rec->add(ROP_SQUEEZE);
@@ -1650,8 +1753,12 @@ static int image_forward_impl(const gbnf_image_flow* f, const float* x, const fl
     RepairOp& op = rec->add(ROP_FINAL);
     op.a = cur - workspace; op.c = ldj - workspace; op.prior = blob + f->prior_off;
     op.i[0] = C; op.i[1] = H; op.i[2] = W; op.i[3] = Hv; op.i[4] = Wv;
+    if (slots != nullptr) { op.b = slots - workspace; op.i[5] = slot_off; }
     return GBNF_OK;
   }
+  if (slots != nullptr && slot_off > 0)
+    hipLaunchKernelGGL(img_ldj_chain_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, (const float*)slots, f->ldj_stride,
+                       slot_off, ldj, n);
   hipLaunchKernelGGL(img_final_kernel, dim3((unsigned)n), dim3(256), 0, s, (const float*)cur, (int64_t)C * H * W,
                      blob + f->prior_off, (const float*)ldj, ll, z, C, H, W, Hv, Wv);
   const hipError_t e = hipGetLastError();
@@ -1674,6 +1781,7 @@ struct RepairSpace {
   unsigned* count;      // [0] marked images, [1] check entries
   float* wsr;           // image_repair_workgroups(n) private workspaces of image_state_floats(f, 1) floats
 };
+// (the private workspaces are image_private_floats(f, mode) apart: in deterministic mode each has its slot row behind it)
 static RepairSpace repair_space(const gbnf_image_flow* f, float* ws, int64_t n) {
   RepairSpace r;
   float* q = ws + image_state_floats(f, n);
@@ -1685,10 +1793,11 @@ static RepairSpace repair_space(const gbnf_image_flow* f, float* ws, int64_t n) 
 }
 
 static void launch_repair(const gbnf_image_flow* f, bool inverse, RepairArgs a, int64_t n, hipStream_t s) {
-  a.ops = f->ops_dev + (inverse ? f->n_ops_fwd : 0);
-  a.n_ops = inverse ? f->n_ops_inv : f->n_ops_fwd;
+  const bool det = !inverse && f->deterministic;          // the forward programme with the ordered log-det epilogues
+  a.ops = f->ops_dev + (inverse ? f->n_ops_fwd : (det ? f->n_ops_fwd + f->n_ops_inv : 0));
+  a.n_ops = inverse ? f->n_ops_inv : (det ? f->n_ops_det : f->n_ops_fwd);
   a.n = n;
-  a.ws_stride = image_state_floats(f, 1);
+  a.ws_stride = image_private_floats(f, f->deterministic != 0);
   a.force_all = f->dev_state + 1;
   a.host_words = f->host_words;
   const dim3 grid((unsigned)image_repair_workgroups(n)), blk(64 * IMG_WAVES);
@@ -1707,9 +1816,7 @@ int gbnf_image_flow_forward(const gbnf_image_flow* f, const float* x, const floa
   if (n < 0) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: n < 0");
   if (n == 0) return GBNF_OK;
   if (!x || !ldj || !workspace) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: x / ldj / workspace is null");
-  int64_t need = 0;
-  gbnf_image_flow_workspace_bytes(f, n, &need);
-  if (workspace_bytes < need) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: workspace of %lld bytes < %lld", (long long)workspace_bytes, (long long)need);
+  if (const int rc = image_check_workspace("gbnf_image_flow_forward", f, n, workspace_bytes)) return rc;
   return image_forward_launch("gbnf_image_flow_forward", f, x, noise, n, z, ldj, ll, workspace, stream);
 }
 
@@ -1772,9 +1879,7 @@ int gbnf_image_flow_forward_y(const gbnf_image_flow* f, const float* x, const fl
   if (n == 0) return GBNF_OK;
   if (!x || !y || !ldj || !workspace) return fail(GBNF_ERR_INVALID, "%s: x / y / ldj / workspace is null", fn);
   if (y_logits && !f->y_head) return fail(GBNF_ERR_INVALID, "%s: y_logits asked of a handle without a class head", fn);
-  int64_t need = 0;
-  gbnf_image_flow_workspace_bytes(f, n, &need);
-  if (workspace_bytes < need) return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld", fn, (long long)workspace_bytes, (long long)need);
+  if (const int rc = image_check_workspace(fn, f, n, workspace_bytes)) return rc;
   // The plain forward with the handle's y-free prior (the range marks, the same-call repair and the on-data check act on its ll as on
   // any call's), kept in scratch; then ONE launch, behind the repair in stream order, gives ll under the image's own prior and the logits.
   float* zs = reinterpret_cast<float*>((char*)workspace + image_plain_bytes(f, n));
@@ -1809,12 +1914,14 @@ static int image_forward_launch(const char* fn, const gbnf_image_flow* f, const 
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   // exact f32: the handle's mode, or a split-f16 handle whose on-data check has failed (pinned word, no synchronisation)
-  if (f->math_mode != GBNF_MATH_F16X3 || f->on_data_demoted()) return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, true, nullptr);
-  if (image_repair_mode() == 0) return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, nullptr);
+  float* slots = image_batch_slots(f, ws, n);              // deterministic mode: the batch's log-det slot array (else null)
+  if (f->math_mode != GBNF_MATH_F16X3 || f->on_data_demoted())
+    return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, true, nullptr, nullptr, nullptr, slots);
+  if (image_repair_mode() == 0) return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, nullptr, nullptr, nullptr, slots);
   // ---- split-f16 pass with range marks; the on-data check (first launch, every check_every-th); the marked images on exact f32
   const RepairSpace r = repair_space(f, ws, n);
   if (hipMemsetAsync(r.mark, 0, (size_t)n * 4, s) != hipSuccess) return fail(GBNF_ERR_HIP, "%s: memset failed", fn);
-  const int rc = image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, r.mark);
+  const int rc = image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, r.mark, nullptr, nullptr, slots);
   if (rc) return rc;
   int32_t every = 256, tol_e9 = 2500;
   (void)gbnf_tuning_get("check_every", &every);
@@ -1839,8 +1946,8 @@ int gbnf_image_flow_actnorm_stats(const gbnf_image_flow* f, const float* x, cons
                                   float* mean_dev, float* var_dev, int32_t* channels, void* workspace, int64_t workspace_bytes, void* stream) {
   if (!f || !x || !mean_dev || !var_dev || !workspace) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_actnorm_stats: null argument");
   if (n < 1 || index < 0) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_actnorm_stats: n = %lld, index = %d", (long long)n, index);
-  int64_t need = 0;
-  gbnf_image_flow_workspace_bytes(f, n, &need);
+  // (this pass reads nobody's log-det: it keeps the atomic form in either mode and stays inside a workspace of the mode-off size)
+  const int64_t need = image_workspace_bytes_mode(f, n, false);
   if (workspace_bytes < need) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_actnorm_stats: workspace of %lld bytes < %lld", (long long)workspace_bytes, (long long)need);
   float* ws = (float*)workspace;
   float* ldj = ws + image_state_floats(f, n);               // (scratch: the pass's own log-det accumulator)
@@ -2040,14 +2147,18 @@ static int image_inverse_impl(const gbnf_image_flow* f, const float* z, const fl
 static int image_record_repair_ops(gbnf_image_flow* f) {
   float* base = reinterpret_cast<float*>(IMG_REC_BASE);
   float* ldj_slot = base + image_state_floats(f, 1) - 64;       // (the spare floats behind the state buffers)
-  Recorder fw, bw;
+  Recorder fw, bw, fd;
   int rc = image_forward_impl(f, nullptr, nullptr, 1, nullptr, ldj_slot, nullptr, base, nullptr, true, nullptr, nullptr, &fw);
   if (!rc) rc = image_inverse_impl(f, nullptr, nullptr, 1.0f, 1, nullptr, base, nullptr, false, nullptr, &bw);
+  // the deterministic mode's forward: the same sequence on the ordered epilogues, its slot row behind the state buffers
+  if (!rc) rc = image_forward_impl(f, nullptr, nullptr, 1, nullptr, ldj_slot, nullptr, base, nullptr, true, nullptr, nullptr, &fd,
+                                   base + image_state_floats(f, 1));
   if (rc) return rc;
-  f->n_ops_fwd = (int)fw.ops.size(); f->n_ops_inv = (int)bw.ops.size();
-  f->repair_lds_fwd = fw.lds; f->repair_lds_inv = bw.lds;
+  f->n_ops_fwd = (int)fw.ops.size(); f->n_ops_inv = (int)bw.ops.size(); f->n_ops_det = (int)fd.ops.size();
+  f->repair_lds_fwd = std::max(fw.lds, fd.lds); f->repair_lds_inv = bw.lds;
   std::vector<RepairOp> all(fw.ops);
   all.insert(all.end(), bw.ops.begin(), bw.ops.end());
+  all.insert(all.end(), fd.ops.begin(), fd.ops.end());
   hipError_t e = hipMalloc((void**)&f->ops_dev, all.size() * sizeof(RepairOp));
   if (e == hipSuccess) e = hipMemcpy(f->ops_dev, all.data(), all.size() * sizeof(RepairOp), hipMemcpyHostToDevice);
   // (the kernel also has a little static LDS -- the reduction buffers of its elementwise ops: 160 KB of dynamic LDS would not fit)
@@ -2066,9 +2177,7 @@ int gbnf_image_flow_inverse(const gbnf_image_flow* f, const float* z, const floa
   if (n == 0) return GBNF_OK;
   if (!z || !x || !workspace) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_inverse: z / x / workspace is null");
   if (f->L > 1 && !eps) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_inverse: %d Split2d level(s) need eps", f->L - 1);
-  int64_t need = 0;
-  gbnf_image_flow_workspace_bytes(f, n, &need);
-  if (workspace_bytes < need) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_inverse: workspace of %lld bytes < %lld", (long long)workspace_bytes, (long long)need);
+  if (const int rc = image_check_workspace("gbnf_image_flow_inverse", f, n, workspace_bytes)) return rc;
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   // split-f16 coupling nets (the fused kernel, as the forward) unless the handle runs on exact f32 (its mode, or a failed on-data

@@ -335,6 +335,8 @@ struct LastLaunch {
   int64_t st_img;
   float* ldj;
   int chp, cout, H, n_strips;
+  int ldj_stride;           // deterministic mode (0 = the atomic form): ldj is this launch's first slot of image 0 in an (n, ldj_stride)
+                            //   array -- wave w of strip s STORES its partial to slot s * IMG_WAVES + w (zero if it ran no epilogue)
 };
 
 // EPI: EPI_COUPLE_AFFINE or EPI_COUPLE_ADD
@@ -481,7 +483,11 @@ __global__ void __launch_bounds__(64 * IMG_WAVES) img_last_hx3_kernel(const Last
   if constexpr (EPI == EPI_COUPLE_AFFINE) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) ld += __shfl_xor(ld, m);
-    if (lane == 0) atomicAdd(p.ldj + n, ld);
+    if (p.ldj_stride > 0) {                                   // (wave-uniform)
+      if (lane == 0) p.ldj[(int64_t)n * p.ldj_stride + strip * IMG_WAVES + wave] = ld;
+    } else if (lane == 0) {
+      atomicAdd(p.ldj + n, ld);
+    }
   }
 }
 

@@ -38,6 +38,9 @@ struct NetLaunch {
   unsigned long long* sat;  // per-device counter of workgroups that met an operand beyond the fp16 range, or null
   unsigned* mark;           // (n,) per-image marks (non-zero: re-evaluate this image on the exact-f32 path), or null
   const unsigned* only;     // repair launches: (n,) run only images whose entry is non-zero; null = all
+  int ldj_stride;           // the evaluation handle's deterministic mode (0 = the atomic form): ldj is this launch's first slot of image
+                            //   0 in an (n, ldj_stride) array of log-det slots -- wave w of workgroup s of image n STORES its partial
+                            //   to slot s * 8 + w (zero if it ran no epilogue) instead of adding it into ldj[n]
   unsigned long long* dbg;  // diagnostic builds (-DGBNF_IMG_STAMPS) only: [workgroup][wave][8] phase cycle sums
 };
 
@@ -47,6 +50,8 @@ size_t img_net_hx3_lds(int W, int chp, int cin, int pre_kc, int cout);
 // One launch for n images (W = H = 16 | 8): grid n * (W == 16 ? 2 : 1) workgroups of 512 threads (hidden widths above 256: n * 4
 // workgroups on 16-wide maps).
 hipError_t img_net_hx3_launch(const NetLaunch& q, int W, bool additive, int64_t n, hipStream_t s);
+// log-det slots per image of such a launch (NetLaunch::ldj_stride): workgroups per image x 8 waves
+int img_net_hx3_ldj_slots(int W, int chp);
 
 // One launch of img_conv_kernel (gbnf_image.hip): an implicit-GEMM convolution of n images, strip by strip.
 struct ConvLaunch {
@@ -60,6 +65,9 @@ struct ConvLaunch {
   int64_t st_img;
   float* ldj;             // (n,) accumulated with atomics (EPI_COUPLE_AFFINE / EPI_SPLIT); EPI_*_ORD: (n, slots) partials, slot
                           // (strip * o_split + osp) * IMG_WAVES + wave of image n is STORED by that wave (zero if it ran no epilogue)
+  int ldj_stride;         // EPI_*_ORD: floats between the slot rows of two images; 0 = the launch's own slot count (the trainer's
+                          // per-launch arrays).  The evaluation handle's deterministic mode keeps ONE (n, stride) array for the whole
+                          // chain: ldj = this launch's first slot of image 0
   int cin, cout, H, W, ks, n_strips;
   int Hv, Wv;             // the map proper: rows < Hv, columns < Wv of the H x W storage (a 14 x 14 map lives in 16 x 16 storage;
                           // everything outside is ZERO in every tensor in HBM -- the 'same' padding of the map -- and stays so)

@@ -856,7 +856,12 @@ __global__ void __launch_bounds__(512) img_net_hx3_kernel(const NetLaunch p) {
   if constexpr (EPI == EPI_COUPLE_AFFINE) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) ld += __shfl_xor(ld, m);
-    if (lane == 0 && wave < NPO && !p.inverse) atomicAdd(p.ldj + n, ld);
+    // (wave-uniform: the deterministic mode's slot store, behind the last accumulator drain like the ordered epilogues of img_conv_body)
+    if (p.ldj_stride > 0) {
+      if (lane == 0) p.ldj[(int64_t)n * p.ldj_stride + strip * WV + wave] = ld;
+    } else if (lane == 0 && wave < NPO && !p.inverse) {
+      atomicAdd(p.ldj + n, ld);
+    }
   }
   IMG_STAMP(6);
 #ifdef GBNF_IMG_STAMPS
@@ -900,6 +905,11 @@ size_t img_net_hx3_lds(int W, int chp, int cin, int pre_kc, int cout) {
   if (cout > 48 || (W == 16 && cout > 32)) return 0;
   if (pre_kc > 7 || (pre_kc > 5 && (W != 8 || chp > 256))) return 0;      // 6 / 7 chunks: the 8-wide instantiations of one half only
   return img_net_hx3_layout(W, chp, cin, pre_kc, nullptr);
+}
+
+int img_net_hx3_ldj_slots(int W, int chp) {
+  const int RO = (W == 16 && img_net_hx3_halves(chp) == 2) ? 4 : 8;
+  return (W == 16 ? 16 / RO : 1) * 8;
 }
 
 template <int W, int EPI, int OT3, int KH>

@@ -394,9 +394,14 @@ class BoostedImageFlow(nn.Module):
         # GBNF_IMAGE_DETERMINISTIC) asks for the image trainer's own ordered path (gbnf_image_trainer_set_deterministic) and is
         # applied to every trainer native_trainer() hands out; with it set the refusal does not fire.  (One flag would do once
         # the refusal is no longer expected of `deterministic` alone.)
-        from .boosted_flow import deterministic_from, image_deterministic_from
+        # A third, `image_eval_deterministic` (args.image_eval_deterministic / env GBNF_IMAGE_EVAL_DETERMINISTIC), asks for the
+        # EVALUATION handles' ordered log-det sums (gbnf_image_flow_set_deterministic) and is applied to every handle native_flow()
+        # hands out: component_forward (eval), component_log_prob, log_prob, forward(y_onehot=...), update_rho, _rho_gradients and
+        # the fixed-mixture term of training_step(fixed=...) then repeat bit for bit.  It reads neither of the other two.
+        from .boosted_flow import deterministic_from, image_deterministic_from, image_eval_deterministic_from
         self.deterministic = deterministic_from(args)
         self.image_deterministic = image_deterministic_from(args)
+        self.image_eval_deterministic = image_eval_deterministic_from(args)
         self.num_flows, self.z_size = args.num_flows, args.z_size
         self.density_evaluation = args.density_evaluation
         self.all_trained, self.component_type = False, args.component_type
@@ -462,7 +467,12 @@ class BoostedImageFlow(nn.Module):
         cached = self._handles.get(c)
         if cached is None or cached[0] != key:
             self._handles[c] = (key, native.NativeImageFlow(image_spec_from_glow_module(flow)))
-        return self._handles[c][1]
+        handle = self._handles[c][1]
+        want = bool(getattr(self, "image_eval_deterministic", False))
+        if getattr(handle, "_eval_deterministic", False) != want:      # (also a cached handle after the module's flag changed)
+            handle.deterministic = want
+            handle._eval_deterministic = want
+        return handle
 
     def _check(self, x):
         if not isinstance(x, torch.Tensor) or not x.is_cuda:
@@ -1027,7 +1037,9 @@ class BoostedImageFlow(nn.Module):
         gbnf_image_flow_numerics: the range marks, the repair launch and the periodic on-data check are part of every call's
         launch sequence and are counted on the device, so a replay repairs an out-of-range image exactly like a stream call; when
         an on-data check has demoted a handle, ``f`` re-captures so that the graph runs the exact-f32 kernels directly instead of
-        the split-f16 pass + full repair.)"""
+        the split-f16 pass + full repair.)  Deterministic evaluation: the graph keeps the mode its handles had when it was
+        captured (``image_eval_deterministic`` at that time); changing the flag afterwards changes stream calls only -- ``f`` does NOT
+        re-capture for it: build a new ``graphed_log_prob`` to have the graph in the other mode."""
         if self.flows[0].y_condition:
             raise NotImplementedError("graphed_log_prob of a class-conditional model is not built: the captured graph has no y input "
                                       "(use log_prob(x, y_onehot=...))")
@@ -1052,6 +1064,8 @@ class BoostedImageFlow(nn.Module):
                 out = self.log_prob(xs, n_used, ns)
             # the handles the graph's kernels read are HELD here: a re-pack cannot free them (and hand their address, hence their
             # id(), to a later handle) while this graph may still be replayed
+            # (... and their workspaces: a handle re-sizes its cached buffer when its deterministic mode changes)
+            state.update(workspaces=[h._ws for h in handles()])
             state.update(handles=handles(), graph=g, x=xs, noise=ns, out=out, demoted=[bool(h.numerics().demoted) for h in handles()])
 
         def f(x, noise):

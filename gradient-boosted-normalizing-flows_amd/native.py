@@ -57,6 +57,7 @@ ABI_SYMBOLS = (
     "gbnf_image_flow_set_ycond", "gbnf_image_flow_y_classes", "gbnf_image_flow_forward_y", "gbnf_image_flow_prior_y",
     "gbnf_image_trainer_bind_ycond", "gbnf_image_trainer_y_classes", "gbnf_image_trainer_nll_step_y",
     "gbnf_image_boosted_step_workspace_bytes_y", "gbnf_image_boosted_nll_step_y",
+    "gbnf_image_flow_set_deterministic", "gbnf_image_flow_get_deterministic",
 )
 
 
@@ -231,6 +232,8 @@ def lib():
     L.gbnf_group_graph_launch.argtypes = [vp, vp]
     L.gbnf_group_graph_destroy.argtypes = [vp]
     L.gbnf_image_flow_eps_floats.argtypes = [vp, C.POINTER(i64)]
+    L.gbnf_image_flow_set_deterministic.argtypes = [vp, i32]
+    L.gbnf_image_flow_get_deterministic.argtypes = [vp, C.POINTER(i32)]
     L.gbnf_image_trainer_create.argtypes = [C.POINTER(_ImageFlowDesc), C.POINTER(vp)]
     L.gbnf_image_trainer_destroy.argtypes = [vp]
     L.gbnf_image_trainer_trace_floats.argtypes = [vp, i64, C.POINTER(i64)]
@@ -513,6 +516,28 @@ class NativeImageFlow:
         self.has_class_head = False
         if spec.get("ycond") is not None:
             self.set_ycond(spec["ycond"])
+
+    @property
+    def deterministic(self):
+        """Deterministic mode of the handle (gbnf_image_flow_get_deterministic / gbnf_image_flow_set_deterministic): while it is on,
+        ``forward`` stores every log-det partial to a slot of its image and adds an image's slots in a fixed order -- z, ldj, ll (and
+        y_logits) of identical calls are bit-identical and an image's ldj / ll do not depend on the batch around it.  Off at creation.
+        A captured graph keeps the mode the handle had when it was captured.  The workspace is larger while the mode is on: every call
+        asks the library for the size of the handle's current mode and grows the cached buffer when it is short."""
+        on = C.c_int32()
+        _check(lib().gbnf_image_flow_get_deterministic(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    @deterministic.setter
+    def deterministic(self, on):
+        _check(lib().gbnf_image_flow_set_deterministic(self.handle, 1 if on else 0))
+        # (the workspace size depends on the mode: the next call finds the cached buffer short and re-sizes it)
+
+    def workspace_bytes(self, n):
+        """Bytes of a call's workspace at a batch of n images in the handle's current mode (gbnf_image_flow_workspace_bytes)."""
+        nb = C.c_int64()
+        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, int(n), C.byref(nb)))
+        return nb.value
 
     def set_ycond(self, yc):
         """gbnf_image_flow_set_ycond: make the handle class-conditional.  ``yc``: the spec's ``"ycond"`` entry -- ``cond_w`` (2Cz, Y),

@@ -649,6 +649,28 @@ int gbnf_image_flow_forward(const gbnf_image_flow* flow, const float* x, const f
                             float* ldj, float* ll, void* workspace, int64_t workspace_bytes, void* stream);
 /* The top prior per channel: mean (Cz,) then log-variance (Cz,) into a HOST buffer of 2 Cz floats. */
 int gbnf_image_flow_prior(const gbnf_image_flow* flow, float* mean_logvar_host);
+/* Deterministic mode of an evaluation handle, a property of the handle like gbnf_image_trainer_set_deterministic of the
+ * trainer (off at creation; with it off the launches, the results and the workspace sizes are what they always were: the
+ * coupling / Split2d epilogues add their per-wave log-det partials into ldj[n] with float atomics in no fixed order, and
+ * ldj / ll of identical calls may differ in the last bit; z never does).  While it is on, for a fixed handle and fixed
+ * inputs, z, ldj, ll (and y_logits) of gbnf_image_flow_forward / gbnf_image_flow_forward_y are bit-identical on every
+ * call, and ldj / ll of an image do not depend on n or on the image's place in the batch.  So are the outputs built on
+ * them: stats_dev[4..6] of gbnf_image_boosted_nll_step / _y and what gbnf_image_mixture_rho_step writes, when every handle
+ * of the call has the mode on.
+ * How: every wave of a log-det-carrying launch STORES its partial (zero if it ran no epilogue) to a slot of its image --
+ * slot = (launch in the chain, strip / workgroup of the image, wave), a function of the handle's geometry and of the
+ * kernels its math mode runs, never of n -- in ONE (n, S) array in the workspace, and one small launch in front of the
+ * last kernel adds an image's slots in slot order onto ldj[n].  The same-call repair of a split-f16 handle adds a repaired
+ * image's slots in the order an exact-f32 handle does: its ldj / ll equal those of a GBNF_MATH_F32 handle in this mode bit
+ * for bit.  z is untouched by the mode.  gbnf_image_flow_inverse writes no log-det and is unchanged.
+ * gbnf_image_flow_workspace_bytes (and gbnf_image_rho_step_workspace_bytes / gbnf_image_boosted_step_workspace_bytes over
+ * such handles) report the larger size while the mode is on: ask again after switching.  A call whose workspace_bytes is
+ * short answers GBNF_ERR_INVALID ("deterministic mode is on") before anything is launched.  gbnf_image_flow_actnorm_stats
+ * reads nobody's log-det, keeps the atomic form and needs the mode-off size only.
+ * A captured graph keeps the mode the handle had at capture time: switching the mode afterwards does not change that graph
+ * (re-capture to change it).  Nothing is promised across different handles' math modes, builds or devices. */
+int gbnf_image_flow_set_deterministic(gbnf_image_flow* flow, int32_t on);
+int gbnf_image_flow_get_deterministic(const gbnf_image_flow* flow, int32_t* on);
 /* ---- class-conditional components (Glow with y_condition, models/glow.py:36-39, 62-84, 105-106) --------------------------------
  * Y = y_classes, (Cz, Hz, Wz) the top latent, HW = Hz * Wz (the map proper), top_h = what gbnf_image_flow_prior returns.
  *   prior:  u = y W_c^T + b_c (n, 2Cz);  h_i = top_h + u_i exp(3 l_c);  z_mu[i,c] = h_i[c], z_var[i,c] = h_i[Cz + c], constant over the map;
@@ -798,8 +820,9 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* trainer, const float* trace,
  * gbnf_image_boosted_step_workspace_bytes report the larger sizes while the mode is on (ask again after switching it), and
  * a workspace sized before switching it on is refused with GBNF_ERR_INVALID ("workspace too small") before the first
  * launch, never overrun.
- * NOT covered: stats_dev[4..6] of gbnf_image_boosted_nll_step and everything gbnf_image_mixture_rho_step writes -- both
- * come from evaluation handles (gbnf_image_flow_*), whose kernels keep their atomics; the evaluation path has no such mode.
+ * stats_dev[4..6] of gbnf_image_boosted_nll_step and everything gbnf_image_mixture_rho_step writes come from evaluation
+ * handles (gbnf_image_flow_*), which have a deterministic mode of their own: gbnf_image_flow_set_deterministic (above).
+ * With it on for every handle of the call, those outputs repeat bit for bit too; with it off their last bit may differ.
  * Nothing is promised across different n, environments, builds or devices. */
 int gbnf_image_trainer_set_deterministic(gbnf_image_trainer* trainer, int32_t on);
 int gbnf_image_trainer_get_deterministic(const gbnf_image_trainer* trainer, int32_t* on);

@@ -41,6 +41,9 @@ def main():
     ap.add_argument("--no-streams", dest="streams", action="store_false",
                     help="all components on one stream (default: one HIP stream per component, their launch chains overlap, "
                          "as BoostedImageFlow.component_log_prob does)")
+    ap.add_argument("--eval-deterministic", dest="eval_deterministic", action="store_true",
+                    help="the handles' deterministic mode (gbnf_image_flow_set_deterministic: ordered log-det sums); without it "
+                         "nothing changes")
     a = ap.parse_args()
     from gbnf_amd import native, synth
     from oracle import gbnf_oracle as oracle
@@ -48,6 +51,9 @@ def main():
     size = tuple(a.input)
     specs = [synth.synth_image_glow_spec(size, a.hidden, a.K, a.L, seed=100 + c, depth=a.depth) for c in range(a.components)]
     flows = [native.NativeImageFlow(sp) for sp in specs]
+    if a.eval_deterministic:
+        for f in flows:
+            f.deterministic = True
     x_np, noise_np = synth.synth_image_batch(a.batch, size, seed=0)
     x, noise = torch.from_numpy(x_np).to(dev), torch.from_numpy(noise_np).to(dev)
     rho = torch.clamp(1.0 / torch.pow(2.0, torch.arange(a.components * 1.0)), min=0.05).to(dev)
@@ -145,7 +151,8 @@ def main():
         "stream_launches_value": stream_rate,
         "config": {"workload": f"{'cifar_glow' if size == (3, 32, 32) else 'image_glow'}: {size[0]}x{size[1]}x{size[2]}, C={a.components} components, K={a.K} steps x L={a.L} levels, h={a.hidden}, "
                                f"invconv, affine, learn_top, batch={a.batch}, synthetic images + weights",
-                   "launch": ("HIP graph replay" if a.graph else "stream launches") + (", one stream per component" if a.streams else "")},
+                   "launch": ("HIP graph replay" if a.graph else "stream launches") + (", one stream per component" if a.streams else ""),
+                   **({"eval_deterministic": True} if a.eval_deterministic else {})},
         # the coupling nets (99 % of the FLOPs) run on the split-f16 kernels img_mid_hx3 / img_last_hx3 unless GBNF_MATH=f32:
         # the peak is that of the pipe they run on; achieved = ALGORITHMIC f32 FLOPs (the f16 pipe executes 3x that)
         "roofline": {"kernel": "gbnf::img_conv_kernel (all convolutions, exact f32)" if exact else
