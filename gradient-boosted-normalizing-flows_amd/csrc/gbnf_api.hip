@@ -1483,6 +1483,67 @@ __global__ void __launch_bounds__(256) mixture_lse_kernel(const float* __restric
   out[idx] = G;
 }
 
+// Bayes' rule over the classes of a generative classifier, a wave per row (4 rows per workgroup), lanes strided over the classes:
+//   a_k = log_prior[k] + class_ll[i, k] (log_prior null: -log Y);  log_px[i] = LSE_k a_k;  log_post[i, k] = a_k - log_px[i];
+//   pred[i] = the first largest entry of the float32 log_post row (a NaN never wins; a row of NaNs gives 0).
+// f64 throughout, rounded once on the way out; the wave reductions are xor trees, so the order depends on Y alone.  torch.logsumexp's
+// semantics: an infinite maximum is replaced by 0 before the subtraction (a row of -inf gives -inf, not NaN).
+constexpr int POST_MAX_CLASSES = 256;
+__global__ void __launch_bounds__(256) class_posterior_kernel(const float* __restrict__ ll, const float* __restrict__ log_prior, int64_t n,
+                                                              int Y, float* __restrict__ log_px, float* __restrict__ log_post,
+                                                              int32_t* __restrict__ pred) {
+  const int lane = threadIdx.x & 63;
+  const int64_t i = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (i >= n) return;                                        // (a whole wave leaves: the shuffles below see full waves)
+  const double uniform = -log((double)Y);
+  double a[POST_MAX_CLASSES / 64];
+  double m = -INFINITY;
+  bool bad = false;
+#pragma unroll
+  for (int j = 0; j < POST_MAX_CLASSES / 64; ++j) {
+    const int k = lane + 64 * j;
+    a[j] = -INFINITY;
+    if (k < Y) {
+      a[j] = (log_prior ? (double)log_prior[k] : uniform) + (double)ll[i * Y + k];
+      if (a[j] != a[j]) bad = true;
+      else if (a[j] > m) m = a[j];
+    }
+  }
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const double o = __shfl_xor(m, s);
+    if (o > m) m = o;
+  }
+  if (isinf(m)) m = 0.0;
+  double se = 0.0;
+#pragma unroll
+  for (int j = 0; j < POST_MAX_CLASSES / 64; ++j)
+    if (lane + 64 * j < Y) se += exp(a[j] - m);
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) se += __shfl_xor(se, s);
+  double lpx = m + log(se);
+  if (__any(bad)) lpx = NAN;                                 // (a NaN term makes the row NaN, as in torch)
+  if (lane == 0) log_px[i] = (float)lpx;
+  float best = 0.0f;
+  int at = -1;
+#pragma unroll
+  for (int j = 0; j < POST_MAX_CLASSES / 64; ++j) {
+    const int k = lane + 64 * j;
+    if (k >= Y) continue;
+    const float v = (float)(a[j] - lpx);
+    if (log_post) log_post[i * Y + k] = v;
+    if (v == v && (at < 0 || v > best)) { best = v; at = k; }
+  }
+  if (pred == nullptr) return;
+#pragma unroll
+  for (int s = 1; s < 64; s <<= 1) {
+    const float ov = __shfl_xor(best, s);
+    const int oi = __shfl_xor(at, s);
+    if (oi >= 0 && (at < 0 || ov > best || (ov == best && oi < at))) { best = ov; at = oi; }
+  }
+  if (lane == 0) pred[i] = at < 0 ? 0 : at;
+}
+
 }  // namespace gbnf
 
 // ---- boosting sample weights (density_experiment.py:624-640): how much each training sample matters to the NEXT
@@ -1761,6 +1822,21 @@ int gbnf_mixture_lse(const float* ll, int64_t ll_row_stride, const float* rho_de
                      ll_row_stride, rho_dev, n_components, n, out);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "mixture_lse launch failed: %s", hipGetErrorString(e));
+  return GBNF_OK;
+}
+
+int gbnf_class_posterior(const float* class_ll, const float* log_prior, int64_t n, int32_t Y, float* log_px, float* log_post,
+                         int32_t* pred, void* stream) {
+  const char* fn = "gbnf_class_posterior";
+  if (Y < 1) return fail(GBNF_ERR_INVALID, "%s: Y = %d (must be >= 1)", fn, (int)Y);
+  if (Y > POST_MAX_CLASSES) return fail(GBNF_ERR_UNSUPPORTED, "%s: Y = %d > %d", fn, (int)Y, POST_MAX_CLASSES);
+  if (n < 0) return fail(GBNF_ERR_INVALID, "%s: n < 0", fn);
+  if (n == 0) return GBNF_OK;
+  if (!class_ll || !log_px) return fail(GBNF_ERR_INVALID, "%s: class_ll / log_px is null", fn);
+  hipLaunchKernelGGL(class_posterior_kernel, dim3((unsigned)((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, class_ll, log_prior, n,
+                     (int)Y, log_px, log_post, pred);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
   return GBNF_OK;
 }
 

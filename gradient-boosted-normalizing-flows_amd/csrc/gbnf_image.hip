@@ -1894,6 +1894,28 @@ int gbnf_image_flow_forward_y(const gbnf_image_flow* f, const float* x, const fl
   return GBNF_OK;
 }
 
+int gbnf_image_flow_forward_classes(const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj,
+                                    float* table, float* y_logits, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* fn = "gbnf_image_flow_forward_classes";
+  if (!f) return fail(GBNF_ERR_INVALID, "%s: flow is null", fn);
+  if (f->y_classes == 0) return fail(GBNF_ERR_INVALID, "%s: no conditioning set (gbnf_image_flow_set_ycond)", fn);
+  if (n < 0) return fail(GBNF_ERR_INVALID, "%s: n < 0", fn);
+  if (n == 0) return GBNF_OK;
+  if (!x || !ldj || !table || !workspace) return fail(GBNF_ERR_INVALID, "%s: x / ldj / table / workspace is null", fn);
+  if (y_logits && !f->y_head) return fail(GBNF_ERR_INVALID, "%s: y_logits asked of a handle without a class head", fn);
+  if (const int rc = image_check_workspace(fn, f, n, workspace_bytes)) return rc;
+  // gbnf_image_flow_forward_y without y: the flow x -> (z, ldj) does not depend on the class, so the plain forward (its protocol as on
+  // any call) runs ONCE, and one launch behind the repair in stream order evaluates the compact z under the prior of every class.
+  float* zs = reinterpret_cast<float*>((char*)workspace + image_plain_bytes(f, n));
+  float* ll0 = zs + image_ycond_z_floats(f, n);
+  float* zc = z ? z : zs;
+  if (const int rc = image_forward_launch(fn, f, x, noise, n, zc, ldj, ll0, workspace, stream)) return rc;
+  ycond_launch_table(image_ycond(f), zc, ldj, n, table, y_logits, (hipStream_t)stream);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
+  return GBNF_OK;
+}
+
 int gbnf_image_flow_prior_y(const gbnf_image_flow* f, const float* y, int64_t n, const float* e, float temperature, float* mean_logvar,
                             float* z_out, void* stream) {
   const char* fn = "gbnf_image_flow_prior_y";

@@ -3,6 +3,7 @@
 //
 //   gbnf_image_mixture_rho_step   one iteration of update_rho (models/boosted_flow.py:119-207, approximate branch): the components'
 //                                 forwards one after another on the caller's stream, then the rho update shared with the tabular call
+//   gbnf_image_mixture_rho_step_y the same over class-conditional components: every forward under its prior of each row's y
 //   g_partial_kernel              per-workgroup sums of -max(ll_G, g_floor) and the count of rows below the floor or non-finite
 //   g_finalize_kernel             G_nll = their mean (image_experiment.py:252-254), the count
 //   boosted_stat_kernel           stats[5] = stats[0] - stats[4]: the reference's nll = g_nll - G_nll (:256)
@@ -151,22 +152,30 @@ int gbnf_image_rho_step_workspace_bytes(const gbnf_image_flow* const* flows, int
   return image_rho_layout(flows, n_flows, n, &flow_bytes, bytes);
 }
 
-int gbnf_image_mixture_rho_step(const gbnf_image_flow* const* flows, int32_t component, const float* x, const float* noise, int64_t n,
-                                float* rho_dev, float step_size, float* ll_workspace, float* stats_dev, void* workspace,
-                                int64_t workspace_bytes, void* stream) {
-  const char* fn = "gbnf_image_mixture_rho_step";
-  if (!flows || !x || !rho_dev || !ll_workspace || !stats_dev || !workspace)
-    return fail(GBNF_ERR_INVALID, "%s: flows / x / rho_dev / ll_workspace / stats_dev / workspace is null", fn);
+// gbnf_image_mixture_rho_step (y null: every handle plain) and gbnf_image_mixture_rho_step_y (y (n, Y): every handle conditioned, one Y)
+static int image_rho_step(const char* fn, const gbnf_image_flow* const* flows, int32_t component, const float* x, const float* noise,
+                          const float* y, bool with_y, int64_t n, float* rho_dev, float step_size, float* ll_workspace, float* stats_dev,
+                          void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!flows || !x || !rho_dev || !ll_workspace || !stats_dev || !workspace || (with_y && !y))
+    return fail(GBNF_ERR_INVALID, "%s: flows / x / %srho_dev / ll_workspace / stats_dev / workspace is null", fn, with_y ? "y / " : "");
   if (component < 1) return fail(GBNF_ERR_INVALID, "%s: component = %d (must be >= 1: component 0 has no weight to learn)", fn, (int)component);
   if (n < 1) return fail(GBNF_ERR_INVALID, "%s: n = %lld (must be >= 1)", fn, (long long)n);
   const int n_flows = (int)component + 1;
   if (const int rc = check_image_flows(fn, flows, n_flows)) return rc;
+  int32_t Y0 = 0;
   for (int c = 0; c < n_flows; ++c) {    // refused HERE, before the first component's launches
     int32_t y_classes = 0;
     if (const int rc = gbnf_image_flow_y_classes(flows[c], &y_classes)) return rc;
-    if (y_classes != 0)
-      return fail(GBNF_ERR_INVALID, "%s: flows[%d] is class-conditional (%d classes) and needs y: the rho update has no such call", fn, c,
-                  (int)y_classes);
+    if (!with_y) {
+      if (y_classes != 0)
+        return fail(GBNF_ERR_INVALID, "%s: flows[%d] is class-conditional (%d classes) and needs y: the rho update has no such call", fn, c,
+                    (int)y_classes);
+      continue;
+    }
+    if (y_classes == 0) return fail(GBNF_ERR_INVALID, "%s: flows[%d] has no conditioning set (gbnf_image_flow_set_ycond)", fn, c);
+    if (c == 0) Y0 = y_classes;
+    else if (y_classes != Y0)
+      return fail(GBNF_ERR_INVALID, "%s: flows[%d] has %d classes, flows[0] %d: y has one width", fn, c, (int)y_classes, (int)Y0);
   }
   int64_t flow_bytes = 0, total = 0;
   if (const int rc = image_rho_layout(flows, n_flows, n, &flow_bytes, &total)) return rc;
@@ -174,10 +183,27 @@ int gbnf_image_mixture_rho_step(const gbnf_image_flow* const* flows, int32_t com
     return fail(GBNF_ERR_INVALID, "%s: workspace of %lld bytes < %lld (gbnf_image_rho_step_workspace_bytes)", fn, (long long)workspace_bytes,
                 (long long)total);
   float* ldj = (float*)((char*)workspace + flow_bytes);
-  for (int c = 0; c < n_flows; ++c)      // one chain after the other on the caller's stream: they share the workspace
-    if (const int rc = gbnf_image_flow_forward(flows[c], x, noise, n, nullptr, ldj, ll_workspace + (int64_t)c * n, workspace, flow_bytes, stream))
-      return rc;
+  for (int c = 0; c < n_flows; ++c) {    // one chain after the other on the caller's stream: they share the workspace
+    float* ll = ll_workspace + (int64_t)c * n;
+    const int rc = with_y ? gbnf_image_flow_forward_y(flows[c], x, noise, y, n, nullptr, ldj, ll, nullptr, workspace, flow_bytes, stream)
+                          : gbnf_image_flow_forward(flows[c], x, noise, n, nullptr, ldj, ll, workspace, flow_bytes, stream);
+    if (rc) return rc;
+  }
   return rho_update_launch(fn, ll_workspace, n, (int)component, rho_dev, step_size, stats_dev, (hipStream_t)stream);
+}
+
+int gbnf_image_mixture_rho_step(const gbnf_image_flow* const* flows, int32_t component, const float* x, const float* noise, int64_t n,
+                                float* rho_dev, float step_size, float* ll_workspace, float* stats_dev, void* workspace,
+                                int64_t workspace_bytes, void* stream) {
+  return image_rho_step("gbnf_image_mixture_rho_step", flows, component, x, noise, nullptr, false, n, rho_dev, step_size, ll_workspace,
+                        stats_dev, workspace, workspace_bytes, stream);
+}
+
+int gbnf_image_mixture_rho_step_y(const gbnf_image_flow* const* flows, int32_t component, const float* x, const float* noise, const float* y,
+                                  int64_t n, float* rho_dev, float step_size, float* ll_workspace, float* stats_dev, void* workspace,
+                                  int64_t workspace_bytes, void* stream) {
+  return image_rho_step("gbnf_image_mixture_rho_step_y", flows, component, x, noise, y, true, n, rho_dev, step_size, ll_workspace,
+                        stats_dev, workspace, workspace_bytes, stream);
 }
 
 int gbnf_image_boosted_step_workspace_bytes(const gbnf_image_flow* fixed, const gbnf_image_trainer* trainer, int64_t n, int64_t* bytes) {

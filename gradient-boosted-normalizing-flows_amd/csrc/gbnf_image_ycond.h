@@ -43,6 +43,9 @@ struct YCondRegions {
 
 // evaluation: ll[i] = log N(z_i; mu_i, lv_i) + ldj[i] and, with a class head and a non-null `logits`, y_logits (n, Y)
 void ycond_launch_eval(const YCond& c, const float* z, const float* ldj, const float* y, int64_t n, float* ll, float* logits, hipStream_t s);
+// evaluation under EVERY class: table[i, k] = log N(z_i; mu(e_k), lv(e_k)) + ldj[i] ((n, Y): what ycond_launch_eval writes to ll[i] for
+// y_i = the one-hot row of class k) and, with a class head and a non-null `logits`, y_logits (n, Y) -- one launch, no y
+void ycond_launch_table(const YCond& c, const float* z, const float* ldj, int64_t n, float* table, float* logits, hipStream_t s);
 // training: nll_i, CE_i, the autograd seed g_z / g_ldj of loss_scale mean(nll) + y_weight mean(CE), the per-image terms.
 // ld: [n_mix] doubles added to every image's log-det (the 1x1 matrices'), or null
 void ycond_launch_seed(const YCond& c, const float* z, const float* ldj, const double* ld, int n_mix, const float* y, int64_t n, float kn,

@@ -10,6 +10,8 @@
 //   img_ycond_reduce_kernel         one thread per parameter entry: the images' terms added in image order in f64 -> the gradient
 //                                   regions of the top prior, project_ycond and project_class, the loss sums, stats[4..7]
 //   img_ycond_prior_kernel          the per-image prior and the top latent of a class-conditional draw
+//   img_ycond_table_kernel          one workgroup per image: ll_i under EVERY class (n, Y) from per-channel mean and centred second
+//                                   moment of z -- the flow does not depend on y, so one forward serves all classes -- and the logits
 //
 // z is the compact top latent (n, Cz, HW of the map proper): nothing here sees the padding of the storage.  Everything is small and
 // latency-bound: no MFMA, no atomics; every sum runs in f64 in an order the sizes alone decide, so every value written here is
@@ -183,6 +185,68 @@ __global__ void __launch_bounds__(YC_THREADS) img_ycond_image_kernel(const YImag
   }
 }
 
+struct YTable {
+  YCond c;
+  const float* z;           // (n, Cz, HW)
+  const float* ldj;         // (n,)
+  float* table;             // (n, Y)
+  float* logits;            // (n, Y), or null
+};
+
+// One workgroup per image, every class at once.  The class moves the prior only, and the prior is constant over the map: with zbar_c the
+// channel's mean and M2_c = sum_p (z - zbar_c)^2,
+//   sum_p (z - mu)^2 = M2_c + HW (zbar_c - mu)^2        (two non-negative terms: nothing cancels, whatever mu is)
+// so z is read twice per image (a wave per channel, lanes over the pixels, as img_ycond_image_kernel) and a class then costs Cz terms
+// instead of Cz HW: thread k adds class k's channels in channel order.  The prior of class k is yc_prior's for y = e_k (its fma chain
+// over a one-hot row leaves W_c[:, k] + b_c exactly), zbar and the logits are img_ycond_image_kernel's to the bit.
+__global__ void __launch_bounds__(YC_THREADS) img_ycond_table_kernel(const YTable q) {
+  __shared__ double zb[YC_MAX_CZ], m2[YC_MAX_CZ];
+  __shared__ double top[2 * YC_MAX_CZ], cb[2 * YC_MAX_CZ], e3[2 * YC_MAX_CZ];
+  const YCond& c = q.c;
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int Y = c.Y, Cz = c.Cz, HW = c.HW;
+  const int64_t i = blockIdx.x;
+  if (tid < 2 * Cz) {
+    double t = 0.0;
+    if (c.top_h != nullptr) t = (double)c.top_h[tid];
+    else if (c.top_bias != nullptr) t = (double)c.top_bias[tid] * exp(3.0 * (double)c.top_logs[tid]);
+    top[tid] = t;
+    cb[tid] = (double)c.cond_b[tid];
+    e3[tid] = exp(3.0 * (double)c.cond_logs[tid]);
+  }
+  const float* zi = q.z + i * (int64_t)Cz * HW;
+  for (int ch = wave; ch < Cz; ch += YC_THREADS / 64) {
+    const float* zc = zi + (int64_t)ch * HW;
+    double s_z = 0.0;
+    for (int p = lane; p < HW; p += 64) s_z += (double)zc[p];
+    s_z = yc_wave_sum(s_z);
+    const double mean = s_z / (double)HW;
+    double s_dd = 0.0;
+    for (int p = lane; p < HW; p += 64) {
+      const double d = (double)zc[p] - mean;
+      s_dd = fma(d, d, s_dd);
+    }
+    s_dd = yc_wave_sum(s_dd);
+    if (lane == 0) { zb[ch] = mean; m2[ch] = s_dd; }
+  }
+  __syncthreads();
+  if (tid >= Y) return;
+  const double hw = (double)HW;
+  double s = 0.0;
+  for (int ch = 0; ch < Cz; ++ch) {
+    const double mu = top[ch] + ((double)c.cond_w[(int64_t)ch * Y + tid] + cb[ch]) * e3[ch];
+    const double lv = top[Cz + ch] + ((double)c.cond_w[(int64_t)(Cz + ch) * Y + tid] + cb[Cz + ch]) * e3[Cz + ch];
+    const double dm = zb[ch] - mu;
+    s += 0.5 * (hw * lv + (m2[ch] + hw * dm * dm) * exp(-lv));
+  }
+  q.table[i * Y + tid] = (float)((double)q.ldj[i] - s);
+  if (q.logits != nullptr && c.class_w != nullptr) {
+    double acc = 0.0;
+    for (int ch = 0; ch < Cz; ++ch) acc = fma(zb[ch], (double)c.class_w[(int64_t)tid * Cz + ch], acc);
+    q.logits[i * Y + tid] = (float)((acc + (double)c.class_b[tid]) * exp(3.0 * (double)c.class_logs[tid]));
+  }
+}
+
 struct YReduce {
   YCond c;
   const float* y;
@@ -318,6 +382,12 @@ void ycond_launch_eval(const YCond& c, const float* z, const float* ldj, const f
   YImage q{};
   q.c = c; q.z = z; q.ldj = ldj; q.y = y; q.ll = ll; q.logits = logits;
   hipLaunchKernelGGL((img_ycond_image_kernel<false>), dim3((unsigned)n), dim3(YC_THREADS), 0, s, q);
+}
+
+void ycond_launch_table(const YCond& c, const float* z, const float* ldj, int64_t n, float* table, float* logits, hipStream_t s) {
+  YTable q{};
+  q.c = c; q.z = z; q.ldj = ldj; q.table = table; q.logits = logits;
+  hipLaunchKernelGGL(img_ycond_table_kernel, dim3((unsigned)n), dim3(YC_THREADS), 0, s, q);
 }
 
 void ycond_launch_seed(const YCond& c, const float* z, const float* ldj, const double* ld, int n_mix, const float* y, int64_t n, float kn,

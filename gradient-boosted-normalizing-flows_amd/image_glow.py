@@ -1027,7 +1027,7 @@ class BoostedImageFlow(nn.Module):
             cur.wait_stream(streams[(x.device, c)])
         return torch.stack(lls, dim=1)
 
-    def graphed_log_prob(self, batch, n_used=None):
+    def graphed_log_prob(self, batch, n_used=None, labels=False):
         """-> ``f(x, noise) -> G (N,)``: ``log_prob`` for batches of ``batch`` images captured ONCE in a HIP graph and
         replayed (static input / output buffers, the components' streams forked and joined inside the graph).  A component is a
         chain of ~50 short launches, so an evaluation call is host-bound as plain stream launches: the replay is 12 % faster at
@@ -1039,10 +1039,15 @@ class BoostedImageFlow(nn.Module):
         an on-data check has demoted a handle, ``f`` re-captures so that the graph runs the exact-f32 kernels directly instead of
         the split-f16 pass + full repair.)  Deterministic evaluation: the graph keeps the mode its handles had when it was
         captured (``image_eval_deterministic`` at that time); changing the flag afterwards changes stream calls only -- ``f`` does NOT
-        re-capture for it: build a new ``graphed_log_prob`` to have the graph in the other mode."""
-        if self.flows[0].y_condition:
-            raise NotImplementedError("graphed_log_prob of a class-conditional model is not built: the captured graph has no y input "
-                                      "(use log_prob(x, y_onehot=...))")
+        re-capture for it: build a new ``graphed_log_prob`` to have the graph in the other mode.
+        ``labels=True`` (a class-conditional model): -> ``f(x, noise, y_onehot) -> G (N,)``, ``log_prob(x, noise=noise, y_onehot=y)``
+        with a static (batch, y_classes) label buffer; the graph holds the components' forward_y chains one after another on one
+        stream, as ``component_log_prob`` runs them for y (no parallel branches)."""
+        if labels:
+            self._conditioned("graphed_log_prob(labels=True)")
+        elif self.flows[0].y_condition:
+            raise NotImplementedError("graphed_log_prob of a class-conditional model needs the rows' labels as a graph input: pass "
+                                      "labels=True for f(x, noise, y_onehot) (or use log_prob(x, y_onehot=...))")
         n_used = self.num_components if n_used is None else int(n_used)
         dev = self.rho.device
         state = {}
@@ -1054,24 +1059,29 @@ class BoostedImageFlow(nn.Module):
             c_, h_, w_ = self.flows[0].input_size
             xs = torch.zeros((batch, c_, h_, w_), dtype=torch.float32, device=dev)
             ns = torch.zeros_like(xs)
+            ys = None
+            if labels:                                           # (any valid label does for the capture: class 0 for every row)
+                ys = torch.zeros((batch, int(self.flows[0].y_classes)), dtype=torch.float32, device=dev)
+                ys[:, 0] = 1.0
             side = torch.cuda.Stream(dev)
             side.wait_stream(torch.cuda.current_stream(dev))
             with torch.cuda.stream(side), torch.no_grad():
-                self.log_prob(xs, n_used, ns)                    # warm-up: stream creation, first-use attributes
+                self.log_prob(xs, n_used, ns, ys)                # warm-up: stream creation, first-use attributes
             torch.cuda.current_stream(dev).wait_stream(side)
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g), torch.no_grad():
-                out = self.log_prob(xs, n_used, ns)
+                out = self.log_prob(xs, n_used, ns, ys)
             # the handles the graph's kernels read are HELD here: a re-pack cannot free them (and hand their address, hence their
             # id(), to a later handle) while this graph may still be replayed
             # (... and their workspaces: a handle re-sizes its cached buffer when its deterministic mode changes)
             state.update(workspaces=[h._ws for h in handles()])
-            state.update(handles=handles(), graph=g, x=xs, noise=ns, out=out, demoted=[bool(h.numerics().demoted) for h in handles()])
+            state.update(handles=handles(), graph=g, x=xs, noise=ns, y=ys, out=out, demoted=[bool(h.numerics().demoted) for h in handles()])
 
-        def f(x, noise):
+        def f(x, noise, y_onehot=None):
             if tuple(x.shape) != (batch,) + tuple(self.flows[0].input_size) or tuple(noise.shape) != tuple(x.shape):
                 raise native.GbnfError(f"graphed_log_prob was captured for batches of shape {(batch,) + tuple(self.flows[0].input_size)}: "
                                        f"got x {tuple(x.shape)}, noise {tuple(noise.shape)}")
+            y = self._y(0, y_onehot, batch) if labels else None
             held = state.get("handles")
             now = handles()
             if (held is None or len(held) != len(now) or any(a is not b for a, b in zip(held, now))
@@ -1079,6 +1089,8 @@ class BoostedImageFlow(nn.Module):
                 capture()
             state["x"].copy_(x)
             state["noise"].copy_(noise)
+            if y is not None:
+                state["y"].copy_(y)
             state["graph"].replay()
             return state["out"]
 
@@ -1090,6 +1102,62 @@ class BoostedImageFlow(nn.Module):
         ll = self.component_log_prob(x, n_used, noise, y_onehot)
         with torch.cuda.device(x.device):
             return native.mixture_lse(ll.t().contiguous(), self.rho)
+
+    # ---- label-free evaluation of a class-conditional model: the class enters a component's top prior only (models/glow.py:62-84), so
+    # one pass of the flow serves every class (gbnf_image_flow_forward_classes)
+    def _conditioned(self, what):
+        if not self.flows[0].y_condition:
+            raise ValueError(f"{what} needs a class-conditional model (y_condition): this one has no classes")
+
+    def _class_tables(self, x, n_used, noise):
+        """(C_used, N, Y) contiguous: component c's log p_c(x | y = k), one ``forward_classes`` per component on the current stream."""
+        n_used = self.num_components if n_used is None else int(n_used)
+        self._check(x)
+        if noise is None:
+            noise = torch.rand_like(x.float())
+        x, noise = x.contiguous().float(), noise.contiguous().float()
+        with torch.cuda.device(x.device):
+            return torch.stack([self.native_flow(c).forward_classes(x, noise)[2] for c in range(n_used)], dim=0)
+
+    def component_class_log_prob(self, x, n_used=None, noise=None):
+        """(N, C_used, Y): ``component_log_prob(x, y_onehot=e_k)[:, c]`` for every class k at once -- no labels, one flow pass per
+        component instead of Y."""
+        self._conditioned("component_class_log_prob")
+        return self._class_tables(x, n_used, noise).permute(1, 0, 2)
+
+    def class_log_prob(self, x, n_used=None, noise=None):
+        """(N, Y): log p(x | y = k) of the boosted mixture -- ``log_prob(x, y_onehot=e_k)`` for every k -- by the recursion over rho on
+        the (C, N Y) view of the components' tables (column k is bit-equal to ``native.mixture_lse`` of that column alone)."""
+        self._conditioned("class_log_prob")
+        t = self._class_tables(x, n_used, noise)
+        with torch.cuda.device(x.device):
+            return native.mixture_lse(t.view(t.shape[0], -1), self.rho).view(t.shape[1], t.shape[2])
+
+    def _bayes(self, x, n_used, noise, class_prior, want_post, want_pred):
+        table = self.class_log_prob(x, n_used, noise)
+        log_prior = None
+        if class_prior is not None:
+            if tuple(class_prior.shape) != (table.shape[1],):
+                raise ValueError(f"class_prior must be ({table.shape[1]},) probabilities, got {tuple(class_prior.shape)}")
+            log_prior = torch.log(class_prior.detach().to(table.device).float()).contiguous()
+        with torch.cuda.device(x.device):
+            return native.class_posterior(table, log_prior, want_post=want_post, want_pred=want_pred)
+
+    def marginal_log_prob(self, x, n_used=None, noise=None, class_prior=None):
+        """(N,): log p(x) = log sum_k p(y = k) p(x | y = k), the density of unlabelled data.  ``class_prior``: (Y,) probabilities,
+        None = uniform."""
+        self._conditioned("marginal_log_prob")
+        return self._bayes(x, n_used, noise, class_prior, False, False)[0]
+
+    def class_posterior(self, x, n_used=None, noise=None, class_prior=None):
+        """(N, Y): log p(y = k | x) of the generative classifier (Bayes' rule on ``class_log_prob``; gbnf_class_posterior)."""
+        self._conditioned("class_posterior")
+        return self._bayes(x, n_used, noise, class_prior, True, False)[1]
+
+    def predict(self, x, n_used=None, noise=None, class_prior=None):
+        """(N,) int64: argmax_k p(x | y = k) p(y = k), the first of the largest."""
+        self._conditioned("predict")
+        return self._bayes(x, n_used, noise, class_prior, False, True)[2].long()
 
     # ---- the mixture weights (models/boosted_flow.py:119-207)
     @torch.no_grad()
@@ -1115,7 +1183,7 @@ class BoostedImageFlow(nn.Module):
         return new_ll, fixed_ll, full_ll
 
     @torch.no_grad()
-    def update_rho(self, data_loader, noise_generator=None):
+    def update_rho(self, data_loader, noise_generator=None, labels=False):
         """models/boosted_flow.py:141-207 (approximate branch) for image components.  The reference's log line references an undefined
         ``g_nll``; the update rule is reproduced, the broken log message is not.  For ``component`` >= 1 every
         iteration is ONE library call (gbnf_image_mixture_rho_step: the components' forwards, the recursion, the gradient and the
@@ -1123,14 +1191,18 @@ class BoostedImageFlow(nn.Module):
         iteration ``min_iters`` = 10, where the reference cannot stop, and the call's 4 statistics per iteration after that.  The
         loader yields ``(x, _)`` with x in [0, 1]; the dequantisation noise is one ``torch.rand(x.shape, generator=noise_generator)``
         draw on the device per batch, the same for every component.  For ``component == 0 and all_trained`` the reference's
-        gradient is identically 0 (new_ll = fixed_ll = 0): rho[0] is clamped to [0.01, 100], without a library call."""
+        gradient is identically 0 (new_ll = fixed_ll = 0): rho[0] is clamped to [0.01, 100], without a library call.
+        ``labels=True`` (a class-conditional model): the loader yields ``(x, y_onehot (N, y_classes))`` and every iteration is one
+        gbnf_image_mixture_rho_step_y call -- every component's ll under its prior of each row's label; everything else as above."""
+        if labels:
+            self._conditioned("update_rho(labels=True)")
         if self.component == 0 and not self.all_trained:
             return
         if getattr(self.args, "rho_iters", 0) == 0:
             return
-        if self.flows[0].y_condition:
-            raise NotImplementedError("update_rho of a class-conditional model is not built: gbnf_image_mixture_rho_step takes no y "
-                                      "(the reference's rho_iters default is 0: the update is skipped there)")
+        if self.flows[0].y_condition and not labels:
+            raise NotImplementedError("update_rho of a class-conditional model needs the rows' labels: gbnf_image_mixture_rho_step takes "
+                                      "no y (pass labels=True and a loader of (x, y_onehot))")
         self.eval()
         c = int(self.component)
         rho = self.rho
@@ -1144,16 +1216,17 @@ class BoostedImageFlow(nn.Module):
         data_iter = iter(data_loader)
         for batch_id in range(max_iters):
             try:
-                (x, _) = next(data_iter)
+                (x, y) = next(data_iter)
             except StopIteration:
                 data_iter = iter(data_loader)
-                (x, _) = next(data_iter)
+                (x, y) = next(data_iter)
             x = x.detach().to(rho.device).contiguous().float()
             self._check(x)
+            y = self._y(0, None if y is None else y.detach().to(rho.device), x.shape[0]) if labels else None
             noise = torch.rand(x.shape, generator=noise_generator, device=x.device)
             with torch.cuda.device(x.device):
                 stats = native.NativeImageFlow.rho_step([self.native_flow(k) for k in range(c + 1)], x, noise, c, rho,
-                                                        init_step / (0.05 * batch_id + 1))
+                                                        init_step / (0.05 * batch_id + 1), y=y)
             # the kernel wrote rho behind autograd's back: move its version counter as training_step does for parameters
             torch.autograd.graph.increment_version([rho])
             if batch_id > min_iters and (batch_id > max_iters or stats.tolist()[3] < tolerance):

@@ -58,6 +58,7 @@ ABI_SYMBOLS = (
     "gbnf_image_trainer_bind_ycond", "gbnf_image_trainer_y_classes", "gbnf_image_trainer_nll_step_y",
     "gbnf_image_boosted_step_workspace_bytes_y", "gbnf_image_boosted_nll_step_y",
     "gbnf_image_flow_set_deterministic", "gbnf_image_flow_get_deterministic",
+    "gbnf_image_flow_forward_classes", "gbnf_class_posterior", "gbnf_image_mixture_rho_step_y",
 )
 
 
@@ -270,6 +271,9 @@ def lib():
     L.gbnf_image_boosted_step_workspace_bytes_y.argtypes = [vp, vp, i64, C.POINTER(i64)]
     L.gbnf_image_boosted_nll_step_y.argtypes = [vp, C.c_float, vp, vp, vp, vp, i64, C.c_float, C.c_float, vp, vp, vp, C.POINTER(_OptHyper),
                                                 vp, vp, i64, vp]
+    L.gbnf_image_flow_forward_classes.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
+    L.gbnf_class_posterior.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
+    L.gbnf_image_mixture_rho_step_y.argtypes = [C.POINTER(vp), i32, vp, vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -703,6 +707,33 @@ class NativeImageFlow:
                                                ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         return z, ldj, ll, logits
 
+    def forward_classes(self, x, noise=None, want_z=False, want_logits=False):
+        """gbnf_image_flow_forward_classes: x (n,C,H,W) -> (z | None, ldj (n,), table (n, Y), y_logits (n, Y) | None) of a
+        class-conditional handle, without labels: ``table[i, k]`` is the ll ``forward(x, noise, y=e_k)`` gives row i, for every class k,
+        from ONE pass of the flow and one small launch (the class enters the top prior only).  Current stream."""
+        import torch
+        _require_device_f32(x, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
+            raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        n = x.shape[0]
+        z = torch.empty((n,) + self.z_shape, dtype=torch.float32, device=x.device) if want_z else None
+        ldj = torch.empty(n, dtype=torch.float32, device=x.device)
+        table = torch.empty((n, self.y_classes), dtype=torch.float32, device=x.device)
+        logits = torch.empty((n, self.y_classes), dtype=torch.float32, device=x.device) if want_logits else None
+        nb = C.c_int64()
+        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
+        if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
+            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        # (a handle without conditioning, logits without a class head: the library refuses, nothing launched)
+        _check(lib().gbnf_image_flow_forward_classes(self.handle, ptr(x), ptr(noise), n, ptr(z), ptr(ldj), ptr(table), ptr(logits),
+                                                     ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+        return z, ldj, table, logits
+
     def split_shapes(self):
         """(C_l/2, H_l, W_l) of the half each Split2d level drops (and re-draws on the way back), first level first."""
         c, h, w = self.input_size
@@ -751,13 +782,14 @@ class NativeImageFlow:
     _rho_ws = {}       # device -> workspace of rho_step (grown to the largest call so far)
 
     @staticmethod
-    def rho_step(flows, x, noise, component, rho, step_size):
+    def rho_step(flows, x, noise, component, rho, step_size, y=None):
         """One iteration of ``update_rho`` for image ``component`` >= 1 on the device (gbnf_image_mixture_rho_step): the forwards of
         ``flows[0 .. component]`` (``NativeImageFlow`` handles in component order, the same ``noise`` for all, None = none) one after
         another on the current stream, the reference's un-normalised recursion, grad = mean(fixed_ll - new_ll) and
         ``rho[component] = clamp(rho[component] - step_size * grad, 0.01, 100)`` written IN PLACE into ``rho`` (a contiguous float32
         device tensor; no version counter moves).  -> stats (4,) device tensor: grad, rho before, rho after, |after - before|.  The
-        (component + 1, n) log-likelihood table of the call stays in ``flows[component].rho_ll``."""
+        (component + 1, n) log-likelihood table of the call stays in ``flows[component].rho_ll``.  ``y`` (n, Y) for class-conditional
+        handles (gbnf_image_mixture_rho_step_y: every component's ll under its prior of each row's y; all handles conditioned, one Y)."""
         import torch
         component = int(component)
         flows = list(flows)[: max(component, 0) + 1]
@@ -775,6 +807,10 @@ class NativeImageFlow:
         if rho.dim() != 1 or rho.numel() <= component:
             raise GbnfError("rho has no entry for this component")
         n = x.shape[0]
+        if y is not None:                       # (plain handles among them, two class counts: the library refuses, nothing launched)
+            _require_device_f32(y, "y")
+            if y.dim() != 2 or y.shape[0] != n or y.shape[1] != max(int(f.y_classes) for f in flows):
+                raise GbnfError(f"y must be ({n}, y_classes), got {tuple(y.shape)}")
         handles = (C.c_void_p * len(flows))(*[f.handle.value for f in flows])
         nb = C.c_int64()
         _check(lib().gbnf_image_rho_step_workspace_bytes(handles, len(flows), n, C.byref(nb)))
@@ -784,6 +820,10 @@ class NativeImageFlow:
         table = flows[component].rho_ll = torch.empty((component + 1, n), dtype=torch.float32, device=x.device)
         stats = torch.zeros(4, dtype=torch.float32, device=x.device)
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        if y is not None:
+            _check(lib().gbnf_image_mixture_rho_step_y(handles, component, ptr(x), ptr(noise), ptr(y), n, ptr(rho), float(step_size),
+                                                       ptr(table), ptr(stats), ptr(ws), ws.numel() * 4, _stream_ptr()))
+            return stats
         _check(lib().gbnf_image_mixture_rho_step(handles, component, ptr(x), ptr(noise), n, ptr(rho), float(step_size), ptr(table),
                                                  ptr(stats), ptr(ws), ws.numel() * 4, _stream_ptr()))
         return stats
@@ -1997,6 +2037,30 @@ def mixture_lse(ll, rho, out=None):
     _check(lib().gbnf_mixture_lse(C.c_void_p(ll.data_ptr() if n else 0), n, C.c_void_p(rho.data_ptr()), c, n,
                                   C.c_void_p(out.data_ptr() if n else 0), _stream_ptr()))
     return out
+
+
+def class_posterior(class_ll, log_prior=None, want_post=True, want_pred=False):
+    """gbnf_class_posterior: class_ll (n, Y) device float32 (a table of ``NativeImageFlow.forward_classes``, or the mixture's),
+    ``log_prior`` (Y,) device log-probabilities or None for uniform -> (log_px (n,), log_post (n, Y) | None, pred (n,) int32 | None):
+    log_px = LSE_k(log_prior + class_ll), log_post = log_prior + class_ll - log_px, pred = the first largest entry of log_post."""
+    import torch
+    _require_device_f32(class_ll, "class_ll")
+    if class_ll.dim() != 2:
+        raise GbnfError(f"class_ll must be (n, Y), got {tuple(class_ll.shape)}")
+    class_ll = class_ll.contiguous()
+    n, Y = class_ll.shape
+    if log_prior is not None:
+        _require_device_f32(log_prior, "log_prior")
+        if tuple(log_prior.shape) != (Y,):
+            raise GbnfError(f"log_prior must be ({Y},), got {tuple(log_prior.shape)}")
+        log_prior = log_prior.contiguous()
+    log_px = torch.empty(n, dtype=torch.float32, device=class_ll.device)
+    post = torch.empty((n, Y), dtype=torch.float32, device=class_ll.device) if want_post else None
+    pred = torch.empty(n, dtype=torch.int32, device=class_ll.device) if want_pred else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+    if n:
+        _check(lib().gbnf_class_posterior(ptr(class_ll), ptr(log_prior), n, Y, ptr(log_px), ptr(post), ptr(pred), _stream_ptr()))
+    return log_px, post, pred
 
 
 def prepared_mixture_lse(ll, rho, out):

@@ -701,6 +701,33 @@ int gbnf_image_flow_forward_y(const gbnf_image_flow* flow, const float* x, const
                               void* stream);
 int gbnf_image_flow_prior_y(const gbnf_image_flow* flow, const float* y_dev, int64_t n, const float* e_or_null, float temperature,
                             float* mean_logvar_dev_or_null, float* z_out_or_null, void* stream);
+/* Label-free evaluation of a class-conditional handle: the log-density of every image under EVERY class from ONE pass of the flow.
+ * In the reference's Glow the class enters the top prior only (models/glow.py:62-84): x -> (z, ldj) does not depend on y.  So
+ *   table[i, k] = sum_{c,p} -0.5 (lv_c + (z[i,c,p] - mu_c)^2 e^-lv_c) + ldj[i],   h = (mu | lv) = top_h + (W_c[:, k] + b_c) exp(3 l_c)
+ * -- the ll gbnf_image_flow_forward_y writes for row i with y = the one-hot row of class k, within 1 float32 ulp (both are double
+ * sums rounded once) -- for all Y classes costs one flow pass and one small launch instead of Y calls of gbnf_image_flow_forward_y.
+ * x, noise, z, ldj, y_logits, workspace as gbnf_image_flow_forward_y (the logits do not depend on y either: they are that call's to
+ * the bit); table (n, Y) DEVICE.  The plain forward runs first with the handle's numerics protocol unchanged (range marks, same-call
+ * repair, on-data check); ONE launch behind the repair in stream order then reads the compact (repaired) z: per image and channel the
+ * mean and the centred second moment of z over the map, in double precision, then per class Cz terms -- sum (z - mu)^2 =
+ * M2 + HW (zbar - mu)^2, two non-negative terms.  Every sum runs in an order the sizes alone decide, no atomics: with the handle in
+ * deterministic mode (gbnf_image_flow_set_deterministic) table is bit-identical across calls and a row does not depend on n or on
+ * its position in the batch.  GBNF_ERR_INVALID (nothing launched): a handle without conditioning, a null x / ldj / table / workspace,
+ * a short workspace (gbnf_image_flow_workspace_bytes), y_logits on a handle without a class head.  n == 0: GBNF_OK.  No host read,
+ * no synchronisation, no allocation. */
+int gbnf_image_flow_forward_classes(const gbnf_image_flow* flow, const float* x, const float* noise, int64_t n, float* z_or_null,
+                                    float* ldj, float* table, float* y_logits_or_null, void* workspace, int64_t workspace_bytes,
+                                    void* stream);
+/* Bayes' rule on such a table (of one component, or of the boosted mixture: gbnf_mixture_lse over the (C, n Y) view of the components'
+ * tables): class_ll (n, Y) DEVICE, log_prior (Y,) DEVICE log-probabilities or NULL for the uniform prior -log Y;
+ *   log_px[i] = LSE_k(log_prior[k] + class_ll[i, k])  (n,)       the label-free log-density
+ *   log_post[i, k] = log_prior[k] + class_ll[i, k] - log_px[i]   (n, Y), or NULL
+ *   pred[i] = the first largest entry of row i of log_post as float32 (n,) int32, or NULL (a NaN never wins; a row of NaNs: 0)
+ * in double precision in a fixed order, rounded once, with torch.logsumexp's treatment of infinities (a row of -inf: log_px = -inf, and
+ * log_post = NaN as in torch).  1 <= Y <= 256 (GBNF_ERR_INVALID below, GBNF_ERR_UNSUPPORTED above); a null class_ll or log_px:
+ * GBNF_ERR_INVALID; n == 0: GBNF_OK.  One launch, no host read. */
+int gbnf_class_posterior(const float* class_ll, const float* log_prior_or_null, int64_t n, int32_t Y, float* log_px,
+                         float* log_post_or_null, int32_t* pred_or_null, void* stream);
 /* State of the image path's numerics protocol (the tabular one: gbnf_flow_numerics).  The coupling nets run on
  * split-f16 MFMA (GBNF_MATH_F16X3) when the create-time probe -- 4 synthetic images through both arithmetic paths --
  * agrees with the exact-f32 kernels to `tolerance` (worst_rel_err = what it measured), else the handle runs on exact f32
@@ -951,13 +978,22 @@ int gbnf_image_trainer_nll_step_y(gbnf_image_trainer* trainer, const float* x, c
  * workspace: caller-owned DEVICE scratch of gbnf_image_rho_step_workspace_bytes(flows, component + 1, n) bytes -- the largest
  * gbnf_image_flow_workspace_bytes of the handles and the call's ldj accumulator, each 256-byte aligned.  GBNF_ERR_INVALID (nothing
  * launched): a null flows / x / rho_dev / ll_workspace / stats_dev / workspace or a null entry of flows, component < 1, n < 1, handles
- * whose input shape (channels, height, width) differs, a class-conditional handle anywhere in flows (the update has no y call), a
+ * whose input shape (channels, height, width) differs, a class-conditional handle anywhere in flows (it needs y: gbnf_image_mixture_rho_step_y), a
  * short workspace.  The partial sums live in the per-device buffer of
  * gbnf_mixture_rho_step: two rho calls on one device must not run concurrently. */
 int gbnf_image_rho_step_workspace_bytes(const gbnf_image_flow* const* flows, int32_t n_flows, int64_t n, int64_t* bytes);
 int gbnf_image_mixture_rho_step(const gbnf_image_flow* const* flows, int32_t component, const float* x, const float* noise,
                                 int64_t n, float* rho_dev, float step_size, float* ll_workspace, float* stats_dev,
                                 void* workspace, int64_t workspace_bytes, void* stream);
+/* The same iteration for class-conditional components: gbnf_image_mixture_rho_step with y (n, Y) DEVICE, the rows' labels as
+ * gbnf_image_flow_forward_y takes them.  Row c of ll_workspace is component c's ll under its prior of each row's y (the code path of
+ * gbnf_image_flow_forward_y: the plain chain, the repair, one more launch); the recursion, the update and stats_dev[4] are the plain
+ * call's.  Every handle of flows[0 .. component] must be conditioned, all with the same Y: a plain handle among them, a second class
+ * count or a null y is GBNF_ERR_INVALID before the first launch, as is everything the plain call refuses.  The workspace is that of
+ * gbnf_image_rho_step_workspace_bytes: a conditioned handle's gbnf_image_flow_workspace_bytes already holds its compact z. */
+int gbnf_image_mixture_rho_step_y(const gbnf_image_flow* const* flows, int32_t component, const float* x, const float* noise,
+                                  const float* y_dev, int64_t n, float* rho_dev, float step_size, float* ll_workspace,
+                                  float* stats_dev, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Replaces: one iteration of image_experiment.py:398-419 for the component being trained, the fixed-mixture term of
  * compute_boosted_loss (:247-261) included -- the image counterpart of gbnf_boosted_nll_step -- in one call on `stream`, with no host
