@@ -241,6 +241,11 @@ def main(argv=None):
     objs.append(yc_o)
     if args.force or not newer(yc_o, [yc_src, yc_hdr]):
         jobs.append([HIPCC] + FLAGS + ["-c", yc_src, "-o", yc_o])
+    # the score of the image path (the adjoint of the dequantise + logit head, the seed, the responsibilities, the mixture's one call): gbnf_image_score.hip
+    sc_o, sc_src = os.path.join(OBJ, "gbnf_image_score.o"), os.path.join(HERE, "gbnf_image_score.hip")
+    objs.append(sc_o)
+    if args.force or not newer(sc_o, [sc_src, imgt_hdr, yc_hdr, hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", sc_src, "-o", sc_o])
     comm_o, comm_src = os.path.join(OBJ, "gbnf_comm.o"), os.path.join(HERE, "gbnf_comm.hip")
     objs.append(comm_o)
     if args.force or not newer(comm_o, [comm_src, hdr[2], hdr[3]]):

@@ -489,6 +489,25 @@ int image_step_compose(const gbnf_image_trainer* t, void* stream) {
   return GBNF_OK;
 }
 
+int image_score_top(const char* fn, const gbnf_image_trainer* t, ImageScoreTop* out) {
+  const ImageStepState* st = t->step;
+  if (!st || !st->ready) return fail(GBNF_ERR_INVALID, "%s: the last bind call of a trainer failed: bind again first", fn);
+  out->ld = ld_sums(st); out->n_mix = st->n_mix; out->top_bias = st->top_bias; out->top_logs = st->top_logs;
+  out->y_classes = st->y_classes;
+  for (int k = 0; k < 6; ++k) out->yc[k] = st->yc[k];
+  return GBNF_OK;
+}
+
+int image_score_logdets(const char* fn, const gbnf_image_trainer* t, void* stream) {
+  const ImageStepState* st = t->step;
+  if (st->n_mix == 0) return GBNF_OK;
+  if (mix_allow_lds() != hipSuccess) return fail(GBNF_ERR_HIP, "%s: the 1x1 kernels' LDS opt-in failed", fn);
+  MixLaunch mq{};
+  mq.steps = st->mix_dev; mq.n_mix = st->n_mix; mq.ld = ld_sums(st); mq.k = 1.0f;
+  hipLaunchKernelGGL((img_mix_logdet_kernel<0>), dim3((unsigned)st->n_mix), dim3(IOPT_THREADS), MIX_LDS_BYTES, (hipStream_t)stream, mq);
+  return GBNF_OK;
+}
+
 }  // namespace gbnf
 
 using namespace gbnf;

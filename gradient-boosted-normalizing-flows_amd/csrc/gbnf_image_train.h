@@ -1,6 +1,7 @@
 // gbnf_image_train.h -- the image trainer (gbnf_image_train.hip) as the one-call training step (gbnf_image_opt.hip) sees it; not part
 // of the C ABI.
 #pragma once
+#include <hip/hip_runtime.h>
 #include <cstdint>
 #include <vector>
 #include "../../include/gbnf.h"
@@ -31,6 +32,27 @@ void image_step_state_destroy(ImageStepState* s);
 // step 1 of gbnf_image_trainer_nll_step for gbnf_image_trainer_actnorm_init: with LU factors bound, the 1x1 matrices are composed
 // into their bound tensors on `stream` (the same launch); nothing bound: nothing launched
 int image_step_compose(const gbnf_image_trainer* t, void* stream);
+
+// What gbnf_image_mixture_score (gbnf_image_score.hip) needs of a trainer's bindings to form ll on the device as the one-call step
+// does: the 1x1 log-dets (hw log|det W| per bound matrix, doubles, written by image_score_logdets), the live top prior (null: zero
+// mean, unit variance) and the conditioning (y_classes 0: none; yc: cond weight, bias, logs, class weight, bias, logs)
+struct ImageScoreTop {
+  const double* ld;
+  int n_mix;
+  const float* top_bias;
+  const float* top_logs;
+  int y_classes;
+  const float* yc[6];
+};
+// GBNF_ERR_INVALID when the trainer's last bind call failed; launches nothing
+int image_score_top(const char* fn, const gbnf_image_trainer* t, ImageScoreTop* out);
+// step 1 of gbnf_image_trainer_nll_step: LU matrices composed into their bound tensors, every 1x1 log-det into `ld`
+int image_score_logdets(const char* fn, const gbnf_image_trainer* t, void* stream);
+
+// The adjoint of img_pre_body (gbnf_image.hip): gs (n, 4C, H/2, W/2) storage, the gradient of the squeezed logits, and g_ldj (n,) ->
+// g_x (n, C, Hi, Wi), stored or added; v is recomputed from x and noise as the forward does (gbnf_image_score.hip)
+void img_launch_pre_adjoint(const float* x, const float* noise, const float* gs, const float* g_ldj, float* g_x, int C, int H, int W, int Hi,
+                            int Wi, float bounds, int accumulate, int64_t n, hipStream_t s);
 
 }  // namespace gbnf
 

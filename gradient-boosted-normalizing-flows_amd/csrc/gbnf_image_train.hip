@@ -11,8 +11,9 @@
 //             an elementwise kernel turns the output gradient into the net's (the log-det term of g_ldj folded in), and every
 //             convolution gives a weight gradient (img_train_wgrad_kernel, below) and a data gradient (img_conv_kernel on the
 //             transposed tiles: the adjoint of a stride-1 'same' convolution is one; its Hv / Wv masking keeps the outside of the map
-//             zero as the forward does).
-//   unfold    ONE launch maps (dW', db') of the folded convolutions and (dW_eff, db_eff) of the mixes to the descriptor's arrays.
+//             zero as the forward does).  gbnf_image_trainer_backward_x carries the state gradient through the first step's mix as well
+//             and on to the image (img_pre_adjoint_kernel, gbnf_image_score.hip); without `grads` it skips every weight-gradient launch.
+//   unfold   ONE launch maps (dW', db') of the folded convolutions and (dW_eff, db_eff) of the mixes to the descriptor's arrays.
 //   init      gbnf_image_trainer_actnorm_init: the data-dependent ActNorm2d initialisation of every layer in ONE walk of the forward.
 //             At a layer to initialise: (a coupling-net layer: its convolution once on identity tiles, store epilogue) -> per-channel
 //             sums and centred squares over chunks of images in f64 (img_train_an_stats_kernel, grid chunks x channels) -> the finish
@@ -911,11 +912,12 @@ int gbnf_image_trainer_actnorm_init(gbnf_image_trainer* t, const float* x, const
 }
 
 // weight gradient of entry `c` and the data gradient of its input.  dst_store: the adjoint's result is stored there (stride dst_img);
-// dst_add: it is ADDED there (the z1 half of the state gradient); both null: no data gradient wanted.
+// dst_add: it is ADDED there (the z1 half of the state gradient); both null: no data gradient wanted.  scr null: no weight gradient
+// wanted (the data-gradient-only form of gbnf_image_trainer_backward_x).
 static void conv_backward(const gbnf_image_trainer* t, const gbnf_image_trainer::Level& lv, const TConv& c, const float* in, int64_t in_img,
                           const float* G, int64_t G_img, float* scr, float* part, float* dst_store, float* dst_add, int64_t dst_img, int64_t n,
                           hipStream_t s) {
-  launch_wgrad(c, in, in_img, G, G_img, scr, part, lv.H, lv.W, lv.Hv, n, s);
+  if (scr != nullptr) launch_wgrad(c, in, in_img, G, G_img, scr, part, lv.H, lv.W, lv.Hv, n, s);
   if (!dst_store && !dst_add) return;
   ConvLaunch p = conv_base(lv, nullptr);
   p.in = G; p.in_img = G_img; p.wp = t->blob_dev + c.bwd_off; p.bias = t->blob_dev + t->zero_off;
@@ -924,16 +926,14 @@ static void conv_backward(const gbnf_image_trainer* t, const gbnf_image_trainer:
   else { p.st = dst_add; p.st_img = dst_img; img_launch_conv(EPI_COUPLE_ADD, p, (int)n, s); }
 }
 
-int gbnf_image_trainer_backward(gbnf_image_trainer* t, const float* trace_c, int64_t n, const float* g_z, const float* g_ldj, float* grads,
-                                void* workspace, int64_t workspace_bytes, void* stream) {
-  if (!t || !trace_c || !grads) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_backward: null argument");
-  if (n <= 0) return n == 0 ? GBNF_OK : fail(GBNF_ERR_INVALID, "gbnf_image_trainer_backward: n < 0");
-  if (n > 65535) return fail(GBNF_ERR_UNSUPPORTED, "gbnf_image_trainer_backward: at most 65535 images per call");
-  const TrainSpace sp = train_space(t, (float*)workspace, n);
-  if (!workspace || workspace_bytes < sp.total * 4) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_backward: workspace too small");
-  hipStream_t s = (hipStream_t)stream;
+// gbnf_image_trainer_backward (g_x null, grads required) and gbnf_image_trainer_backward_x (g_x required: the state gradient also
+// goes through the first step's mix and the adjoint of img_pre_body; grads null: no weight-gradient launch, no scratch memset, no
+// unfold).  The caller has checked every argument.
+static int trainer_backward(const char* fn, gbnf_image_trainer* t, const float* trace_c, int64_t n, const float* g_z, const float* g_ldj,
+                            float* grads, const float* x, const float* noise, float* g_x, int accumulate, const TrainSpace& sp, hipStream_t s) {
   float* trace = const_cast<float*>(trace_c);                // (read only)
-  hipError_t e = hipMemsetAsync(sp.scr, 0, (size_t)t->scratch_floats * 4, s);
+  float* const scr = grads != nullptr ? sp.scr : nullptr;
+  hipError_t e = scr != nullptr ? hipMemsetAsync(scr, 0, (size_t)t->scratch_floats * 4, s) : hipSuccess;
   const float* gl = g_ldj;
   if (gl == nullptr) {
     if (e == hipSuccess) e = hipMemsetAsync(sp.gl0, 0, (size_t)n * 4, s);
@@ -946,7 +946,7 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* t, const float* trace_c, int
     if (g_z != nullptr) img_launch_embed(g_z, cur, lv.C, lv.H, lv.W, lv.Hv, lv.Wv, n, s);
     else if (e == hipSuccess) e = hipMemsetAsync(cur, 0, (size_t)lv.C * lv.H * lv.W * n * 4, s);
   }
-  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_image_trainer_backward: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
   for (int l = t->L - 1; l >= 0; --l) {
     const auto& lv = t->levels[l];
     const int HW = lv.H * lv.W, c1 = lv.C / 2, c2 = lv.C - c1;
@@ -965,7 +965,7 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* t, const float* trace_c, int
       const int64_t total = n * (int64_t)c1 * HW;              // (C even: the dropped half has c1 channels)
       hipLaunchKernelGGL(img_train_split_bwd_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, sp.HO, p.out_img,
                          (const float*)(O + (int64_t)c1 * HW), img, cur + (int64_t)c1 * HW, img, gl, c1, lv.H, lv.W, lv.Hv, lv.Wv, total);
-      conv_backward(t, lv, c, O, img, sp.HO, p.out_img, sp.scr, sp.wpart, nullptr, cur, img, n, s);
+      conv_backward(t, lv, c, O, img, sp.HO, p.out_img, scr, sp.wpart, nullptr, cur, img, n, s);
     }
     for (int k = lv.K - 1; k >= 0; --k) {
       const int first = t->step_first[l][k];
@@ -996,27 +996,57 @@ int gbnf_image_trainer_backward(gbnf_image_trainer* t, const float* trace_c, int
       for (int q = t->n_net - 1; q >= 0; --q) {
         const TConv& c = t->table[first + 1 + q];
         if (q == 0) {
-          conv_backward(t, lv, c, P, img, G, G_img, sp.scr, sp.wpart, nullptr, cur, img, n, s);
+          conv_backward(t, lv, c, P, img, G, G_img, scr, sp.wpart, nullptr, cur, img, n, s);
         } else {
           float* Gn = (G == sp.GA) ? sp.GB : sp.GA;
           const int64_t a_img = (int64_t)c.cin * HW;
-          conv_backward(t, lv, c, sp.A[q - 1], a_img, G, G_img, sp.scr, sp.wpart, Gn, nullptr, a_img, n, s);
+          conv_backward(t, lv, c, sp.A[q - 1], a_img, G, G_img, scr, sp.wpart, Gn, nullptr, a_img, n, s);
           const int64_t total4 = n * a_img / 4;
           hipLaunchKernelGGL(img_train_relu_mask_kernel, dim3((unsigned)((total4 + 255) / 256)), dim3(256), 0, s, Gn, (const float*)sp.A[q - 1], total4);
           G = Gn; G_img = a_img;
         }
       }
       // the mix: cur is the gradient of P_k now
-      const bool need_data = !(l == 0 && k == 0);                // (there is no gradient with respect to x)
-      conv_backward(t, lv, t->table[first], prev, img, cur, img, sp.scr, sp.wpart, need_data ? oth : nullptr, nullptr, img, n, s);
+      const bool need_data = !(l == 0 && k == 0) || g_x != nullptr;      // (the first step's input gradient: only on the way to g_x)
+      conv_backward(t, lv, t->table[first], prev, img, cur, img, scr, sp.wpart, need_data ? oth : nullptr, nullptr, img, n, s);
       if (need_data) std::swap(cur, oth);
     }
   }
-  hipLaunchKernelGGL(img_train_unfold_kernel, dim3(128, (unsigned)t->table.size()), dim3(256), 0, s, (const TConv*)t->table_dev, (const float*)sp.scr,
-                     g_ldj, n, grads);
+  if (grads != nullptr)
+    hipLaunchKernelGGL(img_train_unfold_kernel, dim3(128, (unsigned)t->table.size()), dim3(256), 0, s, (const TConv*)t->table_dev, (const float*)scr,
+                       g_ldj, n, grads);
+  // cur: the gradient of level 0's input, (n, 4C, H/2, W/2) storage -> the image proper
+  if (g_x != nullptr)
+    img_launch_pre_adjoint(x, noise, cur, gl, g_x, t->C, t->H, t->W, t->Hi, t->Wi, t->bounds, accumulate, n, s);
   e = hipGetLastError();
-  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_image_trainer_backward: %s", hipGetErrorString(e));
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s: %s", fn, hipGetErrorString(e));
   return GBNF_OK;
+}
+
+int gbnf_image_trainer_backward(gbnf_image_trainer* t, const float* trace_c, int64_t n, const float* g_z, const float* g_ldj, float* grads,
+                                void* workspace, int64_t workspace_bytes, void* stream) {
+  if (!t || !trace_c || !grads) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_backward: null argument");
+  if (n <= 0) return n == 0 ? GBNF_OK : fail(GBNF_ERR_INVALID, "gbnf_image_trainer_backward: n < 0");
+  if (n > 65535) return fail(GBNF_ERR_UNSUPPORTED, "gbnf_image_trainer_backward: at most 65535 images per call");
+  const TrainSpace sp = train_space(t, (float*)workspace, n);
+  if (!workspace || workspace_bytes < sp.total * 4) return fail(GBNF_ERR_INVALID, "gbnf_image_trainer_backward: workspace too small");
+  return trainer_backward("gbnf_image_trainer_backward", t, trace_c, n, g_z, g_ldj, grads, nullptr, nullptr, nullptr, 0, sp, (hipStream_t)stream);
+}
+
+int gbnf_image_trainer_backward_x(gbnf_image_trainer* t, const float* trace_c, const float* x, const float* noise, int64_t n, const float* g_z,
+                                  const float* g_ldj, float* grads, float* g_x, int32_t accumulate, void* workspace, int64_t workspace_bytes,
+                                  void* stream) {
+  const char* fn = "gbnf_image_trainer_backward_x";
+  if (!t || !trace_c || !x || !g_x) return fail(GBNF_ERR_INVALID, "%s: null argument (trainer, trace, x and g_x are required)", fn);
+  if (n <= 0) return n == 0 ? GBNF_OK : fail(GBNF_ERR_INVALID, "%s: n < 0", fn);
+  if (n > 65535) return fail(GBNF_ERR_UNSUPPORTED, "%s: at most 65535 images per call", fn);
+  int64_t need = 0;
+  if (const int rc = gbnf_image_trainer_workspace_bytes(t, n, &need)) return rc;
+  if (!workspace || workspace_bytes < need)
+    return fail(GBNF_ERR_INVALID, "%s: workspace too small: %lld bytes < %lld (gbnf_image_trainer_workspace_bytes)", fn,
+                (long long)workspace_bytes, (long long)need);
+  const TrainSpace sp = train_space(t, (float*)workspace, n);
+  return trainer_backward(fn, t, trace_c, n, g_z, g_ldj, grads, x, noise, g_x, accumulate ? 1 : 0, sp, (hipStream_t)stream);
 }
 
 }  // extern "C"

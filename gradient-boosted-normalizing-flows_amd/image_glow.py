@@ -379,6 +379,26 @@ class _ImageFlowFunction(torch.autograd.Function):
         return (None, None, None, None) + tuple(views[p].view_as(t) for p, t in zip(ctx.paths, tensors))
 
 
+class _ImageFlowInputGradFunction(torch.autograd.Function):
+    """``_ImageFlowFunction`` whose backward also returns the gradient with respect to x (gbnf_image_trainer_backward_x): the
+    ``input_grad=True`` form of ``component_forward``.  ``noise`` is held fixed."""
+
+    @staticmethod
+    def forward(ctx, trainer, x, noise, paths, *tensors):
+        x = x.detach().contiguous()
+        z, ldj, trace = trainer.forward(x, noise)
+        ctx.trainer, ctx.trace, ctx.paths, ctx.x, ctx.noise = trainer, trace, paths, x, noise
+        ctx.save_for_backward(*tensors)
+        return z, ldj
+
+    @staticmethod
+    def backward(ctx, g_z, g_ldj):
+        tensors = ctx.saved_tensors
+        g_x, _, views = ctx.trainer.backward_x(ctx.trace, ctx.x, ctx.noise, g_z.contiguous().float(), g_ldj.contiguous().float(),
+                                               want_grads=True)
+        return (None, g_x, None, None) + tuple(views[p].view_as(t) for p, t in zip(ctx.paths, tensors))
+
+
 class BoostedImageFlow(nn.Module):
     """models/boosted_flow.py:BoostedFlow for image components: density evaluation, z -> x, and (train mode, gradients enabled) the
     differentiable forward of one component."""
@@ -724,13 +744,15 @@ class BoostedImageFlow(nn.Module):
             out["grads"] = {name: views[path] for path, name in self._step_names(c, bind).items()}
         return out
 
-    def _component_forward_train(self, x, c, noise, y=None):
+    def _component_forward_train(self, x, c, noise, y=None, input_grad=False):
         """Differentiable (z, z_mu, z_var, ldj, y_logits) of component c on its live parameters (models/glow.py:92-110).  y_logits is
         None for an unconditional component; a class-conditional one forms its per-image prior and its logits from the live
         ``project_ycond`` / ``project_class`` with torch ops on (n, 2Cz) and (n, Y) tensors, so the reference's own
-        ``loss.backward()`` loop reaches all six tensors."""
-        if x.requires_grad:
+        ``loss.backward()`` loop reaches all six tensors.  ``input_grad``: the backward also returns the gradient with respect to x."""
+        if x.requires_grad and not input_grad:
             raise NotImplementedError("the image training path has no gradient with respect to x")
+        if input_grad and x.dtype != torch.float32:
+            raise ValueError("input_grad needs a float32 x")
         flow = self.flows[c]
         trainer, bind = self.native_trainer(c)
         paths, tensors, log_dets, plain = [], [], [], {}
@@ -748,7 +770,8 @@ class BoostedImageFlow(nn.Module):
             paths.append(path)
             tensors.append(obj)
         with torch.cuda.device(x.device):
-            z, ldj = _ImageFlowFunction.apply(trainer, x, noise, tuple(paths), *tensors)
+            fn = _ImageFlowInputGradFunction if input_grad else _ImageFlowFunction
+            z, ldj = fn.apply(trainer, x, noise, tuple(paths), *tensors)
         for l, ws in plain.items():
             log_dets.append(trainer.level_pixels[l] * torch.linalg.slogdet(torch.stack(ws).double())[1].sum().to(z.dtype))
         if log_dets:                                     # the 1x1 matrices' own log-determinants: closed form on C x C
@@ -768,19 +791,20 @@ class BoostedImageFlow(nn.Module):
         z_mu, z_var = hy[:, :Cz].view(-1, Cz, 1, 1).expand(z.shape), hy[:, Cz:].view(-1, Cz, 1, 1).expand(z.shape)
         return z, z_mu, z_var, ldj, flow.project_class(z.mean(2).mean(2))
 
-    def component_forward(self, x, c, noise=None, want_z=True, y_onehot=None):
+    def component_forward(self, x, c, noise=None, want_z=True, y_onehot=None, input_grad=False):
         """x (N,C,H,W) in [0,1] -> z, ldj, ll of component c.  ``noise``: the U(0,1) dequantisation noise
         (models/glow.py:135); drawn on the device when None.  In train mode with gradients enabled: the differentiable
         (z, z_mu, z_var, ldj, y_logits) of ``forward`` on the live parameters instead.  A class-conditional component needs
         ``y_onehot`` (n, y_classes) and returns the reference's five values in evaluation mode too:
         (z, z_mu, z_var, ldj, y_logits) with the (n,Cz,1,1) priors expanded as views -- its ll under that prior is
-        ``component_log_prob``'s."""
+        ``component_log_prob``'s.  ``input_grad`` (a recorded call only): an ``x`` that requires grad gets its gradient from
+        ``backward()`` as well (the noise held fixed); without the keyword such an x is refused as ever."""
         self._check(x)
         y = self._y(int(c), y_onehot, x.shape[0])
         if self._recording(int(c)):
             xx = x if x.requires_grad else x.contiguous().float()
             nn_ = torch.rand_like(xx) if noise is None else noise.contiguous().float()
-            return self._component_forward_train(xx, int(c), nn_, y)
+            return self._component_forward_train(xx, int(c), nn_, y, input_grad=bool(input_grad) and x.requires_grad)
         x = x.contiguous().float()
         if noise is None:
             noise = torch.rand_like(x)
@@ -1102,6 +1126,55 @@ class BoostedImageFlow(nn.Module):
         ll = self.component_log_prob(x, n_used, noise, y_onehot)
         with torch.cuda.device(x.device):
             return native.mixture_lse(ll.t().contiguous(), self.rho)
+
+    # ---- the score: grad_x log p(x) of a component and of the mixture (gbnf_image_mixture_score), eval or train mode
+    def _score_call(self, x, comps, log_w, noise, y_onehot, want_r):
+        self._check(x)
+        x = x.detach().contiguous().float()
+        if x.dim() != 4 or tuple(x.shape[1:]) != tuple(self.flows[0].input_size):
+            raise ValueError(f"x must be (n, {tuple(self.flows[0].input_size)}), got {tuple(x.shape)}")
+        if noise is None:
+            noise = torch.rand_like(x)
+        else:
+            self._check(noise)
+            if noise.shape != x.shape:
+                raise ValueError(f"noise must have the shape of x, got {tuple(noise.shape)}")
+            noise = noise.detach().contiguous().float()
+        y = self._y(comps[0], y_onehot, x.shape[0])
+        with torch.cuda.device(x.device):
+            trainers = [self._step_trainer(c)[0] for c in comps]
+            return native.image_mixture_score(trainers, log_w, x, noise, y=y, want_r=want_r)
+
+    def _score_n_used(self, n_used):
+        n_used = self.num_components if n_used is None else int(n_used)
+        if not 1 <= n_used <= self.num_components:
+            raise ValueError(f"n_used={n_used} is outside 1 .. {self.num_components}")
+        return n_used
+
+    def component_score(self, x, c, noise=None, y_onehot=None):
+        """-> (g_x like x, ll (N,)): the score grad_x ll_c(x) of component c and its log-density, from the exact-f32 training-path
+        kernels on the live parameters with no weight gradient computed.  ``noise`` (drawn once when None) is held fixed: the
+        gradient is that of the dequantised density at that noise.  Uninitialised ActNorms raise ValueError as ``training_step``."""
+        c = int(c)
+        if not 0 <= c < self.num_components:
+            raise ValueError(f"c={c} is no component of this model (0 .. {self.num_components - 1})")
+        g_x, ll, _ = self._score_call(x, [c], torch.zeros(1, dtype=torch.float32, device=x.device), noise, y_onehot, False)
+        return g_x, ll
+
+    def score(self, x, n_used=None, noise=None, y_onehot=None, return_log_prob=False, return_responsibilities=False):
+        """grad_x log p(x) of the mixture of the first ``n_used`` components, p = sum_c w_c p_c with w_c = rho_c / sum_{j < n_used} rho_j,
+        in ONE library call: sum_c r_c grad_x ll_c with the responsibilities r_c = softmax_c(log w + ll).  ``noise`` (drawn once when
+        None) is shared by the components and held fixed.  -> g_x, or (g_x[, log_prob (N,)][, responsibilities (N, C_used)])."""
+        n_used = self._score_n_used(n_used)
+        rho = self.rho[:n_used].detach().float()
+        g_x, G, r = self._score_call(x, list(range(n_used)), torch.log(rho / rho.sum()).contiguous(), noise, y_onehot,
+                                     bool(return_responsibilities))
+        out = (g_x,) + ((G,) if return_log_prob else ()) + ((r.t(),) if return_responsibilities else ())
+        return out[0] if len(out) == 1 else out
+
+    def responsibilities(self, x, n_used=None, noise=None, y_onehot=None):
+        """(N, C_used): p(component c | x) under the mixture ``score`` differentiates."""
+        return self.score(x, n_used, noise, y_onehot, return_responsibilities=True)[1]
 
     # ---- label-free evaluation of a class-conditional model: the class enters a component's top prior only (models/glow.py:62-84), so
     # one pass of the flow serves every class (gbnf_image_flow_forward_classes)

@@ -59,6 +59,8 @@ ABI_SYMBOLS = (
     "gbnf_image_boosted_step_workspace_bytes_y", "gbnf_image_boosted_nll_step_y",
     "gbnf_image_flow_set_deterministic", "gbnf_image_flow_get_deterministic",
     "gbnf_image_flow_forward_classes", "gbnf_class_posterior", "gbnf_image_mixture_rho_step_y",
+    "gbnf_image_trainer_backward_x", "gbnf_image_score_seed", "gbnf_mixture_responsibilities",
+    "gbnf_image_mixture_score_workspace_bytes", "gbnf_image_mixture_score",
 )
 
 
@@ -274,6 +276,11 @@ def lib():
     L.gbnf_image_flow_forward_classes.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
     L.gbnf_class_posterior.argtypes = [vp, vp, i64, i32, vp, vp, vp, vp]
     L.gbnf_image_mixture_rho_step_y.argtypes = [C.POINTER(vp), i32, vp, vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp]
+    L.gbnf_image_trainer_backward_x.argtypes = [vp, vp, vp, vp, i64, vp, vp, vp, vp, i32, vp, i64, vp]
+    L.gbnf_image_score_seed.argtypes = [vp, vp, i64, vp, i64, i32, i32, vp, vp, vp]
+    L.gbnf_mixture_responsibilities.argtypes = [vp, vp, i32, i64, vp, vp, vp]
+    L.gbnf_image_mixture_score_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
+    L.gbnf_image_mixture_score.argtypes = [C.POINTER(vp), i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -848,6 +855,7 @@ class NativeImageTrainer:
     CUDA tensor -- the caller's parameter storage itself (``perm`` stays a host int64 array; ``perm_w`` is the composed C x C matrix
     of an InvertibleConv1x1).  Nothing is copied: the library keeps the addresses, this object keeps the tensors alive.  ``learn_top``
     is ignored (the top prior is the caller's).  ``ldj`` of ``forward`` EXCLUDES the log-determinants of the ``perm_w`` matrices.
+    ``backward`` returns the parameters' gradients, ``backward_x`` the gradient with respect to x (with or without them).
 
     ``deterministic``: the weight gradients are flushed as per-slice partials and the log-det sums as per-wave slots, both added in
     a fixed order (gbnf_image_trainer_set_deterministic): ``forward``, ``backward``, ``nll_step`` and the step of
@@ -1294,6 +1302,59 @@ class NativeImageTrainer:
             _check(lib().gbnf_image_trainer_backward(self.handle, ptr(trace), n, ptr(g_z), ptr(g_ldj), ptr(out), ptr(ws),
                                                      ws.numel() * 4, _stream_ptr()))
         return out, {path: out[off: off + int(np.prod(shape))].view(shape) for path, off, shape in self._regions}
+
+    def backward_x(self, trace, x, noise=None, g_z=None, g_ldj=None, want_grads=False, out=None, g_x=None, workspace=None):
+        """The gradient with respect to the input (gbnf_image_trainer_backward_x): ``x`` and ``noise`` as the ``forward`` that left
+        ``trace`` took them.  -> g_x (n, C, H, W); with ``want_grads`` (or a flat buffer ``out`` to accumulate into) also the weight
+        gradients, (g_x, flat, {path: view}) as ``backward`` returns them.  Without them no weight-gradient kernel runs: the form
+        the score uses.  ``g_x``: a tensor to ACCUMULATE into (None: a new one, stored).  ``workspace``: a contiguous device tensor
+        to use instead of the trainer's own (its size is checked by the library)."""
+        import torch
+        _require_device_f32(trace, "trace")
+        _require_device_f32(x, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
+            raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
+        n = x.shape[0]
+        nt = C.c_int64()
+        _check(lib().gbnf_image_trainer_trace_floats(self.handle, n, C.byref(nt)))
+        if trace.numel() != nt.value:
+            raise GbnfError(f"trace has {trace.numel()} floats: not this trainer's at n = {n} ({nt.value})")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        if g_z is not None:
+            _require_device_f32(g_z, "g_z")
+            if tuple(g_z.shape) != (n,) + self.z_shape:
+                raise GbnfError(f"g_z must be {(n,) + self.z_shape}, got {tuple(g_z.shape)}")
+        if g_ldj is not None:
+            _require_device_f32(g_ldj, "g_ldj")
+            if tuple(g_ldj.shape) != (n,):
+                raise GbnfError(f"g_ldj must be ({n},), got {tuple(g_ldj.shape)}")
+        if out is not None:
+            _require_device_f32(out, "out")
+            if out.numel() != self.grad_floats:
+                raise GbnfError(f"out has {out.numel()} elements, expected {self.grad_floats}")
+        elif want_grads:
+            out = torch.zeros(self.grad_floats, dtype=torch.float32, device=x.device)
+        accumulate = g_x is not None
+        if accumulate:
+            _require_device_f32(g_x, "g_x")
+            if g_x.shape != x.shape:
+                raise GbnfError(f"g_x must have the shape of x, got {tuple(g_x.shape)}")
+        else:
+            g_x = torch.empty_like(x)
+        if n:
+            ws = self._workspace(n) if workspace is None else workspace
+            if not ws.is_cuda or not ws.is_contiguous():
+                raise GbnfError("workspace must be a contiguous device tensor")
+            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+            _check(lib().gbnf_image_trainer_backward_x(self.handle, ptr(trace), ptr(x), ptr(noise), n, ptr(g_z), ptr(g_ldj), ptr(out),
+                                                       ptr(g_x), 1 if accumulate else 0, ptr(ws), ws.numel() * ws.element_size(),
+                                                       _stream_ptr()))
+        if out is None:
+            return g_x
+        return g_x, out, {path: out[off: off + int(np.prod(shape))].view(shape) for path, off, shape in self._regions}
 
     def close(self):
         if getattr(self, "handle", None):
@@ -2061,6 +2122,99 @@ def class_posterior(class_ll, log_prior=None, want_post=True, want_pred=False):
     if n:
         _check(lib().gbnf_class_posterior(ptr(class_ll), ptr(log_prior), n, Y, ptr(log_px), ptr(post), ptr(pred), _stream_ptr()))
     return log_px, post, pred
+
+
+def score_seed(z, prior, r=None):
+    """gbnf_image_score_seed: z (n, Cz, Hz, Wz) device float32, ``prior`` = (mu | logvar) as (2Cz,) -- one prior for all rows -- or
+    (n, 2Cz), ``r`` (n,) or None for 1 -> (g_z like z, g_ldj (n,)): the gradient of r * (log_normal_diag(z, mu, logvar) + ldj)."""
+    import torch
+    _require_device_f32(z, "z")
+    _require_device_f32(prior, "prior")
+    if z.dim() != 4:
+        raise GbnfError(f"z must be (n, Cz, Hz, Wz), got {tuple(z.shape)}")
+    n, cz = int(z.shape[0]), int(z.shape[1])
+    if tuple(prior.shape) == (2 * cz,):
+        stride = 0
+    elif tuple(prior.shape) == (n, 2 * cz):
+        stride = 2 * cz
+    else:
+        raise GbnfError(f"prior must be ({2 * cz},) or ({n}, {2 * cz}), got {tuple(prior.shape)}")
+    if r is not None:
+        _require_device_f32(r, "r")
+        if tuple(r.shape) != (n,):
+            raise GbnfError(f"r must be ({n},), got {tuple(r.shape)}")
+    g_z = torch.empty_like(z)
+    g_ldj = torch.empty(n, dtype=torch.float32, device=z.device)
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+    if n:
+        _check(lib().gbnf_image_score_seed(ptr(z), ptr(prior), stride, ptr(r), n, cz, int(z.shape[2] * z.shape[3]), ptr(g_z), ptr(g_ldj),
+                                           _stream_ptr()))
+    return g_z, g_ldj
+
+
+def mixture_responsibilities(ll, log_w):
+    """gbnf_mixture_responsibilities: ll (C, N) device float32 per-component log-densities (image or tabular), log_w (C,) ->
+    (r (C, N) = softmax_c(log_w + ll), G (N,) = logsumexp_c(log_w + ll)); a column of -inf gives G = -inf and r = 0."""
+    import torch
+    _require_device_f32(ll, "ll")
+    _require_device_f32(log_w, "log_w")
+    if ll.dim() != 2 or tuple(log_w.shape) != (ll.shape[0],) or ll.shape[0] < 1:
+        raise GbnfError(f"ll must be (C, N) with C >= 1 and log_w (C,), got {tuple(ll.shape)} and {tuple(log_w.shape)}")
+    c, n = ll.shape
+    r = torch.empty_like(ll)
+    G = torch.empty(n, dtype=torch.float32, device=ll.device)
+    if n:
+        _check(lib().gbnf_mixture_responsibilities(C.c_void_p(ll.data_ptr()), C.c_void_p(log_w.data_ptr()), c, n, C.c_void_p(r.data_ptr()),
+                                                   C.c_void_p(G.data_ptr()), _stream_ptr()))
+    return r, G
+
+
+def image_mixture_score_workspace_bytes(trainers, n):
+    arr = (C.c_void_p * len(trainers))(*[t.handle for t in trainers])
+    nb = C.c_int64()
+    _check(lib().gbnf_image_mixture_score_workspace_bytes(arr, len(trainers), int(n), C.byref(nb)))
+    return int(nb.value)
+
+
+def image_mixture_score(trainers, log_w, x, noise=None, y=None, want_r=False, workspace=None):
+    """gbnf_image_mixture_score: the score of the mixture of ``trainers`` (``NativeImageTrainer``s of components 0 .. C-1 with their
+    LU factors / top prior / conditioning bound) with log-weights ``log_w`` (C,) in ONE library call -> (g_x like x, G (n,) =
+    log p(x), r (C, n) | None).  ``noise`` is shared by the components and held fixed; ``y`` (n, Y) for conditioned trainers.
+    ``workspace``: a contiguous device tensor to use (None: allocated here; its size is checked by the library)."""
+    import torch
+    trainers = list(trainers)
+    if not trainers or any(not isinstance(t, NativeImageTrainer) or not t.handle for t in trainers):
+        raise GbnfError("trainers must be a non-empty sequence of open NativeImageTrainers")
+    _require_device_f32(x, "x")
+    if x.dim() != 4 or any(tuple(x.shape[1:]) != t.input_size for t in trainers):
+        raise GbnfError(f"x must be (n,{trainers[0].input_size}) for every trainer, got {tuple(x.shape)}")
+    n = x.shape[0]
+    if noise is not None:
+        _require_device_f32(noise, "noise")
+        if noise.shape != x.shape:
+            raise GbnfError("noise must have the shape of x")
+    _require_device_f32(log_w, "log_w")
+    if tuple(log_w.shape) != (len(trainers),):
+        raise GbnfError(f"log_w must be ({len(trainers)},), got {tuple(log_w.shape)}")
+    conditioned = [t.y_classes > 0 for t in trainers]
+    if any(conditioned) and (not all(conditioned) or y is None):
+        raise GbnfError("class-conditional trainers need y (n, Y), and every trainer of the call must be conditioned")
+    if y is not None:
+        y = trainers[0]._check_y(y, n)
+    g_x = torch.empty_like(x)
+    G = torch.empty(n, dtype=torch.float32, device=x.device)
+    r = torch.empty((len(trainers), n), dtype=torch.float32, device=x.device) if want_r else None
+    if n:
+        arr = (C.c_void_p * len(trainers))(*[t.handle for t in trainers])
+        if workspace is None:
+            nb = image_mixture_score_workspace_bytes(trainers, n)
+            workspace = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+        elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
+            raise GbnfError("workspace must be a contiguous device tensor")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_image_mixture_score(arr, len(trainers), ptr(log_w), ptr(x), ptr(noise), ptr(y), n, ptr(g_x), ptr(G), ptr(r),
+                                              ptr(workspace), workspace.numel() * workspace.element_size(), _stream_ptr()))
+    return g_x, G, r
 
 
 def prepared_mixture_lse(ll, rho, out):

@@ -823,11 +823,62 @@ int gbnf_image_trainer_grad_floats(const gbnf_image_trainer* trainer, int64_t* f
 /* trace: what gbnf_image_trainer_forward left at the same n, parameters unchanged since.  g_z (n,Cz,Hz,Wz) and g_ldj (n,)
  * may each be NULL, meaning zero.  ACCUMULATES into grads (the caller zeroes it).  The ActNorm2d `logs` gradients include
  * the H*W * sum_n g_ldj[n] term of their own log-determinant; the `perm_weight` gradient is the data path only, consistent
- * with the forward.  There is no gradient with respect to x.  By default the weight gradients are summed with float atomics
- * across the (image, strip) slices of a layer: their last bits depend on the order; in deterministic mode (below) every slice
- * stores its partial and the partials are added in slice order. */
+ * with the forward.  This call returns no gradient with respect to x (gbnf_image_trainer_backward_x does).  By default the weight
+ * gradients are summed with float atomics across the (image, strip) slices of a layer: their last bits depend on the order; in
+ * deterministic mode (below) every slice stores its partial and the partials are added in slice order. */
 int gbnf_image_trainer_backward(gbnf_image_trainer* trainer, const float* trace, int64_t n, const float* g_z,
                                 const float* g_ldj, float* grads, void* workspace, int64_t workspace_bytes, void* stream);
+/* gbnf_image_trainer_backward with the gradient with respect to the input: x and noise (NULL = none) as the forward that left
+ * `trace` took them, g_x (n, C, Hi, Wi) DEVICE, accumulate != 0: g_x += the gradient, else it is stored (every pixel is written).
+ * The state gradient goes through the first step's ActNorm2d + 1 x 1 like through every other step (the same convolution kernel),
+ * then one elementwise launch applies the adjoint of dequantise + logit + first squeeze: with v the forward's pre-logit value,
+ * recomputed in f32 from x and noise,
+ *   g_x = (g_logit + g_ldj[n] (2v - 1)) / (v (1 - v)) * bounds * 255 / 256
+ * on the Hi x Wi image proper (storage outside it carries no gradient).  noise is held fixed: this is the gradient of the
+ * dequantised density at that noise.  No atomics on the data path: g_x repeats bit for bit in either mode.
+ * grads non-NULL: the weight gradients are ACCUMULATED as gbnf_image_trainer_backward does (bit-equal to it in deterministic
+ * mode).  grads NULL: the data-gradient-only form -- no weight-gradient launch, no scratch memset, no partial-sum reduce, no
+ * unfold; g_x is bit-equal to the call with grads.  GBNF_ERR_INVALID (nothing launched): a null trainer / trace / x / g_x, n < 0,
+ * a workspace below gbnf_image_trainer_workspace_bytes(n); GBNF_ERR_UNSUPPORTED: more than 65535 images.  n == 0: GBNF_OK. */
+int gbnf_image_trainer_backward_x(gbnf_image_trainer* trainer, const float* trace, const float* x, const float* noise, int64_t n,
+                                  const float* g_z, const float* g_ldj, float* grads_or_null, float* g_x, int32_t accumulate,
+                                  void* workspace, int64_t workspace_bytes, void* stream);
+/* The autograd seed of  r[i] * (log_normal_diag(z_i, mu, logvar) + ldj_i)  (no 2 pi term; image_experiment.py:227):
+ *   g_z = -r (z - mu) exp(-logvar)  (n, Cz, HW),   g_ldj = r  (n,).
+ * z (n, Cz, HW) compact as gbnf_image_trainer_forward writes it; prior: (mu | logvar), 2 Cz floats per row with a row stride of 0
+ * (one prior for all rows) or 2 Cz (a class-conditional component's per-image prior, gbnf_image_flow_prior_y's layout); r (n,)
+ * DEVICE or NULL = 1.  One elementwise launch.  GBNF_ERR_INVALID: a null z / prior / g_z / g_ldj, n < 0, Cz < 1, HW < 1, another
+ * stride. */
+int gbnf_image_score_seed(const float* z, const float* prior, int64_t prior_stride, const float* r_or_null, int64_t n, int32_t Cz,
+                          int32_t HW, float* g_z, float* g_ldj, void* stream);
+/* Responsibilities of a mixture: ll (C, N) and log_w (C,) DEVICE ->
+ *   G[n] = LSE_c(log_w[c] + ll[c][n])  (N,),    r[c][n] = exp(log_w[c] + ll[c][n] - G[n])  (C, N): softmax over c.
+ * One thread per column, double precision, component order, rounded once.  A column of -inf: G = -inf and r = 0 (no NaN out of
+ * inf - inf; torch.logsumexp's value); a NaN entry makes its column NaN.  Where ll came from does not matter: an image table and
+ * a tabular gbnf_mixture_component_log_prob table are both (C, N).  GBNF_ERR_INVALID: a null pointer, n_components < 1, n < 0. */
+int gbnf_mixture_responsibilities(const float* ll, const float* log_w, int32_t n_components, int64_t n, float* r, float* G,
+                                  void* stream);
+/* The score of the boosted image mixture in ONE call:  log p(x) = LSE_c(log_w[c] + ll_c(x))  over the trainers of components
+ * 0 .. n_components - 1 and  g_x = grad_x log p(x) = sum_c r_c grad_x ll_c,  with no host read, no synchronisation, no allocation:
+ *   1. per component: the 1 x 1 log-dets (LU matrices composed, as gbnf_image_trainer_nll_step's first launch),
+ *      gbnf_image_trainer_forward, and ll_c = log_normal_diag(z, top prior) + ldj + the log-dets (double sums, fixed order);
+ *   2. gbnf_mixture_responsibilities -> G (n,), r (C, n) (copied to r_or_null when given);
+ *   3. per component, in order: gbnf_image_score_seed with row c of r, then the data-gradient-only gbnf_image_trainer_backward_x
+ *      into g_x (n, C, Hi, Wi) -- stored by component 0, added by the others.  The backward is linear in its seeds, so no
+ *      (C, n, C Hi Wi) buffer exists.
+ * The trainers carry what the one-call step binds: gbnf_image_trainer_bind_lu, _bind_top (none: the zero-mean unit prior) and, for
+ * a class-conditional model, _bind_ycond on every one with y (n, Y) DEVICE given.  noise (NULL = none) is shared by all components
+ * and held fixed.  With every trainer in deterministic mode g_x, G and r are bit-identical across calls; otherwise only the
+ * forward's log-det atomics can move their last bits.
+ * workspace: gbnf_image_mixture_score_workspace_bytes -- per component z, ldj, prior and trace; ll, r, the seed, and the largest
+ * gbnf_image_trainer_workspace_bytes.  GBNF_ERR_INVALID (nothing launched): a null trainers / log_w / x / g_x / G / workspace or
+ * entry of trainers, n_components < 1, n < 0, trainers of different input shapes or class counts, a trainer whose last bind
+ * failed, y missing on conditioned trainers or given to plain ones, a short workspace; GBNF_ERR_UNSUPPORTED: more than 65535
+ * images.  n == 0: GBNF_OK. */
+int gbnf_image_mixture_score_workspace_bytes(gbnf_image_trainer* const* trainers, int32_t n_components, int64_t n, int64_t* bytes);
+int gbnf_image_mixture_score(gbnf_image_trainer* const* trainers, int32_t n_components, const float* log_w, const float* x,
+                             const float* noise, const float* y_or_null, int64_t n, float* g_x, float* G, float* r_or_null,
+                             void* workspace, int64_t workspace_bytes, void* stream);
 
 /* Deterministic mode of an image trainer, a property of the trainer like gbnf_trainer_set_deterministic of the tabular one
  * (off at creation; with it off the kernels, the launches, the results and the workspace sizes are what they always were).
