@@ -338,6 +338,11 @@ class _FlowFunction(torch.autograd.Function):
         g_z = None if g_z is None else g_z.contiguous().float()
         g_ldj = None if g_ldj is None else g_ldj.contiguous().float()
         with torch.cuda.device(x.device):
+            if ctx.needs_input_grad[1] and not any(ctx.needs_input_grad[2:]) and not trainer.batch_stats:
+                # no parameter asks for a gradient: the same sweeps without the weight-gradient work (gbnf_trainer_backward_x;
+                # g_x has the bits of the full call)
+                g_x = trainer.backward_x(x, g_z, g_ldj, trace=ctx.trace)
+                return (None, g_x) + (None,) * len(ctx.needs_input_grad[2:])
             g_x, grads = trainer.backward(x, g_z, g_ldj, want_gx=ctx.needs_input_grad[1], trace=ctx.trace)
         out = [g for t, g in zip(trainer.params, grads) if t is not None]
         out = [g if need else None for g, need in zip(out, ctx.needs_input_grad[2:])]
@@ -1189,6 +1194,83 @@ class BoostedFlow(nn.Module):
         with torch.cuda.device(x.device):
             G, _ = self.native_mixture(n_used).log_prob(x, self.rho.contiguous().float(), n_used=n_used)
         return G
+
+    # ---- the score: grad_x log p(x) of a component and of the mixture (gbnf_mixture_score), eval or train mode alike
+    def _score_input(self, x, comps):
+        self._check_ready(x)
+        x = x.detach().contiguous().float()
+        if x.dim() != 2:
+            raise ValueError(f"x must be (N, d), got {tuple(x.shape)}")
+        for c in comps:
+            if not all(bool(l.actnorm.inited) for l in getattr(getattr(self.flows[c], "flow", None), "layers", [])):
+                raise ValueError("ActNorm not initiated: run a forward pass on data first (models/layers.py:473-475)")
+        return x
+
+    def _log_w(self, n_used):
+        rho = self.rho[:n_used].detach().float()
+        return torch.log(rho / rho.sum()).contiguous()
+
+    def _mixture_score(self, x, comps, log_w, ll, want_r):
+        """One gbnf_mixture_score call on the trainers of ``comps``, on RUNNING statistics whatever the module's mode: the trainers'
+        batch-statistics mode is switched off for the call and put back.  The call runs the trainers' forward, which re-derives the
+        BatchNorm entries of their live blobs from the running statistics: a recorded train-mode forward of one of these components
+        that still awaits its backward has lost the batch statistics its backward sweep reads there.  Like every other forward on
+        a trainer, the call therefore moves ``forward_serial``, and that pending backward raises ``_FlowFunction``'s RuntimeError
+        instead of returning wrong gradients (run the backward first, or the forward again)."""
+        trainers = [self.native_trainer(c) for c in comps]
+        modes = [t.batch_stats for t in trainers]
+        try:
+            for t in trainers:
+                t.set_batch_stats(False)
+                if t.has_batch_stats:
+                    t.forward_serial = getattr(t, "forward_serial", 0) + 1
+            return native.mixture_score(trainers, log_w, x, ll=ll, want_r=want_r)
+        finally:
+            for t, on in zip(trainers, modes):
+                t.set_batch_stats(on)
+
+    @torch.no_grad()
+    def component_score(self, x, c):
+        """-> (g_x (N,d), ll (N,)): the score grad_x ll_c(x) of component c and its log-density ll_c = log N(z_c;0,I) + ldj_c, from the
+        training-path kernels on the live parameters with no weight gradient computed.  Running statistics in either module mode;
+        nothing is recorded for autograd.  Uninitialised ActNorms raise ValueError as ``component_inverse``."""
+        c = int(c)
+        if not 0 <= c < self.num_components:
+            raise ValueError(f"c={c} is no component of this model (0 .. {self.num_components - 1})")
+        x = self._score_input(x, [c])
+        with torch.cuda.device(x.device):
+            g_x, ll, _ = self._mixture_score(x, [c], torch.zeros(1, dtype=torch.float32, device=x.device), None, False)
+        return g_x, ll
+
+    @torch.no_grad()
+    def score(self, x, n_used=None, return_log_prob=False, return_responsibilities=False):
+        """grad_x log p(x) of the mixture of the first ``n_used`` components (default as ``log_prob``), p = sum_c w_c p_c with
+        w_c = rho_c / sum_{j < n_used} rho_j -- the closed form of ``log_prob``'s recursion -- as sum_c r_c grad_x ll_c with the
+        responsibilities r_c = softmax_c(log w + ll).  The table ll is the evaluation path's (one launch for all components), so
+        log_prob and responsibilities are its numbers; the gradient is ONE library call on the components' trainers.  In train()
+        mode of a RealNVP with BatchNorm, ``score`` / ``component_score`` between a recorded forward of one of these components and
+        its backward make that backward raise RuntimeError (the trainer's batch statistics are gone): finish the backward first.
+        -> g_x (N,d), or (g_x[, log_prob (N,)][, responsibilities (N, C_used)])."""
+        n_used = self._n_used(n_used)
+        x = self._score_input(x, range(n_used))
+        self._guard(x, range(n_used))
+        with torch.cuda.device(x.device):
+            ll = self.native_mixture(n_used).component_log_prob(x, 0, n_used)
+            g_x, G, r = self._mixture_score(x, list(range(n_used)), self._log_w(n_used), ll, bool(return_responsibilities))
+        out = (g_x,) + ((G,) if return_log_prob else ()) + ((r.t(),) if return_responsibilities else ())
+        return out[0] if len(out) == 1 else out
+
+    @torch.no_grad()
+    def responsibilities(self, x, n_used=None):
+        """(N, C_used): p(component c | x) under the mixture ``score`` differentiates.  Needs no trainer: the evaluation path's table
+        and gbnf_mixture_responsibilities."""
+        n_used = self._n_used(n_used)
+        x = self._score_input(x, range(n_used))
+        self._guard(x, range(n_used))
+        with torch.cuda.device(x.device):
+            ll = self.native_mixture(n_used).component_log_prob(x, 0, n_used)
+            r, _ = native.mixture_responsibilities(ll, self._log_w(n_used))
+        return r.t()
 
     def boosting_weights(self, x, beta=1.0):
         """Step 1-2 of compute_kl_pq_loss (density_experiment.py:612-640) for training component ``self.component``:

@@ -246,6 +246,11 @@ def main(argv=None):
     objs.append(sc_o)
     if args.force or not newer(sc_o, [sc_src, imgt_hdr, yc_hdr, hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", sc_src, "-o", sc_o])
+    # the score of the tabular path (the seed, the accumulate add, the data-gradient-only backward's ABI, the mixture's one call): gbnf_score.hip
+    tsc_o, tsc_src = os.path.join(OBJ, "gbnf_score.o"), os.path.join(HERE, "gbnf_score.hip")
+    objs.append(tsc_o)
+    if args.force or not newer(tsc_o, [tsc_src, opt_hdr, hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", tsc_src, "-o", tsc_o])
     comm_o, comm_src = os.path.join(OBJ, "gbnf_comm.o"), os.path.join(HERE, "gbnf_comm.hip")
     objs.append(comm_o)
     if args.force or not newer(comm_o, [comm_src, hdr[2], hdr[3]]):

@@ -169,4 +169,24 @@ int live_blob_forward(LiveBlob* lb, const TrainLayout& lay, const float* x, floa
 // (tests) the blob as the device packer left it / size in words
 int live_blob_words(const LiveBlob* lb, uint32_t* out_host, int64_t* n_words);
 
+// ---- the data-gradient-only backward of a tabular trainer (gbnf_train.hip; used by gbnf_score.hip) -------------------
+// What gbnf_score.hip needs of a trainer to lay out a call
+struct TrainerScoreView {
+  int d;
+  int64_t grad_floats;
+  int batch_stats;        // gbnf_trainer_set_batch_stats is on
+  int repairing;          // GBNF_MATH_DEFAULT: two forms of every call
+};
+int trainer_score_view(const gbnf_trainer* t, TrainerScoreView* out);
+// Bytes of backward workspace trainer_backward_x needs at n rows: gbnf_trainer_workspace_bytes without the deterministic mode's
+// weight-gradient partials (no launch of the data-gradient-only form touches them)
+int64_t trainer_backward_x_base_bytes(const gbnf_trainer* t, int64_t n);
+// gbnf_trainer_backward cut down to dL/dx: the same sweeps on the same launch parameters STORE g_x (n, d); no weight-gradient launch,
+// no partial-sum reduce, no gradient memset or commit.  The per-step kernels add their ActNorm / BatchNorm sums into `discard`
+// (grad_floats floats, contents of no consequence); a repairing trainer leaves the g_x of its two forms in `xpair` (2 n d floats,
+// unused otherwise) and selects between them on the device.  The caller has checked t, x, g_x, workspace, n > 0 and refused
+// batch-statistics mode; the deterministic-mode and workspace-size refusals happen here, before any launch.
+int trainer_backward_x(const gbnf_trainer* t, const float* x, int64_t n, const float* trace, const float* g_z, const float* g_ldj, float* g_x,
+                       void* workspace, int64_t workspace_bytes, float* discard, float* xpair, hipStream_t s);
+
 }  // namespace gbnf

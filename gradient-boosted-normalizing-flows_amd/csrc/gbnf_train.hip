@@ -2542,6 +2542,92 @@ int gbnf_trainer_repair_count(const gbnf_trainer* t, int64_t* calls, int32_t res
 
 }  // extern "C"
 
+// ---- backward, the data gradient only (gbnf_trainer_backward_x, gbnf_score.hip) -------------------------------------------
+// The walk of gbnf_trainer_backward with everything that serves `grads` alone cut off on the host: the sweeps get the launch
+// parameters they always get (so g_x has the bits of the full call), the chained one leaves its parameter partials in the slack rows
+// where nobody reads them, the per-step one adds its ActNorm / BatchNorm sums into `discard`.
+int gbnf::trainer_score_view(const gbnf_trainer* t, TrainerScoreView* out) {
+  if (!t || !out) return fail(GBNF_ERR_INVALID, "trainer_score_view: null argument");
+  out->d = t->d; out->grad_floats = t->grad_floats; out->batch_stats = t->batch_stats; out->repairing = t->rep.f != nullptr ? 1 : 0;
+  return GBNF_OK;
+}
+
+// The backward workspace without the deterministic mode's weight-gradient partials, which no launch of this call touches
+int64_t gbnf::trainer_backward_x_base_bytes(const gbnf_trainer* t, int64_t n) {
+  if (t->rep.f) return std::max(trainer_backward_x_base_bytes(t->rep.f, n), trainer_backward_x_base_bytes(t->rep.s, n));
+  return t->lay.at(n).workspace_bytes();
+}
+
+// Both forms of a repairing trainer into xpair, the decision between them as backward_repairing takes it, then the commit of g_x alone
+static int backward_x_repairing(const gbnf_trainer* t, const float* x, int64_t n, const float* trace, const float* g_z, const float* g_ldj,
+                                float* g_x, void* workspace, int64_t workspace_bytes, float* discard, float* xpair, hipStream_t s) {
+  const int64_t nx = n * (int64_t)t->d;
+  if (workspace_bytes < trainer_backward_x_base_bytes(t, n))
+    return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward_x: workspace too small: %lld bytes < %lld", (long long)workspace_bytes,
+                (long long)trainer_backward_x_base_bytes(t, n));
+  if (!xpair) return fail(GBNF_ERR_INVALID, "gbnf_trainer_backward_x: a repairing trainer needs room for the g_x of both forms");
+  float* xf = xpair;
+  float* xs = xpair + nx;
+  int rc = trainer_backward_x(t->rep.f, x, n, trace, g_z, g_ldj, xf, workspace, workspace_bytes, discard, nullptr, s);
+  if (rc) return rc;
+  const int mode = trace == nullptr ? 0 : (trace == t->rep.last_fwd_trace ? 1 : 2);
+  hipLaunchKernelGGL(repair_decide_kernel, dim3(1), dim3(1), 0, s, t->rep.dev, mode, saturation_counter(), 0);
+  if (trace != nullptr) rc = gbnf_trainer_forward(t->rep.s, x, n, nullptr, nullptr, const_cast<float*>(trace), s);
+  if (rc == GBNF_OK) rc = trainer_backward_x(t->rep.s, x, n, trace, g_z, g_ldj, xs, workspace, workspace_bytes, discard, nullptr, s);
+  if (rc) return rc;
+  const unsigned cb = (unsigned)((nx + 255) / 256 < 1024 ? (nx + 255) / 256 : 1024);
+  hipLaunchKernelGGL(repair_commit_kernel, dim3(cb ? cb : 1), dim3(256), 0, s, (const unsigned*)(t->rep.dev + 2), (const float*)nullptr,
+                     (const float*)nullptr, (float*)nullptr, (int64_t)0, (const float*)xf, (const float*)xs, g_x, nx);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "gbnf_trainer_backward_x commit: %s", hipGetErrorString(e));
+  t->last_bwd_ranges = t->rep.f->last_bwd_ranges;
+  return GBNF_OK;
+}
+
+int gbnf::trainer_backward_x(const gbnf_trainer* t, const float* x, int64_t n, const float* trace, const float* g_z, const float* g_ldj,
+                             float* g_x, void* workspace, int64_t workspace_bytes, float* discard, float* xpair, hipStream_t s) {
+  const char* fn = "gbnf_trainer_backward_x";
+  if (const int rc = trainer_deterministic_check(t, n, trace != nullptr, fn)) return rc;      // (nothing launched yet)
+  if (t->rep.f) return backward_x_repairing(t, x, n, trace, g_z, g_ldj, g_x, workspace, workspace_bytes, discard, xpair, s);
+  const TrainLayout lay = t->lay.at(n);
+  if (workspace_bytes < lay.workspace_bytes())
+    return fail(GBNF_ERR_INVALID, "%s: workspace too small: %lld bytes < %lld", fn, (long long)workspace_bytes,
+                (long long)lay.workspace_bytes());
+  const bool safe = t->math == GBNF_MATH_BF16X6;
+  if (safe && trace == nullptr) {      // without a trace: the traced pair, the forward into the trainer's own buffer
+    float* own_trace = nullptr;
+    float* own_ldj = nullptr;
+    int rc = own_buffer(t, lay, &own_trace, &own_ldj);
+    if (rc == GBNF_OK) rc = gbnf_trainer_forward(t, x, n, nullptr, own_ldj, own_trace, s);
+    if (rc) return rc;
+    trace = own_trace;
+  }
+  // the scale of this call's gradients, as gbnf_trainer_backward finds it
+  (void)hipMemsetAsync(t->gmax_dev, 0, sizeof(unsigned), s);
+  {
+    const int64_t work = n * (g_z ? t->d : 1);
+    const unsigned gb = (unsigned)((work + 256 * 16 - 1) / (256 * 16) < 256 ? (work + 256 * 16 - 1) / (256 * 16) : 256);
+    hipLaunchKernelGGL(gmax_kernel, dim3(gb ? gb : 1), dim3(256), 0, s, g_z, g_ldj, n, t->d, t->gmax_dev);
+  }
+  const Chain why = chained_or_why(t, lay, /*forward=*/false, trace, nullptr);
+  if (why == Chain::Yes) {
+    LiveReduce red{};      // (taken over and dropped: the partial sums stay in the slack rows behind the trace)
+    t->last_bwd_ranges = 1;
+    return live_blob_backward(t->live, lay, const_cast<float*>(trace), g_z, g_ldj, g_x, discard, t->gmax_dev, s, &red);
+  }
+  if (safe) return refuse_range_safe(fn, why, n);
+  TrainLaunch p;
+  fill_launch(t, lay, p, x);
+  p.g_z = g_z; p.g_ldj = g_ldj; p.g_x = g_x; p.grads = discard; p.ws = (float*)workspace; p.trace = trace;
+  p.gmax = t->gmax_dev;
+  t->last_bwd_ranges = 0;
+  if (trace == nullptr) launch_prep(t, s);
+  launch_train<1>(t, p, s);
+  const hipError_t e = hipGetLastError();
+  if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s launch: %s", fn, hipGetErrorString(e));
+  return GBNF_OK;
+}
+
 // What gbnf_opt.hip needs of a trainer.  The two halves of a repairing trainer bind the same tensors: the f16x3 half speaks for both.
 int gbnf::trainer_opt_view(const gbnf_trainer* t, TrainerOptView* out) {
   if (!t || !out) return fail(GBNF_ERR_INVALID, "trainer_opt_view: null argument");

@@ -61,6 +61,8 @@ ABI_SYMBOLS = (
     "gbnf_image_flow_forward_classes", "gbnf_class_posterior", "gbnf_image_mixture_rho_step_y",
     "gbnf_image_trainer_backward_x", "gbnf_image_score_seed", "gbnf_mixture_responsibilities",
     "gbnf_image_mixture_score_workspace_bytes", "gbnf_image_mixture_score",
+    "gbnf_trainer_backward_x_workspace_bytes", "gbnf_trainer_backward_x", "gbnf_score_seed",
+    "gbnf_mixture_score_workspace_bytes", "gbnf_mixture_score",
 )
 
 
@@ -281,6 +283,11 @@ def lib():
     L.gbnf_mixture_responsibilities.argtypes = [vp, vp, i32, i64, vp, vp, vp]
     L.gbnf_image_mixture_score_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
     L.gbnf_image_mixture_score.argtypes = [C.POINTER(vp), i32, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
+    L.gbnf_trainer_backward_x_workspace_bytes.argtypes = [vp, i64, C.POINTER(i64)]
+    L.gbnf_trainer_backward_x.argtypes = [vp, vp, i64, vp, vp, vp, vp, i32, vp, i64, vp]
+    L.gbnf_score_seed.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]
+    L.gbnf_mixture_score_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
+    L.gbnf_mixture_score.argtypes = [C.POINTER(vp), i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -1640,6 +1647,59 @@ class NativeTrainer:
             off += size
         return g_x, grads
 
+    def backward_x_workspace_bytes(self, n):
+        nb = C.c_int64()
+        _check(lib().gbnf_trainer_backward_x_workspace_bytes(self.handle, int(n), C.byref(nb)))
+        return int(nb.value)
+
+    def backward_x(self, x, g_z=None, g_ldj=None, trace=None, g_x=None, workspace=None):
+        """The gradient with respect to the input alone (gbnf_trainer_backward_x): the sweeps of ``backward`` with no weight-gradient
+        launch, no partial-sum reduce and no gradient buffer -> g_x (n, d), bit-equal to ``backward(..., want_gx=True)[0]``.  ``g_x``:
+        a tensor to ACCUMULATE into (None: a new one, stored).  ``trace`` as for ``backward``.  ``workspace``: a contiguous device
+        tensor to use instead of the trainer's own (its size is checked by the library).  A trainer in batch-statistics mode raises
+        GbnfError: that gradient needs the batch sums of the full backward."""
+        import torch
+        _require_device_f32(x, "x")
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise GbnfError(f"x must be (n,{self.d}), got {tuple(x.shape)}")
+        n = x.shape[0]
+        if g_z is not None:
+            _require_device_f32(g_z, "g_z")
+            if g_z.shape != x.shape:
+                raise GbnfError(f"g_z must be ({n},{self.d}), got {tuple(g_z.shape)}")
+        if g_ldj is not None:
+            _require_device_f32(g_ldj, "g_ldj")
+            if tuple(g_ldj.shape) != (n,):
+                raise GbnfError(f"g_ldj must be ({n},), got {tuple(g_ldj.shape)}")
+        if trace is not None:
+            _require_device_f32(trace, "trace")
+            nt = C.c_int64()
+            _check(lib().gbnf_trainer_trace_floats(self.handle, n, C.byref(nt)))
+            if trace.numel() != nt.value:
+                raise GbnfError(f"trace has {trace.numel()} floats: not this trainer's at n = {n} ({nt.value})")
+        accumulate = g_x is not None
+        if accumulate:
+            _require_device_f32(g_x, "g_x")
+            if g_x.shape != x.shape:
+                raise GbnfError(f"g_x must have the shape of x, got {tuple(g_x.shape)}")
+        else:
+            g_x = torch.empty_like(x)
+        if not n:
+            return g_x
+        if workspace is None:
+            nb = self.backward_x_workspace_bytes(n)
+            ws = getattr(self, "_bx_ws", None)
+            if ws is None or ws.numel() * 4 < nb or ws.device != x.device:
+                ws = self._bx_ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+        else:
+            ws = workspace
+            if not isinstance(ws, torch.Tensor) or not ws.is_cuda or not ws.is_contiguous():
+                raise GbnfError("workspace must be a contiguous device tensor")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_trainer_backward_x(self.handle, ptr(x), n, ptr(trace), ptr(g_z), ptr(g_ldj), ptr(g_x), 1 if accumulate else 0,
+                                             ptr(ws), ws.numel() * ws.element_size(), _stream_ptr()))
+        return g_x
+
     def repair_count(self, reset=False):
         """Forward / backward calls of this trainer whose bf16x6 re-run actually ran (a "repair" trainer; always 0 otherwise).
         Synchronises with the device (gbnf_trainer_repair_count)."""
@@ -2124,14 +2184,57 @@ def class_posterior(class_ll, log_prior=None, want_post=True, want_pred=False):
     return log_px, post, pred
 
 
-def score_seed(z, prior, r=None):
-    """gbnf_image_score_seed: z (n, Cz, Hz, Wz) device float32, ``prior`` = (mu | logvar) as (2Cz,) -- one prior for all rows -- or
-    (n, 2Cz), ``r`` (n,) or None for 1 -> (g_z like z, g_ldj (n,)): the gradient of r * (log_normal_diag(z, mu, logvar) + ldj)."""
+def tabular_score_seed(z, r=None, base=None, want_ll=False):
+    """gbnf_score_seed, the explicit tabular entry point: z (n, d) device float32, ``r`` (n,) or None for 1, ``base`` = (mean (d,),
+    std (d,)) device tensors or None for N(0, I) -> (g_z = -r (z - mean) / std^2, g_ldj = r[, ll (n,) = sum_j log N(z_j; mean_j,
+    std_j) with ``want_ll``; the caller adds ldj])."""
     import torch
     _require_device_f32(z, "z")
+    if z.dim() != 2:
+        raise GbnfError(f"z must be (n, d), got {tuple(z.shape)}")
+    n, d = int(z.shape[0]), int(z.shape[1])
+    if d < 1:
+        raise GbnfError(f"z must be (n, d) with d >= 1, got {tuple(z.shape)}")
+    mean = std = None
+    if base is not None:
+        mean, std = base
+        for t, name in ((mean, "base mean"), (std, "base std")):
+            _require_device_f32(t, name)
+            if tuple(t.shape) != (d,):
+                raise GbnfError(f"{name} must be ({d},), got {tuple(t.shape)}")
+    if r is not None:
+        _require_device_f32(r, "r")
+        if tuple(r.shape) != (n,):
+            raise GbnfError(f"r must be ({n},), got {tuple(r.shape)}")
+    g_z = torch.empty_like(z)
+    g_ldj = torch.empty(n, dtype=torch.float32, device=z.device)
+    ll = torch.empty(n, dtype=torch.float32, device=z.device) if want_ll else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+    if n:
+        _check(lib().gbnf_score_seed(ptr(z), ptr(mean), ptr(std), ptr(r), n, d, ptr(g_z), ptr(g_ldj), ptr(ll), _stream_ptr()))
+    return (g_z, g_ldj, ll) if want_ll else (g_z, g_ldj)
+
+
+def score_seed(z, prior=None, r=None, base=None, want_ll=False):
+    """The autograd seed of a component's log-density scaled per row by ``r`` ((n,) or None for 1), chosen by the rank of z
+    (``tabular_score_seed`` is the same tabular call without the dispatch).
+    Tabular, z (n, d) device float32 (gbnf_score_seed): ``base`` = (mean (d,), std (d,)) device tensors or None for N(0, I) ->
+    (g_z = -r (z - mean) / std^2, g_ldj = r[, ll (n,) = sum_j log N(z_j; mean_j, std_j) with ``want_ll``; the caller adds ldj]).
+    Image, z (n, Cz, Hz, Wz) (gbnf_image_score_seed): ``prior`` = (mu | logvar) as (2Cz,) -- one prior for all rows -- or (n, 2Cz) ->
+    (g_z like z, g_ldj (n,)): the gradient of r * (log_normal_diag(z, mu, logvar) + ldj)."""
+    import torch
+    _require_device_f32(z, "z")
+    if z.dim() == 2:
+        if prior is not None:
+            raise GbnfError("a tabular z (n, d) takes base=(mean, std), not an image prior")
+        return tabular_score_seed(z, r, base, want_ll)
+    if base is not None or want_ll:
+        raise GbnfError("base and want_ll belong to the tabular form: z must be (n, d)")
+    if prior is None:
+        raise GbnfError("an image z (n, Cz, Hz, Wz) needs its prior (mu | logvar)")
     _require_device_f32(prior, "prior")
     if z.dim() != 4:
-        raise GbnfError(f"z must be (n, Cz, Hz, Wz), got {tuple(z.shape)}")
+        raise GbnfError(f"z must be (n, d) or (n, Cz, Hz, Wz), got {tuple(z.shape)}")
     n, cz = int(z.shape[0]), int(z.shape[1])
     if tuple(prior.shape) == (2 * cz,):
         stride = 0
@@ -2214,6 +2317,65 @@ def image_mixture_score(trainers, log_w, x, noise=None, y=None, want_r=False, wo
         ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
         _check(lib().gbnf_image_mixture_score(arr, len(trainers), ptr(log_w), ptr(x), ptr(noise), ptr(y), n, ptr(g_x), ptr(G), ptr(r),
                                               ptr(workspace), workspace.numel() * workspace.element_size(), _stream_ptr()))
+    return g_x, G, r
+
+
+def _open_trainers(trainers):
+    trainers = list(trainers)
+    if not trainers or any(not isinstance(t, NativeTrainer) or not t.handle for t in trainers):
+        raise GbnfError("trainers must be a non-empty sequence of open NativeTrainers")
+    return trainers
+
+
+def mixture_score_workspace_bytes(trainers, n):
+    trainers = _open_trainers(trainers)
+    arr = (C.c_void_p * len(trainers))(*[t.handle for t in trainers])
+    nb = C.c_int64()
+    _check(lib().gbnf_mixture_score_workspace_bytes(arr, len(trainers), int(n), C.byref(nb)))
+    return int(nb.value)
+
+
+def mixture_score(trainers, log_w, x, ll=None, base=None, want_r=False, workspace=None):
+    """gbnf_mixture_score: the score of the mixture of ``trainers`` (``NativeTrainer``s of components 0 .. C-1, on running statistics)
+    with log-weights ``log_w`` (C,) in ONE library call -> (g_x like x, G (n,) = log p(x), r (C, n) | None).  ``ll``: the (C, n)
+    table of per-component log-densities if the caller has it (``NativeMixture.component_log_prob``: one launch for all components),
+    None: one more forward per component.  ``base`` = (mean (d,), std (d,)) device tensors or None for N(0, I).  ``workspace``: a
+    contiguous device tensor to use (None: allocated here; its size is checked by the library).  The call runs every trainer's
+    forward on the running statistics: a ``forward(want_trace=True)`` made in batch-statistics mode before it must not be followed
+    by its ``backward`` after it (the BatchNorm entries that backward reads were re-derived; ``BoostedFlow`` raises in that case)."""
+    import torch
+    trainers = _open_trainers(trainers)
+    _require_device_f32(x, "x")
+    if x.dim() != 2 or any(x.shape[1] != t.d for t in trainers):
+        raise GbnfError(f"x must be (n,{trainers[0].d}) for every trainer, got {tuple(x.shape)}")
+    n, nc = x.shape[0], len(trainers)
+    _require_device_f32(log_w, "log_w")
+    if tuple(log_w.shape) != (nc,):
+        raise GbnfError(f"log_w must be ({nc},), got {tuple(log_w.shape)}")
+    if ll is not None:
+        _require_device_f32(ll, "ll")
+        if tuple(ll.shape) != (nc, n):
+            raise GbnfError(f"ll must be ({nc}, {n}), got {tuple(ll.shape)}")
+    mean = std = None
+    if base is not None:
+        mean, std = base
+        for t, name in ((mean, "base mean"), (std, "base std")):
+            _require_device_f32(t, name)
+            if tuple(t.shape) != (x.shape[1],):
+                raise GbnfError(f"{name} must be ({x.shape[1]},), got {tuple(t.shape)}")
+    g_x = torch.empty_like(x)
+    G = torch.empty(n, dtype=torch.float32, device=x.device)
+    r = torch.empty((nc, n), dtype=torch.float32, device=x.device) if want_r else None
+    if n:
+        arr = (C.c_void_p * nc)(*[t.handle for t in trainers])
+        if workspace is None:
+            nb = mixture_score_workspace_bytes(trainers, n)
+            workspace = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+        elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
+            raise GbnfError("workspace must be a contiguous device tensor")
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        _check(lib().gbnf_mixture_score(arr, nc, ptr(log_w), ptr(mean), ptr(std), ptr(ll), ptr(x), n, ptr(g_x), ptr(G), ptr(r),
+                                        ptr(workspace), workspace.numel() * workspace.element_size(), _stream_ptr()))
     return g_x, G, r
 
 

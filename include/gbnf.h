@@ -880,6 +880,58 @@ int gbnf_image_mixture_score(gbnf_image_trainer* const* trainers, int32_t n_comp
                              const float* noise, const float* y_or_null, int64_t n, float* g_x, float* G, float* r_or_null,
                              void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- The score of the tabular path: grad_x log p(x) of a flow component and of the boosted mixture ----
+ * gbnf_trainer_backward_x: the data-gradient-only form of gbnf_trainer_backward.  g_x (n, d) is required and is STORED, or ADDED
+ * to when accumulate != 0; there is no `grads`.  The sweeps of gbnf_trainer_backward run on the launch parameters they always get,
+ * so with accumulate == 0 g_x is bit-equal to what that call writes for the same inputs -- on the register-chained sweep, the
+ * per-step kernels, a GBNF_MATH_BF16X6 and a repairing trainer, with the forward call's `trace` or NULL (as there: the trace is
+ * const for the states only).  What serves the weight gradients alone does not run: no weight-gradient launch, no partial-sum
+ * reduce (the chained sweep's ActNorm / BatchNorm partials stay in the slack rows behind the trace), no gradient memset or commit
+ * of a repairing trainer; the per-step kernels add their normalisation sums into a discard region of the workspace.  `accumulate`
+ * is a temporary (n, d) plus one elementwise launch: the backward kernels only store.
+ * workspace: gbnf_trainer_backward_x_workspace_bytes(n) -- gbnf_trainer_workspace_bytes(n) without the weight-gradient partials of
+ * deterministic mode (nothing here touches them: the size does not depend on that mode) + the discard region
+ * (gbnf_trainer_grad_floats floats) + the g_x of both forms of a repairing trainer (which gbnf_trainer_backward keeps in memory
+ * of its own) + the temporary, last: a call with accumulate == 0 is served by a workspace n d floats (rounded up to 256 bytes)
+ * shorter.
+ * Refused before any launch -- GBNF_ERR_INVALID: a null trainer / x / g_x / workspace, n < 0, a short workspace;
+ * GBNF_ERR_UNSUPPORTED: a trainer in batch-statistics mode (gbnf_trainer_set_batch_stats: its input gradient needs the batch
+ * sums that only the full backward forms), and the deterministic-mode refusals of gbnf_trainer_backward, unchanged.  n == 0:
+ * GBNF_OK. */
+int gbnf_trainer_backward_x_workspace_bytes(const gbnf_trainer* trainer, int64_t n, int64_t* bytes);
+int gbnf_trainer_backward_x(const gbnf_trainer* trainer, const float* x, int64_t n, const float* trace, const float* g_z,
+                            const float* g_ldj, float* g_x, int32_t accumulate, void* workspace, int64_t workspace_bytes,
+                            void* stream);
+/* The autograd seed of  r[i] * (sum_j log N(z_ij; mean_j, std_j) + ldj_i)  and that sum, in one elementwise launch (one wave per
+ * 64 rows, no LDS):
+ *   g_z = -r (z - mean) / std^2  (n, d),   g_ldj = r  (n,),   ll[i] = sum_j log N(z_ij; mean_j, std_j)  (n,) unless NULL.
+ * mean / std (d,) DEVICE, both or neither; NULL = the standard normal.  r (n,) DEVICE or NULL = 1.  The constant is that of
+ * gbnf_mixture_component_log_prob, 2 pi term included; the per-row sum runs in double, in feature order, and is rounded once;
+ * the caller adds ldj.  GBNF_ERR_INVALID: a null z / g_z / g_ldj, n < 0, d < 1, exactly one of mean / std. */
+int gbnf_score_seed(const float* z, const float* base_mean_or_null, const float* base_std_or_null, const float* r_or_null, int64_t n,
+                    int32_t d, float* g_z, float* g_ldj, float* ll_or_null, void* stream);
+/* The score of the boosted tabular mixture in ONE call:  log p(x) = LSE_c(log_w[c] + ll_c(x))  over the trainers of components
+ * 0 .. n_components - 1 (the closed form of gbnf_mixture_lse's recursion: log_w[c] = log(rho[c] / sum(rho[0:n_components]))) and
+ * g_x = grad_x log p(x) = sum_c r_c grad_x ll_c  (n, d),  with no host read, no synchronisation, no allocation:
+ *   1. the table ll (C, n): ll_or_null as it is (DEVICE; e.g. gbnf_mixture_component_log_prob's, one launch for all components),
+ *      else per component gbnf_trainer_forward into one reused (n, d) buffer and gbnf_score_seed's ll + ldj.  (That forward gets
+ *      the call's trace buffer as scratch: every math mode then stays on its register-chained sweep and a range-safe trainer
+ *      allocates nothing.)  n_components == 1 without a table: skipped, the ll of step 3's forward is what G is made of;
+ *   2. gbnf_mixture_responsibilities -> G (n,), r (C, n) (copied to r_or_null when given);
+ *   3. per component, in order: a traced gbnf_trainer_forward, gbnf_score_seed with row c of r, gbnf_trainer_backward_x into g_x
+ *      -- stored by component 0, added by the others.
+ * base mean / std (d,) DEVICE, both or neither (NULL: N(0, I)); the table given must have been made with the same base.  The
+ * workspace (gbnf_mixture_score_workspace_bytes) holds ONE trace, sized for the widest component, not C of them: the price is a
+ * second forward per component when no table is given.  On the chained sweeps nothing on the data path is atomic: g_x, G and r
+ * repeat bit for bit.
+ * Refused with nothing launched -- GBNF_ERR_INVALID: a null trainers / entry of trainers / log_w / x / g_x / G / workspace,
+ * n_components < 1, n < 0, trainers of different d, exactly one of mean / std, a short workspace; GBNF_ERR_UNSUPPORTED: a trainer
+ * in batch-statistics mode, and gbnf_trainer_backward's deterministic-mode refusals.  n == 0: GBNF_OK. */
+int gbnf_mixture_score_workspace_bytes(gbnf_trainer* const* trainers, int32_t n_components, int64_t n, int64_t* bytes);
+int gbnf_mixture_score(gbnf_trainer* const* trainers, int32_t n_components, const float* log_w, const float* base_mean_or_null,
+                       const float* base_std_or_null, const float* ll_or_null, const float* x, int64_t n, float* g_x, float* G,
+                       float* r_or_null, void* workspace, int64_t workspace_bytes, void* stream);
+
 /* Deterministic mode of an image trainer, a property of the trainer like gbnf_trainer_set_deterministic of the tabular one
  * (off at creation; with it off the kernels, the launches, the results and the workspace sizes are what they always were).
  * While it is on, for a fixed trainer, fixed inputs, fixed parameter values, a fixed n and a fixed process environment
