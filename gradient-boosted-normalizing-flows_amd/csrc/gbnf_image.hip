@@ -277,6 +277,8 @@ __device__ __forceinline__ void img_conv_body(const ConvLaunch& p, const int n, 
           } else {                                                  // Split2d: log_normal_diag(z2; mean, log-var)
             const float dlt = z2 - h0;
             ld += -0.5f * (h1 + dlt * dlt * __expf(-h1));           // utils/distributions.py:14, models/layers.py:703
+            if constexpr (EPI == EPI_SPLIT_EPS || EPI == EPI_SPLIT_EPS_ORD)      // the half as EPI_SPLIT_INV takes it back (T = 1),
+              p.eps[(int64_t)n * p.eps_img + ((int64_t)j * p.Hv + row) * p.Wv + pc] = dlt * __expf(-h1);      // in the map's own size
           }
         }
       }
@@ -337,14 +339,14 @@ __device__ __forceinline__ void img_conv_body(const ConvLaunch& p, const int n, 
     }
   }
 
-  if constexpr (EPI == EPI_COUPLE_AFFINE || EPI == EPI_SPLIT) {
+  if constexpr (EPI == EPI_COUPLE_AFFINE || EPI == EPI_SPLIT || EPI == EPI_SPLIT_EPS) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) ld += __shfl_xor(ld, m);
     if (lane == 0) atomicAdd(p.ldj + n, ld);
   }
   // the ordered forms: every wave of every workgroup reaches this point and stores its partial (zero if it ran no epilogue) to its
   // slot of image n; img_ldj_reduce_kernel adds the slots in slot order
-  if constexpr (EPI == EPI_COUPLE_AFFINE_ORD || EPI == EPI_SPLIT_ORD) {
+  if constexpr (EPI == EPI_COUPLE_AFFINE_ORD || EPI == EPI_SPLIT_ORD || EPI == EPI_SPLIT_EPS_ORD) {
 #pragma unroll
     for (int m = 1; m < 64; m <<= 1) ld += __shfl_xor(ld, m);
     const int slots = p.ldj_stride > 0 ? p.ldj_stride : p.n_strips * p.o_split * IMG_WAVES;
@@ -676,6 +678,7 @@ struct RepairOp {
   float f[2];
   const float* prior;     // ROP_FINAL
   int64_t eps_img, eps_lvl;   // ROP_UNSQUEEZE: eps of this level = eps + eps_lvl * n_batch + image * eps_img (0 / 0: none)
+                              // ROP_CONV with a Split2d epilogue (forward programmes): the same, of RepairArgs::eps_out
 };
 
 struct RepairArgs {
@@ -694,6 +697,7 @@ struct RepairArgs {
   float tol;
   unsigned* host_words;       // pinned: [2] checks completed, [3] checks failed, [4] worst relative difference (float bits);
                               // [5] [6] [7]: the same of the z -> x direction
+  float* eps_out;             // forward, gbnf_image_flow_encode: the call's eps (null: not asked for)
 };
 
 __global__ void __launch_bounds__(256) img_compact_kernel(const unsigned* __restrict__ mark, int n, unsigned* __restrict__ list,
@@ -770,6 +774,11 @@ __global__ void __launch_bounds__(64 * IMG_WAVES) img_repair_kernel(const Repair
             else if (op.epi == EPI_COUPLE_AFFINE) img_repair_conv<EPI_COUPLE_AFFINE>(p, op.pt, op.ks);
             else if (op.epi == EPI_COUPLE_ADD) img_repair_conv<EPI_COUPLE_ADD>(p, op.pt, op.ks);
             else if (op.epi == EPI_COUPLE_AFFINE_ORD) img_repair_conv<EPI_COUPLE_AFFINE_ORD>(p, op.pt, op.ks);     // (the deterministic
+            else if (a.eps_out != nullptr && !a.check) {      // gbnf_image_flow_encode: the image's eps of this level too (a check writes nothing)
+              p.eps = a.eps_out + op.eps_lvl * a.n + img * op.eps_img; p.eps_img = 0;
+              if (op.epi == EPI_SPLIT_ORD) img_repair_conv<EPI_SPLIT_EPS_ORD>(p, op.pt, op.ks);
+              else img_repair_conv<EPI_SPLIT_EPS>(p, op.pt, op.ks);
+            }
             else if (op.epi == EPI_SPLIT_ORD) img_repair_conv<EPI_SPLIT_ORD>(p, op.pt, op.ks);                     //  mode's programme)
             else img_repair_conv<EPI_SPLIT>(p, op.pt, op.ks);
           } else {
@@ -1176,7 +1185,7 @@ struct ActNormStats;
 static int image_record_repair_ops(gbnf_image_flow* f);
 static int image_forward_impl(const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj, float* ll,
                               float* workspace, hipStream_t s, bool force_f32, unsigned* mark, ActNormStats* stats = nullptr,
-                              Recorder* rec = nullptr, float* slots = nullptr);
+                              Recorder* rec = nullptr, float* slots = nullptr, float* eps = nullptr);
 
 static int image_probe(gbnf_image_flow* f) {
   constexpr int PN = 4;
@@ -1396,6 +1405,8 @@ int gbnf_image_flow_create_mode(const gbnf_image_flow_desc* d, int32_t math_mode
     if (e == hipSuccess) e = allow_lds<EPI_SPLIT>();
     if (e == hipSuccess) e = allow_lds<EPI_COUPLE_AFFINE_ORD>();
     if (e == hipSuccess) e = allow_lds<EPI_SPLIT_ORD>();
+    if (e == hipSuccess) e = allow_lds<EPI_SPLIT_EPS>();
+    if (e == hipSuccess) e = allow_lds<EPI_SPLIT_EPS_ORD>();
     if (e == hipSuccess) e = allow_lds<EPI_COUPLE_AFFINE_INV>();
     if (e == hipSuccess) e = allow_lds<EPI_COUPLE_ADD_INV>();
     if (e == hipSuccess) e = allow_lds<EPI_SPLIT_INV>();
@@ -1533,8 +1544,12 @@ struct ActNormStats {
   int channels;      // out: channels of that ActNorm2d (-1: index past the last one)
 };
 static int image_forward_impl(const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj, float* ll,
-                              float* workspace, hipStream_t s, bool force_f32, unsigned* mark, ActNormStats* stats, Recorder* rec, float* slots) {
+                              float* workspace, hipStream_t s, bool force_f32, unsigned* mark, ActNormStats* stats, Recorder* rec, float* slots,
+                              float* eps) {
   const int64_t chw = f->state_img;
+  // eps (gbnf_image_flow_encode; null = not asked for): every Split2d level also stores the half it drops, standardised, in the layout
+  // gbnf_image_flow_inverse reads -- level 0 first, level l a contiguous (n, C_l/2, Hv_l, Wv_l) array at eps + eps_off * n
+  int64_t eps_off = 0;
   // slots (deterministic mode; null = the atomic form): the (n, f->ldj_stride) log-det slot array of this pass.  Every launch that
   // carries a log-det takes the next run of each image's row (slot_off: fixed by the launches in front of it, i.e. by the handle's
   // geometry and the kernels its math mode runs) and STORES one partial per wave; one thread per image adds the row in slot order
@@ -1730,13 +1745,21 @@ static int image_forward_impl(const gbnf_image_flow* f, const float* x, const fl
       p.H = H; p.W = W; p.Hv = Hv; p.Wv = Wv; p.n_strips = n_strips; p.ldj = ldj;
       p.in = cur; p.in_img = img; p.wp = blob + c.w_off; p.bias = blob + c.b_off;
       p.st = cur + (int64_t)c1 * H * W; p.st_img = img; p.cin = c.cin; p.cout = c.cout; p.ks = c.ks;
+      const int64_t eps_lvl = (int64_t)(C - c1) * Hv * Wv;      // (eps has the map's own size)
+      if (eps != nullptr) { p.eps = eps + eps_off * n; p.eps_img = eps_lvl; }
       if (slots != nullptr) {
         p.ldj = take_slots(n_strips * IMG_WAVES); p.ldj_stride = f->ldj_stride;
         if (p.ldj == nullptr) return fail(GBNF_ERR_INVALID, "%s", slots_short);
-        launch_conv<EPI_SPLIT_ORD>(p, (int)n, s, rec);
+        if (eps != nullptr) launch_conv<EPI_SPLIT_EPS_ORD>(p, (int)n, s);
+        else launch_conv<EPI_SPLIT_ORD>(p, (int)n, s, rec);
       } else {
-        launch_conv<EPI_SPLIT>(p, (int)n, s, rec);
+        if (eps != nullptr) launch_conv<EPI_SPLIT_EPS>(p, (int)n, s);
+        else launch_conv<EPI_SPLIT>(p, (int)n, s, rec);
       }
+      if (rec != nullptr) {      // the recorded split op knows where its level's eps goes: the repair launch of an encode call stores them
+        rec->ops.back().eps_img = eps_lvl; rec->ops.back().eps_lvl = eps_off;
+      }
+      eps_off += eps_lvl;
       const int Hn = H / 2 < 8 ? 8 : H / 2, Wn = W / 2 < 8 ? 8 : W / 2;      // storage of the next level (at least 8 wide)
       if (rec != nullptr) {
         RepairOp& op = rec->add(ROP_SQUEEZE);
@@ -1807,7 +1830,7 @@ static void launch_repair(const gbnf_image_flow* f, bool inverse, RepairArgs a, 
 
 // the launches of gbnf_image_flow_forward, every argument checked by the caller
 static int image_forward_launch(const char* fn, const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj,
-                                float* ll, void* workspace, void* stream);
+                                float* ll, void* workspace, void* stream, float* eps = nullptr);
 
 int gbnf_image_flow_forward(const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj,
                             float* ll, void* workspace, int64_t workspace_bytes, void* stream) {
@@ -1818,6 +1841,21 @@ int gbnf_image_flow_forward(const gbnf_image_flow* f, const float* x, const floa
   if (!x || !ldj || !workspace) return fail(GBNF_ERR_INVALID, "gbnf_image_flow_forward: x / ldj / workspace is null");
   if (const int rc = image_check_workspace("gbnf_image_flow_forward", f, n, workspace_bytes)) return rc;
   return image_forward_launch("gbnf_image_flow_forward", f, x, noise, n, z, ldj, ll, workspace, stream);
+}
+
+// gbnf_image_flow_forward with the Split2d halves kept: the same launches, the same numerics protocol, the split launches (and the
+// split ops of the repair programme) on the eps-storing epilogues.  No host read, no synchronisation, no allocation.
+int gbnf_image_flow_encode(const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* eps, float* ldj,
+                           float* ll, void* workspace, int64_t workspace_bytes, void* stream) {
+  const char* fn = "gbnf_image_flow_encode";
+  if (!f) return fail(GBNF_ERR_INVALID, "%s: flow is null", fn);
+  if (f->y_classes > 0 && ll) return fail(GBNF_ERR_INVALID, "%s: the handle is class-conditional: ll needs y (gbnf_image_flow_forward_y)", fn);
+  if (n < 0) return fail(GBNF_ERR_INVALID, "%s: n < 0", fn);
+  if (n == 0) return GBNF_OK;
+  if (!x || !z || !ldj || !workspace) return fail(GBNF_ERR_INVALID, "%s: x / z / ldj / workspace is null", fn);
+  if (f->L > 1 && !eps) return fail(GBNF_ERR_INVALID, "%s: %d Split2d level(s) need eps", fn, f->L - 1);
+  if (const int rc = image_check_workspace(fn, f, n, workspace_bytes)) return rc;
+  return image_forward_launch(fn, f, x, noise, n, z, ldj, ll, workspace, stream, f->L > 1 ? eps : nullptr);
 }
 
 // The handle's conditioning as the kernels of gbnf_image_ycond.hip take it
@@ -1932,18 +1970,18 @@ int gbnf_image_flow_prior_y(const gbnf_image_flow* f, const float* y, int64_t n,
 }
 
 static int image_forward_launch(const char* fn, const gbnf_image_flow* f, const float* x, const float* noise, int64_t n, float* z, float* ldj,
-                                float* ll, void* workspace, void* stream) {
+                                float* ll, void* workspace, void* stream, float* eps) {
   hipStream_t s = (hipStream_t)stream;
   float* ws = (float*)workspace;
   // exact f32: the handle's mode, or a split-f16 handle whose on-data check has failed (pinned word, no synchronisation)
   float* slots = image_batch_slots(f, ws, n);              // deterministic mode: the batch's log-det slot array (else null)
   if (f->math_mode != GBNF_MATH_F16X3 || f->on_data_demoted())
-    return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, true, nullptr, nullptr, nullptr, slots);
-  if (image_repair_mode() == 0) return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, nullptr, nullptr, nullptr, slots);
+    return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, true, nullptr, nullptr, nullptr, slots, eps);
+  if (image_repair_mode() == 0) return image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, nullptr, nullptr, nullptr, slots, eps);
   // ---- split-f16 pass with range marks; the on-data check (first launch, every check_every-th); the marked images on exact f32
   const RepairSpace r = repair_space(f, ws, n);
   if (hipMemsetAsync(r.mark, 0, (size_t)n * 4, s) != hipSuccess) return fail(GBNF_ERR_HIP, "%s: memset failed", fn);
-  const int rc = image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, r.mark, nullptr, nullptr, slots);
+  const int rc = image_forward_impl(f, x, noise, n, z, ldj, ll, ws, s, false, r.mark, nullptr, nullptr, slots, eps);
   if (rc) return rc;
   int32_t every = 256, tol_e9 = 2500;
   (void)gbnf_tuning_get("check_every", &every);
@@ -1952,7 +1990,7 @@ static int image_forward_launch(const char* fn, const gbnf_image_flow* f, const 
                      f->dev_state, f->host_words, (int)every);
   RepairArgs a{};
   a.mark = r.mark; a.ws = r.wsr;
-  a.x = x; a.noise = noise; a.z = z; a.ldj = ldj; a.ll = ll;
+  a.x = x; a.noise = noise; a.z = z; a.ldj = ldj; a.ll = ll; a.eps_out = eps;
   a.xchw = (int64_t)f->C * f->Hi * f->Wi; a.zsz = (int64_t)f->zC * f->zH * f->zW;      // (x and z have the map's own size)
   a.tol = 1e-9f * (float)tol_e9;
   a.check = 1; a.list = r.check_list; a.count = r.count + 1;

@@ -12,7 +12,10 @@ enum { EPI_RELU = 0, EPI_STORE = 1, EPI_COUPLE_AFFINE = 2, EPI_COUPLE_ADD = 3, E
        EPI_COUPLE_AFFINE_INV = 5, EPI_COUPLE_ADD_INV = 6, EPI_SPLIT_INV = 7,
        // the image trainer's deterministic mode: EPI_COUPLE_AFFINE / EPI_SPLIT whose waves STORE their log-det partials to per-image
        // slots (ConvLaunch::ldj, img_ldj_slots) instead of adding them into ldj[n]; img_launch_ldj_reduce adds the slots in order
-       EPI_COUPLE_AFFINE_ORD = 8, EPI_SPLIT_ORD = 9 };
+       EPI_COUPLE_AFFINE_ORD = 8, EPI_SPLIT_ORD = 9,
+       // gbnf_image_flow_encode: EPI_SPLIT / EPI_SPLIT_ORD that also STORE the standardised half the level drops,
+       // eps = (z2 - mean) * exp(-log-var) -- the exact inverse of EPI_SPLIT_INV at temperature 1 -- to ConvLaunch::eps
+       EPI_SPLIT_EPS = 10, EPI_SPLIT_EPS_ORD = 11 };
 
 struct NetLaunch {
   const float* pre_in;      // (n, *, H, W) f32: the coupling net's input z1
@@ -82,6 +85,8 @@ struct ConvLaunch {
   const float* pre_wp;    // packed 3x3 weights [cin/16 tiles][9][pre_kc][64][4]
   const float* pre_bias;
   int pre_cin;
+  float* eps;             // EPI_SPLIT_EPS*: this level's eps (n, cout/2, Hv, Wv) -- the map's own size, no storage padding --
+  int64_t eps_img;        //   first channel of image 0, and the floats between images; only pixels of the map proper are stored
 };
 
 // ---- the evaluation path's kernels as the training path (gbnf_image_train.hip) launches them; defined in gbnf_image.hip.

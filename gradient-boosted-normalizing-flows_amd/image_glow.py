@@ -876,6 +876,70 @@ class BoostedImageFlow(nn.Module):
         with torch.cuda.device(z.device):
             return handle.inverse(z.contiguous().float(), eps, temperature)
 
+    # ---- the component as the bijection it is: x -> (z, eps) -> x (gbnf_image_flow_encode / gbnf_image_flow_inverse) on the evaluation
+    # handles, no gradients.  ``noise`` None: no dequantisation noise is added (u = 255 x / 256), so the calls are deterministic.
+    def _latent_args(self, x, components, noise):
+        self._check(x)
+        c = self._sample_component(components) if isinstance(components, str) else int(components)
+        x = x.contiguous().float()
+        if noise is not None:
+            self._check(noise)
+            noise = noise.contiguous().float()
+        return c, x, noise
+
+    @torch.no_grad()
+    def encode_latent(self, x, components, noise=None):
+        """x (n,C,H,W) in [0,1] -> (z, eps) of one component: the top latent and the list of standardised halves its Split2d levels
+        drop (native.NativeImageFlow.encode), the form ``decode(z, eps=eps, temperature=1.0, components=c)`` takes back."""
+        c, x, noise = self._latent_args(x, components, noise)
+        with torch.cuda.device(x.device):
+            z, eps, _, _ = self.native_flow(c).encode(x, noise)
+        return z, eps
+
+    @torch.no_grad()
+    def reconstruct(self, x, components, noise=None):
+        """decode(encode_latent(x)) at temperature 1: the dequantised input u = (255 x + noise) / 256 to the rounding of the two passes."""
+        c, x, noise = self._latent_args(x, components, noise)
+        with torch.cuda.device(x.device):
+            handle = self.native_flow(c)
+            z, eps, _, _ = handle.encode(x, noise)
+            return handle.inverse(z, eps, 1.0)
+
+    @torch.no_grad()
+    def interpolate(self, x_a, x_b, weights, components, noise=None):
+        """Latent interpolation between two batches of images: (len(weights), n, C, H, W), entry k the decode at temperature 1 of
+        (1 - w_k) (z, eps)(x_a) + w_k (z, eps)(x_b) -- linear in the full latent; weights 0 and 1 return the two reconstructions."""
+        c, x_a, noise = self._latent_args(x_a, components, noise)
+        self._check(x_b)
+        x_b = x_b.contiguous().float()
+        if x_b.shape != x_a.shape:
+            raise ValueError(f"x_a and x_b must have one shape, got {tuple(x_a.shape)} and {tuple(x_b.shape)}")
+        with torch.cuda.device(x_a.device):
+            handle = self.native_flow(c)
+            za, ea, _, _ = handle.encode(x_a, noise)
+            zb, eb, _, _ = handle.encode(x_b, noise)
+            out = []
+            for w in weights:
+                w = float(w)
+                # (1 - w) a + w b, not a + w (b - a): the end points are the two latents bit for bit
+                out.append(handle.inverse((1.0 - w) * za + w * zb, [(1.0 - w) * p + w * q for p, q in zip(ea, eb)], 1.0))
+        return torch.stack(out) if out else x_a.new_empty((0,) + tuple(x_a.shape))
+
+    @torch.no_grad()
+    def round_trip_error(self, x, components=None, noise=None):
+        """The on-data invertibility check of both directions: per component max |decode(encode(x)) - u| with u = (255 x + noise) / 256,
+        a device tensor (no host read).  ``components``: an int, a sequence of ints, or None = every component."""
+        if components is None:
+            components = range(self.num_components)
+        elif isinstance(components, int):
+            components = [components]
+        errs = []
+        for c in components:
+            c, xx, nz = self._latent_args(x, int(c), noise)
+            u = (255.0 * xx + (nz if nz is not None else 0.0)) / 256.0
+            errs.append((self.reconstruct(xx, c, nz) - u).abs().amax() if xx.numel() else xx.new_zeros(()))
+        return torch.stack(errs) if errs else x.new_zeros(0, dtype=torch.float32)
+
     @torch.no_grad()
     def sample(self, n=None, *, temperature=1.0, n_used=None, e=None, eps=None, uniforms=None, generator=None, return_components=False,
                y_onehot=None):

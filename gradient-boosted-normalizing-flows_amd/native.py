@@ -63,6 +63,7 @@ ABI_SYMBOLS = (
     "gbnf_image_mixture_score_workspace_bytes", "gbnf_image_mixture_score",
     "gbnf_trainer_backward_x_workspace_bytes", "gbnf_trainer_backward_x", "gbnf_score_seed",
     "gbnf_mixture_score_workspace_bytes", "gbnf_mixture_score",
+    "gbnf_image_flow_encode",
 )
 
 
@@ -258,6 +259,7 @@ def lib():
     L.gbnf_image_trainer_apply_update.argtypes = [vp, vp, vp, vp, C.POINTER(_OptHyper), vp, vp]
     L.gbnf_image_trainer_nll_step.argtypes = [vp, vp, vp, i64, C.c_float, vp, vp, vp, C.POINTER(_OptHyper), vp, vp, i64, vp]
     L.gbnf_image_flow_inverse.argtypes = [vp, vp, vp, C.c_float, i64, vp, vp, i64, vp]
+    L.gbnf_image_flow_encode.argtypes = [vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
     L.gbnf_image_rho_step_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
     L.gbnf_image_mixture_rho_step.argtypes = [C.POINTER(vp), i32, vp, vp, i64, vp, C.c_float, vp, vp, vp, i64, vp]
     L.gbnf_image_boosted_step_workspace_bytes.argtypes = [vp, vp, i64, C.POINTER(i64)]
@@ -758,6 +760,42 @@ class NativeImageFlow:
                 out.append((c // 2, h, w))
                 c //= 2
         return out
+
+    def encode(self, x, noise=None, want_ll=False):
+        """gbnf_image_flow_encode: x (n,C,H,W) in [0,1] (+ dequantisation noise) -> (z, eps, ldj (n,), ll (n,) | None), the forward
+        with the half each Split2d level drops kept: ``eps`` is a list with one (n, C_l/2, H_l, W_l) tensor per entry of
+        ``split_shapes()`` (views of one allocation) -- the form ``inverse`` takes, so that ``inverse(z, eps, 1.0)`` returns the
+        dequantised input (255 x + noise) / 256.  A class-conditional handle is accepted without ``y`` (x -> z, eps, ldj does not
+        depend on it); its ll needs y, so ``want_ll`` raises there.  No gradient flows through the call.  Current stream."""
+        import torch
+        _require_device_f32(x, "x")
+        if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
+            raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        n = x.shape[0]
+        per = C.c_int64()
+        _check(lib().gbnf_image_flow_eps_floats(self.handle, C.byref(per)))
+        z = torch.empty((n,) + self.z_shape, dtype=torch.float32, device=x.device)
+        flat = torch.empty(per.value * n, dtype=torch.float32, device=x.device)
+        ldj = torch.empty(n, dtype=torch.float32, device=x.device)
+        ll = torch.empty(n, dtype=torch.float32, device=x.device) if want_ll else None
+        nb = C.c_int64()
+        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
+        if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
+            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+        # (ll asked of a class-conditional handle: the library refuses, nothing launched)
+        _check(lib().gbnf_image_flow_encode(self.handle, ptr(x.contiguous()), ptr(noise.contiguous() if noise is not None else None), n,
+                                            ptr(z), ptr(flat), ptr(ldj), ptr(ll), ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+        eps, off = [], 0
+        for sh in self.split_shapes():
+            k = n * sh[0] * sh[1] * sh[2]
+            eps.append(flat[off:off + k].view((n,) + sh))
+            off += k
+        return z, eps, ldj, ll
 
     def inverse(self, z, eps=None, temperature=1.0):
         """z (n,Cz,Hz,Wz) -> x (n,C,H,W): the reference's Glow.decode(z, None, temperature) (gbnf_image_flow_inverse).

@@ -788,6 +788,22 @@ int gbnf_image_flow_actnorm_stats(const gbnf_image_flow* flow, const float* x, c
 int gbnf_image_flow_eps_floats(const gbnf_image_flow* flow, int64_t* per_image);
 int gbnf_image_flow_inverse(const gbnf_image_flow* flow, const float* z, const float* eps, float temperature, int64_t n,
                             float* x, void* workspace, int64_t workspace_bytes, void* stream);
+/* The full-latent x -> (z, eps) direction: gbnf_image_flow_forward that KEEPS the half each Split2d level drops instead of only
+ * folding its density into ldj.  x, noise, z, ldj, ll, the workspace (gbnf_image_flow_workspace_bytes: unchanged, eps goes straight
+ * to the caller's buffer) and the numerics protocol are those of gbnf_image_flow_forward; z and ldj are required here.
+ * eps: gbnf_image_flow_eps_floats() floats per image in the layout gbnf_image_flow_inverse reads -- level 0 first, each level a
+ * contiguous (n, C_l/2, H_l, W_l) array of the map's own size -- holding eps = (z2 - mean) * exp(-log-var) with (mean, log-var) =
+ * split_prior(z1) (models/layers.py:689-703), the exact algebraic inverse of Split2d's reverse at temperature 1; may be NULL
+ * only for a one-level flow.  Contract: gbnf_image_flow_inverse(z, eps, temperature = 1) on this call's outputs returns the
+ * dequantised input u = (255 x + noise) / 256 (to the rounding of the two passes).  A caller who wants another temperature
+ * divides eps.  An image that the split-f16 pass marks out of range, and every image of a call whose on-data check failed, gets its
+ * eps from the exact-f32 sequence in the same call, like its z / ldj / ll.  Deterministic mode (gbnf_image_flow_set_deterministic)
+ * is honoured (ordered log-det sums); z and eps are identical in both modes.  A class-conditional handle is accepted, since
+ * x -> (z, eps, ldj) does not depend on y; on such a handle ll must be NULL (it needs y: GBNF_ERR_INVALID otherwise).
+ * GBNF_ERR_INVALID before any launch: null flow / x / z / ldj / workspace, null eps on a multi-level flow, a short workspace,
+ * n < 0.  n == 0: GBNF_OK.  No host read, no synchronisation, no allocation: the call can be captured in a graph. */
+int gbnf_image_flow_encode(const gbnf_image_flow* flow, const float* x, const float* noise, int64_t n, float* z, float* eps,
+                           float* ldj, float* ll_or_null, void* workspace, int64_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------------------------
  * Training path of ONE image Glow component: the forward on the LIVE parameters and its backward pass, exact f32
