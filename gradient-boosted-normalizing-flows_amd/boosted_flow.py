@@ -1195,6 +1195,50 @@ class BoostedFlow(nn.Module):
             G, _ = self.native_mixture(n_used).log_prob(x, self.rho.contiguous().float(), n_used=n_used)
         return G
 
+    @torch.no_grad()
+    def evaluate(self, data_loader, n_used=None):
+        """density_experiment.py:544-603, the boosted branch, on the device: per batch of a loader of ``(x, _)`` ONE library call
+        (gbnf_mixture_evaluate: one flow launch for components [0, n_used), the recursion and the running sums in a device state),
+        and ONE host read after the last batch -- where the reference runs ``component + 1`` module forwards for G and a further one
+        for g per batch, a ``torch.cat`` over the whole set and ``.mean().item()``.  Puts the module in eval mode.  -> dict of floats:
+          nll, g_nll, ratio          the reference's three (:582-591; ratio = mean(g_nll - G_nll); with ``component == 0 and not
+                                     all_trained``: g_nll = nll, ratio = 0.0); g is ``self.component``
+          expected_component_nll     -mean_i sum_c w_c ll_c(x_i), w = rho[:n_used] / sum: what drawing components "1:c" estimates
+          nll_batch_mean             the mean over batches of the batch means of G_nll (the form of the non-boosted branch, :594)
+          rows, batches, non_finite_rows
+        Default ``n_used`` as ``log_prob`` (all components once ``all_trained``; pass ``component + 1`` for the reference's range).
+        An empty loader raises ValueError."""
+        self.eval()
+        n_used = self._n_used(n_used)
+        c = int(self.component)
+        if c >= n_used:
+            raise ValueError(f"component {c} is not among the first n_used = {n_used} components")
+        dev = self.rho.device
+        rho = self.rho.contiguous().float()
+        state = None
+        for (x, _) in data_loader:
+            x = x.detach().to(dev)
+            self._check_ready(x)
+            x = x.contiguous().float()
+            for k in range(n_used):
+                self._ensure_actnorm(x, k)
+            self._guard(x, range(n_used))
+            with torch.cuda.device(x.device):
+                if state is None:
+                    state = native.eval_state(x.device)
+                self.native_mixture(n_used).evaluate(x, c, rho, state, n_used=n_used)
+        s = None if state is None else state.tolist()          # the one host read
+        if s is None or s[0] == 0:
+            raise ValueError("evaluate: the loader yielded no rows")
+        S = native.EVAL_STATE
+        rows, batches = s[S["rows"]], s[S["batches"]]
+        out = {"nll": -s[S["sum_G"]] / rows, "g_nll": -s[S["sum_g"]] / rows, "ratio": s[S["sum_G_minus_g"]] / rows,
+               "expected_component_nll": -s[S["sum_E"]] / rows, "nll_batch_mean": -s[S["batch_mean_G"]] / batches,
+               "rows": int(rows), "batches": int(batches), "non_finite_rows": int(s[S["non_finite_rows"]])}
+        if c == 0 and not self.all_trained:
+            out["g_nll"], out["ratio"] = out["nll"], 0.0
+        return out
+
     # ---- the score: grad_x log p(x) of a component and of the mixture (gbnf_mixture_score), eval or train mode alike
     def _score_input(self, x, comps):
         self._check_ready(x)

@@ -194,6 +194,11 @@ def main(argv=None):
     objs.append(iboost_o)
     if args.force or not newer(iboost_o, [iboost_src, opt_hdr, os.path.join(HERE, "gbnf_image_train.h"), hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", iboost_src, "-o", iboost_o])
+    # the validation pass (running sums of a loader's log-likelihoods and class loss in a device state, the one-call forms): gbnf_eval.hip
+    eval_o, eval_src = os.path.join(OBJ, "gbnf_eval.o"), os.path.join(HERE, "gbnf_eval.hip")
+    objs.append(eval_o)
+    if args.force or not newer(eval_o, [eval_src, hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", eval_src, "-o", eval_o])
     for v in read_variants():
         o = os.path.join(OBJ, "v_" + "_".join(str(a) for a in v) + ".o")
         objs.append(o)

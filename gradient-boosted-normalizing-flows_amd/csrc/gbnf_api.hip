@@ -1469,18 +1469,7 @@ __global__ void __launch_bounds__(256) mixture_lse_kernel(const float* __restric
                                                           float* __restrict__ out) {
   const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (idx >= n) return;
-  float G = ll[idx];
-  float rsum = rho[0];
-  for (int c = 1; c < n_comp; ++c) {
-    rsum += rho[c];
-    const float r = rho[c] / rsum;
-    const float a = logf(1.0f - r) + G;
-    const float b = logf(r) + ll[(int64_t)c * stride + idx];
-    float m = fmaxf(a, b);
-    if (isinf(m)) m = 0.0f;
-    G = m + logf(expf(a - m) + expf(b - m));
-  }
-  out[idx] = G;
+  out[idx] = mixture_lse_row(ll, stride, rho, n_comp, idx);      // (gbnf_internal.h: shared with gbnf_eval.hip)
 }
 
 // Bayes' rule over the classes of a generative classifier, a wave per row (4 rows per workgroup), lanes strided over the classes:

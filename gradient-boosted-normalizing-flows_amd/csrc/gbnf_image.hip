@@ -1174,6 +1174,8 @@ int gbnf::image_flow_input_shape(const gbnf_image_flow* f, int* channels, int* h
   return GBNF_OK;
 }
 
+bool gbnf::image_flow_has_class_head(const gbnf_image_flow* f) { return f != nullptr && f->y_classes != 0 && f->y_head; }
+
 extern "C" {
 
 #ifdef GBNF_IMG_STAMPS

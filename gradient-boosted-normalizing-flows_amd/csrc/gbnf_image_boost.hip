@@ -111,8 +111,8 @@ static int check_fixed_image(const char* fn, const gbnf_image_flow* fixed, const
   return GBNF_OK;
 }
 
-// handles [0, n_flows) are non-null and take images of one shape
-static int check_image_flows(const char* fn, const gbnf_image_flow* const* flows, int n_flows) {
+// handles [0, n_flows) are non-null and take images of one shape  (gbnf_internal.h: shared with gbnf_eval.hip)
+int check_image_flows(const char* fn, const gbnf_image_flow* const* flows, int n_flows) {
   int C0 = 0, H0 = 0, W0 = 0;
   for (int c = 0; c < n_flows; ++c) {
     if (!flows[c]) return fail(GBNF_ERR_INVALID, "%s: flows[%d] is null", fn, c);
@@ -122,6 +122,28 @@ static int check_image_flows(const char* fn, const gbnf_image_flow* const* flows
     else if (C != C0 || H != H0 || W != W0)
       return fail(GBNF_ERR_INVALID, "%s: flows[%d] takes %d x %d x %d images, flows[0] %d x %d x %d", fn, c, C, H, W, C0, H0, W0);
   }
+  return GBNF_OK;
+}
+
+// with_y false: every handle is plain;  true: every handle is conditioned, all on one class count (*y_classes_out, may be null)
+// (gbnf_internal.h: shared with gbnf_eval.hip)
+int check_image_flows_y(const char* fn, const gbnf_image_flow* const* flows, int n_flows, bool with_y, int32_t* y_classes_out) {
+  int32_t Y0 = 0;
+  for (int c = 0; c < n_flows; ++c) {
+    int32_t y_classes = 0;
+    if (const int rc = gbnf_image_flow_y_classes(flows[c], &y_classes)) return rc;
+    if (!with_y) {
+      if (y_classes != 0)
+        return fail(GBNF_ERR_INVALID, "%s: flows[%d] is class-conditional (%d classes) and needs y: this call takes none (the _y call does)", fn,
+                    c, (int)y_classes);
+      continue;
+    }
+    if (y_classes == 0) return fail(GBNF_ERR_INVALID, "%s: flows[%d] has no conditioning set (gbnf_image_flow_set_ycond)", fn, c);
+    if (c == 0) Y0 = y_classes;
+    else if (y_classes != Y0)
+      return fail(GBNF_ERR_INVALID, "%s: flows[%d] has %d classes, flows[0] %d: y has one width", fn, c, (int)y_classes, (int)Y0);
+  }
+  if (y_classes_out) *y_classes_out = Y0;
   return GBNF_OK;
 }
 
@@ -162,21 +184,7 @@ static int image_rho_step(const char* fn, const gbnf_image_flow* const* flows, i
   if (n < 1) return fail(GBNF_ERR_INVALID, "%s: n = %lld (must be >= 1)", fn, (long long)n);
   const int n_flows = (int)component + 1;
   if (const int rc = check_image_flows(fn, flows, n_flows)) return rc;
-  int32_t Y0 = 0;
-  for (int c = 0; c < n_flows; ++c) {    // refused HERE, before the first component's launches
-    int32_t y_classes = 0;
-    if (const int rc = gbnf_image_flow_y_classes(flows[c], &y_classes)) return rc;
-    if (!with_y) {
-      if (y_classes != 0)
-        return fail(GBNF_ERR_INVALID, "%s: flows[%d] is class-conditional (%d classes) and needs y: the rho update has no such call", fn, c,
-                    (int)y_classes);
-      continue;
-    }
-    if (y_classes == 0) return fail(GBNF_ERR_INVALID, "%s: flows[%d] has no conditioning set (gbnf_image_flow_set_ycond)", fn, c);
-    if (c == 0) Y0 = y_classes;
-    else if (y_classes != Y0)
-      return fail(GBNF_ERR_INVALID, "%s: flows[%d] has %d classes, flows[0] %d: y has one width", fn, c, (int)y_classes, (int)Y0);
-  }
+  if (const int rc = check_image_flows_y(fn, flows, n_flows, with_y, nullptr)) return rc;    // refused HERE, before the first component's launches
   int64_t flow_bytes = 0, total = 0;
   if (const int rc = image_rho_layout(flows, n_flows, n, &flow_bytes, &total)) return rc;
   if (workspace_bytes < total)

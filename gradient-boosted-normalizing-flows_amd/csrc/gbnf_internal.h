@@ -32,6 +32,33 @@ int rho_update_launch(const char* fn, const float* ll, int64_t n, int component,
                       hipStream_t s);
 // The input proper of an image evaluation handle (channels, height, width), for gbnf_image_boost.hip (gbnf_image.hip)
 int image_flow_input_shape(const gbnf_image_flow* f, int* channels, int* height, int* width);
+// Whether a conditioned handle was given project_class (it can write y_logits), for gbnf_eval.hip (gbnf_image.hip)
+bool image_flow_has_class_head(const gbnf_image_flow* f);
+// What gbnf_image_mixture_rho_step checks of its handles before the first launch, for the calls built like it (gbnf_eval.hip):
+// handles [0, n_flows) non-null and of one input shape;  with_y false: every handle plain, true: every handle conditioned on one
+// class count (*y_classes, may be null)  (gbnf_image_boost.hip)
+int check_image_flows(const char* fn, const gbnf_image_flow* const* flows, int n_flows);
+int check_image_flows_y(const char* fn, const gbnf_image_flow* const* flows, int n_flows, bool with_y, int32_t* y_classes);
+
+// One row of the mixture recursion  G_0 = ll_0;  r_c = rho_c / sum(rho[0..c]);  G_c = LSE2(log(1 - r_c) + G_{c-1}, log r_c + ll_c)
+// (density_experiment.py:567-571) in float32 with torch.logsumexp's semantics for the 2-way LSE: the body of mixture_lse_kernel
+// (gbnf_api.hip), shared with eval_partial_kernel (gbnf_eval.hip) so that both give the same bits.  The rho prefix sums are
+// recomputed per thread (C is tiny, the loads are wave-uniform).
+__device__ __forceinline__ float mixture_lse_row(const float* __restrict__ ll, int64_t stride, const float* __restrict__ rho, int n_comp,
+                                                 int64_t idx) {
+  float G = ll[idx];
+  float rsum = rho[0];
+  for (int c = 1; c < n_comp; ++c) {
+    rsum += rho[c];
+    const float r = rho[c] / rsum;
+    const float a = logf(1.0f - r) + G;
+    const float b = logf(r) + ll[(int64_t)c * stride + idx];
+    float m = fmaxf(a, b);
+    if (isinf(m)) m = 0.0f;
+    G = m + logf(expf(a - m) + expf(b - m));
+  }
+  return G;
+}
 
 // Kernel-variant key only (not a descriptor value): the activation differs between the steps / nets of a component
 // (`--coupling_network random` in the reference); the kernel reads it per step and net from the step header.

@@ -18,6 +18,8 @@ does (models/layers.py:473-486) -- or by loading a trained checkpoint / ``set_ac
 """
 from __future__ import annotations
 
+import math
+
 import numpy as np
 import torch
 import torch.nn as nn
@@ -1368,6 +1370,80 @@ class BoostedImageFlow(nn.Module):
             torch.autograd.graph.increment_version([rho])
             if batch_id > min_iters and (batch_id > max_iters or stats.tolist()[3] < tolerance):
                 break
+
+    # ---- the validation pass (image_experiment.py:296-337)
+    @torch.no_grad()
+    def evaluate(self, data_loader, noise_generator=None, labels=False, n_used=None, y_weight=None):
+        """image_experiment.py:296-337 for a boosted model, on the device: per batch the forwards of components [0, n_used), the
+        recursion and the running sums in a device state, and ONE host read after the last batch.  A plain model's component chains
+        overlap on their own streams as in ``component_log_prob`` and gbnf_eval_accumulate follows on the current stream; with
+        ``labels`` a batch is ONE library call (gbnf_image_mixture_evaluate_y, the chains one after the other).  The reference estimates its loss from ``3 num_components`` forwards of components drawn with ``"1:c"`` per batch
+        and reads it back per batch; here every component runs once and the draw is replaced by its expectation under
+        w = rho[:n_used] / sum.  The loader yields ``(x, _)`` with x in [0, 1]; the dequantisation noise is one
+        ``torch.rand(x.shape, generator=noise_generator)`` draw on the device per batch, the same for every component, as in
+        ``update_rho``.  Default ``n_used``: all components once ``all_trained``, else ``component + 1`` -- what ``"1:c"`` draws
+        from.  Puts the module in eval mode.  -> dict of floats, with D = C H W pixels:
+          bpd                        the mixture's bits per dimension, -mean(G_ll) / (ln2 D)
+          g_bpd                      those of component ``self.component``
+          expected_component_bpd     -mean_i sum_c w_c ll_c(x_i) / (ln2 D)
+          loss                       the expectation of the reference's ``avg_loss``: the mean over batches of
+                                     sum_c w_c bpd_c + y_weight sum_c w_c CE_c  (the second term only with ``labels``)
+          rows, batches, non_finite_rows
+        ``labels=True`` (a class-conditional model): the loader yields ``(x, y_onehot (N, y_classes))``, every batch is one
+        gbnf_image_mixture_evaluate_y call, and the dict also has ``loss_classes`` (the rho-weighted mean cross-entropy of
+        image_experiment.py:236), ``accuracy`` (the rho-weighted share of rows whose largest logit is the label) and
+        ``total_loss = bpd + y_weight loss_classes``.  ``y_weight`` defaults to ``args.y_weight``, else 0.01.  The ``multi_class``
+        branch of the reference's loss is not built.  An empty loader raises ValueError."""
+        if labels:
+            self._conditioned("evaluate(labels=True)")
+        elif self.flows[0].y_condition:
+            raise NotImplementedError("evaluate of a class-conditional model needs the rows' labels: gbnf_image_mixture_evaluate takes "
+                                      "no y (pass labels=True and a loader of (x, y_onehot))")
+        self.eval()
+        if n_used is None:
+            n_used = self.num_components if self.all_trained else self.component + 1
+        n_used, c = int(n_used), int(self.component)
+        if not 1 <= n_used <= self.num_components:
+            raise ValueError(f"n_used={n_used} outside [1, {self.num_components}]")
+        if c >= n_used:
+            raise ValueError(f"component {c} is not among the first n_used = {n_used} components")
+        if y_weight is None:
+            y_weight = getattr(self.args, "y_weight", None)
+        y_weight = 0.01 if y_weight is None else float(y_weight)
+        rho = self.rho
+        if rho.dtype != torch.float32 or not rho.is_contiguous():
+            rho = rho.contiguous().float()
+        state, pixels = None, 0
+        for (x, y) in data_loader:
+            x = x.detach().to(rho.device).contiguous().float()
+            self._check(x)
+            y = self._y(0, None if y is None else y.detach().to(rho.device), x.shape[0]) if labels else None
+            noise = torch.rand(x.shape, generator=noise_generator, device=x.device)
+            with torch.cuda.device(x.device):
+                if state is None:
+                    state, pixels = native.eval_state(x.device), int(x[0].numel())
+                if y is None:
+                    # a plain model's chains overlap on the components' own streams (component_log_prob): a pass of 8 batches of 64
+                    # through a CIFAR-shaped C = 4 model measured 12.1 ms this way and 15.7 ms with the one call's chains one after
+                    # the other (DESIGN.md section 4.7); the sums are the one call's: the same two launches on the same table
+                    native.eval_accumulate(self.component_log_prob(x, n_used, noise).t().contiguous(), rho, c, state)
+                else:
+                    native.NativeImageFlow.evaluate([self.native_flow(k) for k in range(n_used)], x, noise, c, rho, state, y=y)
+        s = None if state is None else state.tolist()          # the one host read
+        if s is None or s[0] == 0:
+            raise ValueError("evaluate: the loader yielded no rows")
+        S = native.EVAL_STATE
+        rows, batches = s[S["rows"]], s[S["batches"]]
+        per_dim = 1.0 / (math.log(2.0) * pixels)
+        out = {"bpd": -s[S["sum_G"]] / rows * per_dim, "g_bpd": -s[S["sum_g"]] / rows * per_dim,
+               "expected_component_bpd": -s[S["sum_E"]] / rows * per_dim, "loss": -s[S["batch_mean_E"]] / batches * per_dim,
+               "rows": int(rows), "batches": int(batches), "non_finite_rows": int(s[S["non_finite_rows"]])}
+        if labels:
+            out["loss"] += y_weight * s[S["batch_mean_ce"]] / batches
+            out["loss_classes"] = s[S["sum_ce"]] / rows
+            out["accuracy"] = s[S["sum_correct"]] / rows
+            out["total_loss"] = out["bpd"] + y_weight * out["loss_classes"]
+        return out
 
     # ---- checkpoint side-car (SURVEY.md S5 for image components)
     def _side_car_modules(self, c):

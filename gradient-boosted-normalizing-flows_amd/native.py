@@ -64,7 +64,17 @@ ABI_SYMBOLS = (
     "gbnf_trainer_backward_x_workspace_bytes", "gbnf_trainer_backward_x", "gbnf_score_seed",
     "gbnf_mixture_score_workspace_bytes", "gbnf_mixture_score",
     "gbnf_image_flow_encode",
+    "gbnf_eval_workspace_bytes", "gbnf_eval_accumulate", "gbnf_eval_accumulate_class_loss", "gbnf_mixture_evaluate",
+    "gbnf_image_mixture_evaluate_workspace_bytes", "gbnf_image_mixture_evaluate", "gbnf_image_mixture_evaluate_y",
 )
+
+# the evaluation state of the validation pass (include/gbnf.h: GBNF_EVAL_STATE_DOUBLES and its layout)
+EVAL_STATE_DOUBLES = 16
+EVAL_STATE = {"rows": 0, "batches": 1, "sum_G": 2, "sum_g": 3, "sum_G_minus_g": 4, "sum_E": 5, "batch_mean_G": 6, "batch_mean_g": 7,
+              "batch_mean_E": 8, "non_finite_rows": 9, "sum_ce": 10, "batch_mean_ce": 11, "sum_correct": 12}
+# the grid of the accumulate kernels: min(ceil(n / EVAL_ROWS_PER_WORKGROUP), EVAL_MAX_PARTIALS) workgroups, a grid-stride loop beyond
+EVAL_ROWS_PER_WORKGROUP = 1024
+EVAL_MAX_PARTIALS = 256
 
 
 class GbnfError(RuntimeError):
@@ -290,6 +300,13 @@ def lib():
     L.gbnf_score_seed.argtypes = [vp, vp, vp, vp, i64, i32, vp, vp, vp, vp]
     L.gbnf_mixture_score_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
     L.gbnf_mixture_score.argtypes = [C.POINTER(vp), i32, vp, vp, vp, vp, vp, i64, vp, vp, vp, vp, i64, vp]
+    L.gbnf_eval_workspace_bytes.argtypes = [i64, C.POINTER(i64)]
+    L.gbnf_eval_accumulate.argtypes = [vp, i64, i32, i64, vp, i32, vp, vp, vp, i64, vp]
+    L.gbnf_eval_accumulate_class_loss.argtypes = [vp, vp, i64, i32, vp, i32, i32, vp, vp, i64, vp]
+    L.gbnf_mixture_evaluate.argtypes = [vp, vp, i64, i32, i32, vp, vp, vp, vp, vp, i64, vp]
+    L.gbnf_image_mixture_evaluate_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
+    L.gbnf_image_mixture_evaluate.argtypes = [C.POINTER(vp), i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
+    L.gbnf_image_mixture_evaluate_y.argtypes = [C.POINTER(vp), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -879,6 +896,56 @@ class NativeImageFlow:
         _check(lib().gbnf_image_mixture_rho_step(handles, component, ptr(x), ptr(noise), n, ptr(rho), float(step_size), ptr(table),
                                                  ptr(stats), ptr(ws), ws.numel() * 4, _stream_ptr()))
         return stats
+
+    _eval_ws = {}      # device -> workspace of evaluate (grown to the largest call so far)
+    _eval_ll = {}      # device -> the (n_used, n) table of the last evaluate call (kept while the size repeats)
+
+    @staticmethod
+    def evaluate(flows, x, noise, component, rho, state, y=None):
+        """One batch of the validation pass over image components on the device (gbnf_image_mixture_evaluate): the forwards of
+        ``flows`` (``NativeImageFlow`` handles in component order: all of them are used, the same ``noise`` for all, None = none) one
+        after another on the current stream, then the running sums of ``eval_accumulate`` with ``g = flows[component]`` ADDED into
+        ``state`` (``eval_state``).  ``y`` (n, Y) for class-conditional handles (gbnf_image_mixture_evaluate_y: every component's ll under
+        its prior of each row's y, and every component's share of the class loss into entries 10 - 12).  -> the call's (len(flows), n)
+        log-likelihood table: scratch that is kept while the size repeats, so the next call of that size overwrites it."""
+        import torch
+        flows, component = list(flows), int(component)
+        if not flows or not 0 <= component < len(flows):
+            raise GbnfError(f"evaluate needs handles of components 0 .. n_used - 1 and 0 <= component < n_used, got component = {component} "
+                            f"and {len(flows)} handle(s)")
+        _require_device_f32(x, "x")
+        _require_device_f32(rho, "rho")
+        _require_eval_state(state)
+        if x.dim() != 4 or x.shape[0] < 1 or any(tuple(x.shape[1:]) != f.input_size for f in flows):
+            raise GbnfError(f"x must be (n,{flows[0].input_size}) with n >= 1 for every handle, got {tuple(x.shape)}")
+        if noise is not None:
+            _require_device_f32(noise, "noise")
+            if noise.shape != x.shape:
+                raise GbnfError("noise must have the shape of x")
+        if rho.dim() != 1 or rho.numel() < len(flows):
+            raise GbnfError("rho is shorter than the handle list")
+        n = x.shape[0]
+        if y is not None:                       # (plain handles among them, two class counts, no head: the library refuses, nothing launched)
+            _require_device_f32(y, "y")
+            if y.dim() != 2 or y.shape[0] != n or y.shape[1] != max(int(f.y_classes) for f in flows):
+                raise GbnfError(f"y must be ({n}, y_classes), got {tuple(y.shape)}")
+        handles = (C.c_void_p * len(flows))(*[f.handle.value for f in flows])
+        nb = C.c_int64()
+        _check(lib().gbnf_image_mixture_evaluate_workspace_bytes(handles, len(flows), n, C.byref(nb)))
+        ws = NativeImageFlow._eval_ws.get(x.device)
+        if ws is None or ws.numel() * 4 < nb.value:
+            ws = NativeImageFlow._eval_ws[x.device] = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        table = NativeImageFlow._eval_ll.get(x.device)
+        if table is None or tuple(table.shape) != (len(flows), n):
+            table = NativeImageFlow._eval_ll[x.device] = torch.empty((len(flows), n), dtype=torch.float32, device=x.device)
+        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        if y is not None:
+            _check(lib().gbnf_image_mixture_evaluate_y(handles, len(flows), component, ptr(x), ptr(noise), ptr(y), n, ptr(rho), ptr(table),
+                                                       None, ptr(state), ptr(ws), ws.numel() * 4, _stream_ptr()))
+            return table
+        _check(lib().gbnf_image_mixture_evaluate(handles, len(flows), component, ptr(x), ptr(noise), n, ptr(rho), ptr(table), None,
+                                                 ptr(state), ptr(ws), ws.numel() * 4, _stream_ptr()))
+        return table
 
     def close(self):
         if getattr(self, "handle", None):
@@ -2043,6 +2110,35 @@ class NativeMixture:
                                            _stream_ptr()))
         return stats
 
+    def evaluate(self, x, component, rho, state, n_used=None, want_G=False):
+        """One batch of the validation pass on the device (gbnf_mixture_evaluate): the log-densities of components [0, n_used) in ONE
+        flow launch, then the running sums of ``eval_accumulate`` with ``g = component`` ADDED into ``state`` (``eval_state``); no
+        host read.  -> G (n,) with ``want_G``, else None.  The (n_used, n) table of the call stays in ``self.eval_ll``: scratch kept
+        on the handle while the size repeats, so the next call of that size overwrites it."""
+        import torch
+        _require_device_f32(x, "x")
+        _require_device_f32(rho, "rho")
+        _require_eval_state(state)
+        n_used = self.n_components if n_used is None else int(n_used)
+        if x.dim() != 2 or x.shape[1] != self.d:
+            raise GbnfError(f"x must be (n,{self.d}), got {tuple(x.shape)}")
+        if rho.dim() != 1 or rho.numel() < n_used:
+            raise GbnfError("rho shorter than n_used")
+        n = x.shape[0]
+        table = getattr(self, "eval_ll", None)
+        if table is None or tuple(table.shape) != (n_used, n) or table.device != x.device:
+            table = self.eval_ll = torch.empty((n_used, n), dtype=torch.float32, device=x.device)
+        ws = _eval_workspace(x.device, n)
+        G = torch.empty(n, dtype=torch.float32, device=x.device) if want_G else None
+        if not 0 <= int(component) < n_used:
+            raise GbnfError(f"component = {component} outside [0, {n_used})")
+        if n == 0:                              # (an empty batch adds nothing, `batches` included: there is nothing to launch)
+            return G
+        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+        _check(lib().gbnf_mixture_evaluate(self.handle, ptr(x), n, n_used, int(component), ptr(rho), ptr(table), ptr(G), ptr(state), ptr(ws),
+                                           ws.numel() * ws.element_size(), _stream_ptr()))
+        return G
+
     def close(self):
         if getattr(self, "handle", None):
             lib().gbnf_mixture_destroy(self.handle)
@@ -2196,6 +2292,81 @@ def mixture_lse(ll, rho, out=None):
     _check(lib().gbnf_mixture_lse(C.c_void_p(ll.data_ptr() if n else 0), n, C.c_void_p(rho.data_ptr()), c, n,
                                   C.c_void_p(out.data_ptr() if n else 0), _stream_ptr()))
     return out
+
+
+# ---- the validation pass: running sums of a loader's batches in a device state (gbnf_eval_accumulate and the calls around it)
+def eval_state(device):
+    """A zeroed evaluation state: ``EVAL_STATE_DOUBLES`` float64 on ``device`` (layout: ``EVAL_STATE`` / include/gbnf.h).  The
+    evaluate calls only ever add to it; read it once after the last batch."""
+    import torch
+    return torch.zeros(EVAL_STATE_DOUBLES, dtype=torch.float64, device=device)
+
+
+def _require_eval_state(state):
+    import torch
+    if not isinstance(state, torch.Tensor) or not state.is_cuda or state.dtype != torch.float64 or not state.is_contiguous() \
+            or state.numel() < EVAL_STATE_DOUBLES:
+        raise GbnfError(f"state must be a contiguous float64 device tensor of {EVAL_STATE_DOUBLES} entries (native.eval_state)")
+    return state
+
+
+_eval_ws = {}      # device -> the partial-sum scratch of the accumulate calls
+
+
+def _eval_workspace(device, n):
+    import torch
+    nb = C.c_int64()
+    _check(lib().gbnf_eval_workspace_bytes(n, C.byref(nb)))
+    ws = _eval_ws.get(device)
+    if ws is None or ws.numel() * 8 < nb.value:
+        ws = _eval_ws[device] = torch.empty((nb.value + 7) // 8, dtype=torch.float64, device=device)
+    return ws
+
+
+def eval_accumulate(ll, rho, component, state, want_G=False, workspace=None):
+    """gbnf_eval_accumulate: the sums of one batch's (n_used, n) table ``ll`` of per-component log-likelihoods (float32 on the device,
+    unit column stride; the rows may be strided) ADDED into ``state``: rows, batches, sum G_ll (the recursion of ``mixture_lse``, bit
+    for bit), sum g_ll (row ``component``), sum (G_ll - g_ll), sum E_ll (the rho-weighted mean of the rows), their batch means, the
+    non-finite rows.  Two launches, no host read.  -> G (n,) with ``want_G``, else None.  ``workspace``: a float64 device tensor of
+    gbnf_eval_workspace_bytes (default: one per device, so calls on one device must not run on two streams at once)."""
+    import torch
+    if not isinstance(ll, torch.Tensor) or not ll.is_cuda or ll.dtype != torch.float32 or ll.dim() != 2 or (ll.shape[1] > 1 and ll.stride(1) != 1):
+        raise GbnfError("ll must be a (n_used, n) float32 device table with unit column stride")
+    _require_device_f32(rho, "rho")
+    _require_eval_state(state)
+    n_used, n = ll.shape
+    if rho.dim() != 1 or rho.numel() < n_used:
+        raise GbnfError("rho shorter than the number of components")
+    stride = ll.stride(0) if n_used > 1 else max(n, 1)
+    ws = _eval_workspace(ll.device, n) if workspace is None else workspace
+    G = torch.empty(n, dtype=torch.float32, device=ll.device) if want_G else None
+    if n == 0 and 0 <= int(component) < n_used:      # (an empty table has no address to hand over; the library adds nothing for it)
+        return G
+    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
+    _check(lib().gbnf_eval_accumulate(ptr(ll), stride, n_used, n, ptr(rho), int(component), ptr(G), ptr(state), ptr(ws),
+                                      ws.numel() * ws.element_size(), _stream_ptr()))
+    return G
+
+
+def eval_accumulate_class_loss(y_logits, y, rho, c, state, n_used=None, workspace=None):
+    """gbnf_eval_accumulate_class_loss: component ``c``'s share of the class loss of one batch ADDED into entries 10 - 12 of ``state``:
+    with w = rho[c] / sum(rho[:n_used]),  w sum_i CE_i,  w mean_i CE_i  and  w #{argmax logits_i == argmax y_i}, where
+    CE_i = logsumexp(y_logits_i) - y_logits_i[argmax y_i] in float64 (F.cross_entropy(y_logits, argmax(y)); the first largest entry
+    wins both argmaxes).  y_logits, y: (n, Y) float32 on the device, 1 <= Y <= 256.  ``n_used`` defaults to ``rho.numel()``."""
+    _require_device_f32(y_logits, "y_logits")
+    _require_device_f32(y, "y")
+    _require_device_f32(rho, "rho")
+    _require_eval_state(state)
+    if y_logits.dim() != 2 or y.shape != y_logits.shape:
+        raise GbnfError("y_logits and y must both be (n, Y)")
+    n, Y = y_logits.shape
+    n_used = rho.numel() if n_used is None else int(n_used)
+    if rho.dim() != 1 or rho.numel() < n_used:
+        raise GbnfError("rho shorter than n_used")
+    ws = _eval_workspace(y.device, n) if workspace is None else workspace
+    ptr = lambda t: C.c_void_p(t.data_ptr())
+    _check(lib().gbnf_eval_accumulate_class_loss(ptr(y_logits), ptr(y), n, Y, ptr(rho), n_used, int(c), ptr(state), ptr(ws),
+                                                 ws.numel() * ws.element_size(), _stream_ptr()))
 
 
 def class_posterior(class_ll, log_prior=None, want_post=True, want_pred=False):

@@ -1195,6 +1195,77 @@ int gbnf_mixture_sample_begin(const float* rho_dev, int32_t n_used, const float*
 int gbnf_mixture_sample_finish(gbnf_flow* const* flows, int32_t n_flows, const int64_t* counts_host, const int64_t* order, int64_t n,
                                float* x, float* ldj_or_null, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- the validation pass ---------------------------------------------------------------------------------------------------------
+ * Replaces: evaluate(model, data_loader, args) of both drivers -- density_experiment.py:544-603 (per batch component + 1 module
+ * forwards for G, one more for g, then torch.cat over the whole set and .mean().item()) and image_experiment.py:296-337 (per batch
+ * 3 C forwards of randomly drawn components and one .item()) -- by running sums that stay on the device across the batches of a
+ * loader and are read once after the last one.
+ *
+ * The evaluation state: GBNF_EVAL_STATE_DOUBLES doubles of caller-owned DEVICE memory.  The caller zeroes it before the first batch
+ * and reads it after the last; the library only ever ADDS to it:
+ *   [0] rows seen                          [1] batches seen (calls with n >= 1)
+ *   [2] sum G_ll     [3] sum g_ll          [4] sum (G_ll - g_ll)          [5] sum E_ll
+ *   [6] [7] [8]  the sums over batches of the batch means of G_ll, g_ll, E_ll
+ *   [9] rows where G_ll, g_ll or E_ll is not finite (they are still added: a NaN reaches the mean as it does in the reference)
+ *   [10] sum over rows of w_c CE           [11] sum over batches of w_c (batch-mean CE)     [12] sum over rows of w_c [pred == label]
+ *   [13..15] 0 (reserved)
+ * with, per row i of a (n_used, n) table ll of per-component log-likelihoods,
+ *   G_ll[i]  the recursion of density_experiment.py:561-573 over rows 0 .. n_used - 1: the float32 operations of gbnf_mixture_lse,
+ *            bit for bit;
+ *   g_ll[i]  ll[component][i];  G_ll - g_ll is formed in float32, as the reference forms g_nll - G_nll (:588);
+ *   E_ll[i]  sum_c w_c ll[c][i] in double, w_c = rho[c] / sum_{k < n_used} rho[k]: the exact expectation of what the image driver
+ *            estimates with 3 C draws of components="1:c" (every product and sum rounded on its own, in index order).
+ * So  nll = -[2] / [0],  g_nll = -[3] / [0],  ratio = [4] / [0]  (:582-588), and  -[6] / [1]  is the mean of batch means of :594.
+ * All sums run in double: per workgroup in an LDS tree (workgroup b of a grid of min(ceil(n / 1024), 256) takes rows
+ * b * 256 + t, stepping by the grid), then over the workgroups' partial sums in index order.  No atomics: the same calls in the
+ * same order give the same bits.  No host read, no synchronisation, no allocation.
+ *
+ * gbnf_eval_workspace_bytes: the size of the partial-sum scratch (DEVICE memory, 256-byte aligned) of the two accumulate calls.
+ * gbnf_eval_accumulate: two launches (the partial sums, a one-workgroup finalise that adds into state_dev) on a table with row
+ *   stride ll_row_stride floats; G_out_or_null: G_ll (n floats).  n == 0: GBNF_OK, nothing added (`batches` neither).
+ *   GBNF_ERR_INVALID before any launch: a null ll / rho_dev / state_dev / workspace, n < 0, n_used < 1, component outside
+ *   [0, n_used), ll_row_stride < n, a short workspace.
+ * gbnf_eval_accumulate_class_loss: component c's share of the class loss of class-conditional image models into entries 10 - 12
+ *   (rows and batches are not touched: the table's call counts them).  y_logits (n, Y), y (n, Y) DEVICE, 1 <= Y <= 256:
+ *   CE_i = LSE(logits_i) - logits_i[first largest entry of y_i] -- F.cross_entropy(y_logits, argmax(y)), image_experiment.py:236 --
+ *   in double; the prediction is the first largest logit, and a NaN never wins.  The refusals of gbnf_eval_accumulate, and Y outside
+ *   [1, 256], c outside [0, n_used).
+ * Two calls on one workspace must not run concurrently. */
+#define GBNF_EVAL_STATE_DOUBLES 16
+int gbnf_eval_workspace_bytes(int64_t n, int64_t* bytes);
+int gbnf_eval_accumulate(const float* ll, int64_t ll_row_stride, int32_t n_used, int64_t n, const float* rho_dev, int32_t component,
+                         float* G_out_or_null, double* state_dev, void* workspace, int64_t workspace_bytes, void* stream);
+int gbnf_eval_accumulate_class_loss(const float* y_logits, const float* y, int64_t n, int32_t Y, const float* rho_dev, int32_t n_used,
+                                    int32_t c, double* state_dev, void* workspace, int64_t workspace_bytes, void* stream);
+/* Replaces: one batch of density_experiment.py:549-579 in one call: gbnf_mixture_component_log_prob(mix, x, n, 0, n_used,
+ * ll_workspace) -- ONE flow launch for all components; the reference's extra forward of components="c" is row `component` of that
+ * table and is not run again --, then gbnf_eval_accumulate on it.  ll_workspace: (n_used, n) DEVICE floats, also an output;
+ * workspace: gbnf_eval_workspace_bytes.  Refused before any launch: everything gbnf_eval_accumulate refuses, a null mix or x,
+ * n_used beyond the mixture's components. */
+int gbnf_mixture_evaluate(const gbnf_mixture* mix, const float* x, int64_t n, int32_t n_used, int32_t component, const float* rho_dev,
+                          float* ll_workspace, float* G_out_or_null, double* state_dev, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+/* Replaces: one batch of image_experiment.py:302-334, built as gbnf_image_mixture_rho_step is: the forwards of flows[0 .. n_used - 1]
+ * one after the other on the caller's stream (the same noise for all) into ll_workspace ((n_used, n) DEVICE floats, also an output),
+ * then gbnf_eval_accumulate on that table.  With D = C H W pixels, the mixture's bits per dimension are -[2] / ([0] ln2 D) and the
+ * expectation of the reference's avg_loss is -[8] / ([1] ln2 D) (+ y_weight [11] / [1] for the _y call).
+ * workspace: gbnf_image_mixture_evaluate_workspace_bytes(flows, n_used, n) bytes -- the largest gbnf_image_flow_workspace_bytes of the
+ * handles, the call's ldj accumulator, n Y floats of logits (Y: the classes of flows[0], 0 for a plain model), the partial sums, each
+ * 256-byte aligned.  GBNF_ERR_INVALID (nothing launched): a null flows / x / rho_dev / ll_workspace / state_dev / workspace or a null
+ * entry of flows, n < 1, n_used < 1, component outside [0, n_used), handles whose input shape differs, a class-conditional handle
+ * (it needs y: the _y call), a short workspace.
+ * gbnf_image_mixture_evaluate_y: the same over class-conditional components with y (n, Y) DEVICE: every forward is
+ * gbnf_image_flow_forward_y under its prior of each row's y, with the logits into the workspace, and
+ * gbnf_eval_accumulate_class_loss follows each component.  Every handle must be conditioned on the same Y and have a class head: a
+ * plain handle, a second class count, a handle without a head or a null y is GBNF_ERR_INVALID before the first launch. */
+int gbnf_image_mixture_evaluate_workspace_bytes(const gbnf_image_flow* const* flows, int32_t n_flows, int64_t n, int64_t* bytes);
+int gbnf_image_mixture_evaluate(const gbnf_image_flow* const* flows, int32_t n_used, int32_t component, const float* x,
+                                const float* noise, int64_t n, const float* rho_dev, float* ll_workspace, float* G_out_or_null,
+                                double* state_dev, void* workspace, int64_t workspace_bytes, void* stream);
+int gbnf_image_mixture_evaluate_y(const gbnf_image_flow* const* flows, int32_t n_used, int32_t component, const float* x,
+                                  const float* noise, const float* y_dev, int64_t n, const float* rho_dev, float* ll_workspace,
+                                  float* G_out_or_null, double* state_dev, void* workspace, int64_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
