@@ -1239,6 +1239,58 @@ class BoostedFlow(nn.Module):
             out["g_nll"], out["ratio"] = out["nll"], 0.0
         return out
 
+    @torch.no_grad()
+    def fit_weights(self, data_loader, n_used=None, max_iters=1000, tol=1e-9, write=True):
+        """All weights of the first ``n_used`` components at once, by EM with the components fixed (gbnf_weights_em): the
+        fully-corrective step of boosting.  No reference counterpart; it supersedes ``update_rho``, which moves ``rho[component]``
+        alone.  One pass over a loader of ``(x, _)``: every batch's component log-likelihoods go, in ONE flow launch, into their columns
+        of a ``(n_used, rows)`` device table (sized by ``len(data_loader.dataset)`` when there is one; otherwise the batches' tables are
+        concatenated once); then ONE library call iterates on that table, started at ``rho[:n_used] / sum``, until the mean
+        log-likelihood moves by at most ``tol`` or ``max_iters`` updates were made -- no component forward and no host read per
+        iteration.  ``write``: ``self.rho[:n_used]`` becomes ``w * sum(rho[:n_used])`` clamped to the reference's [0.01, 100] in place
+        (gbnf_weights_to_rho; the entries beyond keep their standing).  Puts the module in eval mode.  ONE host read.  -> dict:
+          nll_before, nll_after   -mean_i G(x_i) at the starting and at the final weights (never larger after than before)
+          iters, converged        updates applied; whether the tolerance stopped them
+          rows, excluded          rows used; rows left out (a NaN or +inf entry, or -inf under every component)
+          weights                 the final w (n_used floats, before any clamp)
+          clamped                 entries of rho that met the range (0 without ``write``)
+        Default ``n_used`` as ``log_prob``.  An empty loader, or a rho with a negative or non-finite entry, raises ValueError."""
+        self.eval()
+        n_used = self._n_used(n_used)
+        if n_used > native.WEIGHTS_MAX_COMPONENTS:
+            raise ValueError(f"fit_weights handles up to {native.WEIGHTS_MAX_COMPONENTS} components, got n_used = {n_used}")
+        rho = self.rho
+        if rho.dtype != torch.float32 or not rho.is_contiguous():
+            raise ValueError("fit_weights reads (and with write=True writes) self.rho in place: it must be contiguous float32")
+        dev = rho.device
+        try:
+            capacity = len(data_loader.dataset)
+        except (AttributeError, TypeError):
+            capacity = None
+        table, filled, pieces = None, 0, []
+        for (x, _) in data_loader:
+            x = x.detach().to(dev)
+            self._check_ready(x)
+            x = x.contiguous().float()
+            if x.shape[0] == 0:
+                continue
+            for k in range(n_used):
+                self._ensure_actnorm(x, k)
+            self._guard(x, range(n_used))
+            with torch.cuda.device(dev):
+                mix = self.native_mixture(n_used)
+                if capacity is None:
+                    pieces.append(mix.component_log_prob(x, 0, n_used))
+                else:
+                    table = native.weights_table_room(table, n_used, capacity, filled, x.shape[0], dev)
+                    mix.prepared_component_log_prob(x, table, 0, n_used, col_offset=filled)(native._stream_ptr())
+            filled += x.shape[0]
+        if filled == 0:
+            raise ValueError("fit_weights: the loader yielded no rows")
+        if capacity is None:
+            table = pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
+        return native.fit_weights_on_table(table[:, :filled], rho, n_used, max_iters, tol, write)
+
     # ---- the score: grad_x log p(x) of a component and of the mixture (gbnf_mixture_score), eval or train mode alike
     def _score_input(self, x, comps):
         self._check_ready(x)

@@ -199,6 +199,11 @@ def main(argv=None):
     objs.append(eval_o)
     if args.force or not newer(eval_o, [eval_src, hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", eval_src, "-o", eval_o])
+    # all mixture weights at once (EM over a cached table of component log-likelihoods, the weights back into rho): gbnf_weights.hip
+    wt_o, wt_src = os.path.join(OBJ, "gbnf_weights.o"), os.path.join(HERE, "gbnf_weights.hip")
+    objs.append(wt_o)
+    if args.force or not newer(wt_o, [wt_src, hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", wt_src, "-o", wt_o])
     for v in read_variants():
         o = os.path.join(OBJ, "v_" + "_".join(str(a) for a in v) + ".o")
         objs.append(o)

@@ -1445,6 +1445,54 @@ class BoostedImageFlow(nn.Module):
             out["total_loss"] = out["bpd"] + y_weight * out["loss_classes"]
         return out
 
+    @torch.no_grad()
+    def fit_weights(self, data_loader, noise_generator=None, labels=False, n_used=None, max_iters=1000, tol=1e-9, write=True):
+        """All weights of the first ``n_used`` components at once, by EM with the components fixed (gbnf_weights_em): what
+        ``BoostedFlow.fit_weights`` does, on the table ``component_log_prob`` writes.  No reference counterpart; it supersedes
+        ``update_rho``.  One pass over the loader -- ``(x, _)`` with x in [0, 1], or ``(x, y_onehot)`` with ``labels``; the noise
+        and the labels are handled as in ``evaluate`` --, every batch's ``(n_used, n)`` table copied into its columns of a device
+        table of ``len(data_loader.dataset)`` columns (without a dataset the batches' tables are concatenated once), then ONE library
+        call for all iterations and, with ``write``, gbnf_weights_to_rho on ``self.rho``.  ONE host read.  -> the dict of
+        ``BoostedFlow.fit_weights`` (nll_* in nats per image)."""
+        if labels:
+            self._conditioned("fit_weights(labels=True)")
+        elif self.flows[0].y_condition:
+            raise NotImplementedError("fit_weights of a class-conditional model needs the rows' labels (pass labels=True and a loader "
+                                      "of (x, y_onehot))")
+        self.eval()
+        if n_used is None:
+            n_used = self.num_components if self.all_trained else self.component + 1
+        n_used = int(n_used)
+        if not 1 <= n_used <= min(self.num_components, native.WEIGHTS_MAX_COMPONENTS):
+            raise ValueError(f"n_used={n_used} outside [1, {min(self.num_components, native.WEIGHTS_MAX_COMPONENTS)}]")
+        rho = self.rho
+        if rho.dtype != torch.float32 or not rho.is_contiguous():
+            raise ValueError("fit_weights reads (and with write=True writes) self.rho in place: it must be contiguous float32")
+        try:
+            capacity = len(data_loader.dataset)
+        except (AttributeError, TypeError):
+            capacity = None
+        table, filled, pieces = None, 0, []
+        for (x, y) in data_loader:
+            x = x.detach().to(rho.device).contiguous().float()
+            self._check(x)
+            if x.shape[0] == 0:
+                continue
+            y = self._y(0, None if y is None else y.detach().to(rho.device), x.shape[0]) if labels else None
+            noise = torch.rand(x.shape, generator=noise_generator, device=x.device)
+            ll = self.component_log_prob(x, n_used, noise, y_onehot=y).t()
+            if capacity is None:
+                pieces.append(ll)
+            else:
+                table = native.weights_table_room(table, n_used, capacity, filled, x.shape[0], rho.device)
+                table[:, filled:filled + x.shape[0]].copy_(ll)
+            filled += x.shape[0]
+        if filled == 0:
+            raise ValueError("fit_weights: the loader yielded no rows")
+        if capacity is None:
+            table = torch.cat(pieces, dim=1)
+        return native.fit_weights_on_table(table[:, :filled], rho, n_used, max_iters, tol, write)
+
     # ---- checkpoint side-car (SURVEY.md S5 for image components)
     def _side_car_modules(self, c):
         flow = self.flows[c]

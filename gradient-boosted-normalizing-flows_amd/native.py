@@ -66,7 +66,14 @@ ABI_SYMBOLS = (
     "gbnf_image_flow_encode",
     "gbnf_eval_workspace_bytes", "gbnf_eval_accumulate", "gbnf_eval_accumulate_class_loss", "gbnf_mixture_evaluate",
     "gbnf_image_mixture_evaluate_workspace_bytes", "gbnf_image_mixture_evaluate", "gbnf_image_mixture_evaluate_y",
+    "gbnf_weights_em_workspace_bytes", "gbnf_weights_em", "gbnf_weights_to_rho",
 )
+# all mixture weights at once (include/gbnf.h: EM over a cached table of component log-likelihoods)
+WEIGHTS_SYMBOLS = ("gbnf_weights_em_workspace_bytes", "gbnf_weights_em", "gbnf_weights_to_rho")
+WEIGHTS_MAX_COMPONENTS = 64
+WEIGHTS_STATE_DOUBLES = 8 + WEIGHTS_MAX_COMPONENTS
+# state[7] reads bad_start + 2 * (entries weights_to_rho clamped); the weights start at WEIGHTS_STATE["weights"]
+WEIGHTS_STATE = {"iters": 0, "converged": 1, "rows": 2, "excluded": 3, "L0": 4, "L": 5, "delta": 6, "flags": 7, "weights": 8}
 
 # the evaluation state of the validation pass (include/gbnf.h: GBNF_EVAL_STATE_DOUBLES and its layout)
 EVAL_STATE_DOUBLES = 16
@@ -307,6 +314,9 @@ def lib():
     L.gbnf_image_mixture_evaluate_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
     L.gbnf_image_mixture_evaluate.argtypes = [C.POINTER(vp), i32, i32, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
     L.gbnf_image_mixture_evaluate_y.argtypes = [C.POINTER(vp), i32, i32, vp, vp, vp, i64, vp, vp, vp, vp, vp, i64, vp]
+    L.gbnf_weights_em_workspace_bytes.argtypes = [i32, i64, C.POINTER(i64)]
+    L.gbnf_weights_em.argtypes = [vp, i64, i32, i64, vp, i32, C.c_double, vp, vp, i64, vp]
+    L.gbnf_weights_to_rho.argtypes = [vp, i32, C.c_float, C.c_float, vp, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -2367,6 +2377,110 @@ def eval_accumulate_class_loss(y_logits, y, rho, c, state, n_used=None, workspac
     ptr = lambda t: C.c_void_p(t.data_ptr())
     _check(lib().gbnf_eval_accumulate_class_loss(ptr(y_logits), ptr(y), n, Y, ptr(rho), n_used, int(c), ptr(state), ptr(ws),
                                                  ws.numel() * ws.element_size(), _stream_ptr()))
+
+
+# ---- all mixture weights at once: EM over a cached (C, n) table of component log-likelihoods (gbnf_weights_em, gbnf_weights_to_rho)
+def weights_state(device):
+    """An evaluation state of ``weights_em``: ``WEIGHTS_STATE_DOUBLES`` float64 on ``device`` (layout: ``WEIGHTS_STATE`` / include/gbnf.h).
+    The call overwrites it."""
+    import torch
+    return torch.zeros(WEIGHTS_STATE_DOUBLES, dtype=torch.float64, device=device)
+
+
+def _require_weights_state(state):
+    import torch
+    if not isinstance(state, torch.Tensor) or not state.is_cuda or state.dtype != torch.float64 or not state.is_contiguous() \
+            or state.numel() < WEIGHTS_STATE_DOUBLES:
+        raise GbnfError(f"state must be a contiguous float64 device tensor of {WEIGHTS_STATE_DOUBLES} entries (native.weights_state)")
+    return state
+
+
+_weights_ws = {}      # device -> the control words and partial sums of weights_em (grown to the largest call so far)
+
+
+def weights_em(ll, rho, max_iters, tol, state=None, workspace=None):
+    """gbnf_weights_em: EM for the weights of the mixture over the (C, n) table ``ll`` of per-component log-likelihoods (float32 on the
+    device, unit column stride; the rows may be strided), started at ``rho[:C] / sum(rho[:C])`` and run until
+    ``|L_t - L_{t-1}| <= tol`` or ``max_iters`` updates (``tol <= 0``: exactly ``max_iters``), all on the device: ``max_iters + 2``
+    launches, of which those behind the stopping evaluation return at once; no host read.  -> ``state`` (``WEIGHTS_STATE``; given or
+    new), overwritten.  ``rho`` is only read.  ``workspace``: a float64 device tensor of gbnf_weights_em_workspace_bytes (default:
+    one per device, so calls on one device must not run on two streams at once)."""
+    import torch
+    if not isinstance(ll, torch.Tensor) or not ll.is_cuda or ll.dtype != torch.float32 or ll.dim() != 2 or (ll.shape[1] > 1 and ll.stride(1) != 1):
+        raise GbnfError("ll must be a (C, n) float32 device table with unit column stride")
+    _require_device_f32(rho, "rho")
+    n_comp, n = ll.shape
+    if rho.dim() != 1 or rho.numel() < n_comp:
+        raise GbnfError("rho shorter than the number of components")
+    state = weights_state(ll.device) if state is None else _require_weights_state(state)
+    stride = ll.stride(0) if n_comp > 1 else max(n, 1)
+    nb = C.c_int64()
+    _check(lib().gbnf_weights_em_workspace_bytes(n_comp, n, C.byref(nb)))
+    if workspace is None:
+        workspace = _weights_ws.get(ll.device)
+        if workspace is None or workspace.numel() * 8 < nb.value:
+            workspace = _weights_ws[ll.device] = torch.empty((nb.value + 7) // 8, dtype=torch.float64, device=ll.device)
+    # (an empty table has no address to hand over; no row of it is read: rho's stands in)
+    llp = C.c_void_p(ll.data_ptr() if ll.numel() else rho.data_ptr())
+    _check(lib().gbnf_weights_em(llp, stride, n_comp, n, C.c_void_p(rho.data_ptr()), int(max_iters), float(tol),
+                                 C.c_void_p(state.data_ptr()), C.c_void_p(workspace.data_ptr()),
+                                 workspace.numel() * workspace.element_size(), _stream_ptr()))
+    return state
+
+
+def weights_to_rho(state, rho, rho_min=0.01, rho_max=100.0, n_components=None):
+    """gbnf_weights_to_rho: ``rho[c] = clamp(w_c * sum(rho[:C]), rho_min, rho_max)`` for c < C in place, with w the weights in ``state``
+    (``weights_em``); entries at and beyond C stay.  Nothing is written after a bad start; twice the number of clamped entries is
+    added into ``state[7]``.  ``n_components`` defaults to ``rho.numel()``.  The caller moves rho's version counter."""
+    _require_weights_state(state)
+    _require_device_f32(rho, "rho")
+    n_comp = rho.numel() if n_components is None else int(n_components)
+    if rho.dim() != 1 or rho.numel() < n_comp:
+        raise GbnfError("rho shorter than the number of components")
+    _check(lib().gbnf_weights_to_rho(C.c_void_p(state.data_ptr()), n_comp, float(rho_min), float(rho_max), C.c_void_p(rho.data_ptr()),
+                                     _stream_ptr()))
+    return rho
+
+
+def weights_table_room(table, n_components, capacity, filled, n, device):
+    """The (n_components, >= filled + n) float32 device table ``fit_weights`` fills batch by batch: made at ``capacity`` columns on the
+    first batch, and doubled (its ``filled`` columns copied) should a loader yield more rows than its dataset holds."""
+    import torch
+    if table is not None and filled + n <= table.shape[1]:
+        return table
+    grown = torch.empty((n_components, max(capacity, filled + n, 0 if table is None else 2 * table.shape[1])), dtype=torch.float32,
+                        device=device)
+    if table is not None:
+        grown[:, :filled].copy_(table[:, :filled])
+    return grown
+
+
+def fit_weights_on_table(table, rho, n_components, max_iters, tol, write):
+    """The tail of both modules' ``fit_weights``: ``weights_em`` on the filled (C, rows) table, ``weights_to_rho`` on ``rho`` with
+    ``write`` (and rho's version counter moved, as the rho update does), ONE host read -> the report dict."""
+    import torch
+    with torch.cuda.device(table.device):
+        state = weights_em(table, rho, max_iters, tol)
+        if write:
+            weights_to_rho(state, rho, n_components=n_components)
+            # the kernel wrote rho behind autograd's back: move its version counter as the rho update does
+            torch.autograd.graph.increment_version([rho])
+    out = weights_report(state, n_components)
+    if out.pop("bad_start"):
+        raise ValueError("fit_weights: no usable row (every row holds a NaN or +inf, or is -inf under every component), or rho has a "
+                         f"negative or non-finite entry or sums to 0; rows used {out['rows']}, excluded {out['excluded']}")
+    out.pop("delta")
+    return out
+
+
+def weights_report(state, n_components):
+    """The dict ``fit_weights`` returns, from ONE host read of a ``weights_em`` state."""
+    s = state.tolist()
+    S = WEIGHTS_STATE
+    flags = int(s[S["flags"]])
+    return {"nll_before": -s[S["L0"]], "nll_after": -s[S["L"]], "iters": int(s[S["iters"]]), "converged": bool(s[S["converged"]]),
+            "rows": int(s[S["rows"]]), "excluded": int(s[S["excluded"]]), "weights": s[S["weights"]:S["weights"] + n_components],
+            "clamped": flags // 2, "bad_start": bool(flags & 1), "delta": s[S["delta"]]}
 
 
 def class_posterior(class_ll, log_prior=None, want_post=True, want_pred=False):

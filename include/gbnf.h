@@ -1266,6 +1266,49 @@ int gbnf_image_mixture_evaluate_y(const gbnf_image_flow* const* flows, int32_t n
                                   const float* noise, const float* y_dev, int64_t n, const float* rho_dev, float* ll_workspace,
                                   float* G_out_or_null, double* state_dev, void* workspace, int64_t workspace_bytes, void* stream);
 
+/* ---- all mixture weights at once: EM over a cached table of component log-likelihoods ---------------------------------------------
+ * No reference counterpart.  Supersedes update_rho (models/boosted_flow.py:141-207; gbnf_mixture_rho_step here), which moves one
+ * rho[component] at a time along mean(G_ll - g_ll) and never revisits earlier weights.  The recursion of gbnf_mixture_lse is the
+ * plain normalised mixture G = LSE_c(log w_c + ll_c) with w_c = rho_c / sum_{k < C} rho_k; with the components fixed, the weights
+ * that maximise the mean of G over a set of rows are a concave problem, and EM never decreases that mean.
+ *
+ * gbnf_weights_em: ll is a (C, n) DEVICE table with row stride ll_row_stride >= n floats (what
+ * gbnf_mixture_component_log_prob[_strided] or an image call wrote).  Everything below is in double:
+ *   w^(0)_c = rho_dev[c] / sum_k rho_dev[k], from the float32 entries, the sum in index order;
+ *   evaluation t = 0 .. max_iters:  per row  G_i = LSE_c(log w^(t)_c + ll[c][i])  (the largest term subtracted first),
+ *     L_t = (1 / N_used) sum_i G_i,   S_c = sum_i exp(log w^(t)_c + ll[c][i] - G_i);
+ *   stop when t >= 1, tol > 0 and |L_t - L_{t-1}| <= tol (converged; the weights stay w^(t)), or when t == max_iters;
+ *   otherwise w^(t+1)_c = S_c / N_used.   tol <= 0: no convergence test, exactly max_iters updates.
+ * So L at the final weights is always evaluated.  A row is excluded, and counted, when it holds a NaN or +inf or when all its
+ * entries are -inf; single -inf entries are legal and give r = 0 as in gbnf_mixture_responsibilities.  w_c = 0 is a legal fixed
+ * point (log w = -inf, no NaN); a row whose every finite entry belongs to a component of weight 0 has G = -inf and adds no r.
+ * Bad start -- N_used == 0, an entry of rho_dev[0..C) that is not finite or < 0, or a sum <= 0 --: [7] is set, no update is made,
+ * [2] and [3] are counted, [4] and [5] are what one evaluation at rho_dev[c] / sum gives (NaN without a usable row or weight) and
+ * [8..) hold those quotients as formed.
+ * state_dev (GBNF_WEIGHTS_STATE_DOUBLES doubles, DEVICE) is overwritten, nothing is added to it:
+ *   [0] updates applied   [1] converged (0 / 1)   [2] rows used   [3] rows excluded   [4] L_0   [5] L at the final weights
+ *   [6] the last |L_t - L_{t-1}| (0 after a single evaluation)   [7] bad_start (0 / 1)   [8 .. 8 + C) the final weights
+ * Sums: across the 64 rows of a wave in a fixed tree, over the rows a wave walks, over the 4 waves, then over the workgroups'
+ * partial sums in index order (a grid of min(max(ceil(n / 1024), 1), 256) workgroups of 256 rows, stepping by the grid).  No
+ * atomics: the same call gives the same bits.  max_iters + 2 launches are enqueued (evaluation k re-adds the partial sums of
+ * evaluation k - 1 in every workgroup, through two alternating partial buffers; the last launch only finalises); "stopped" is a
+ * DEVICE word, and every launch behind the stopping evaluation returns at once.  No host read, no synchronisation, no allocation.
+ * workspace: gbnf_weights_em_workspace_bytes(C, n) bytes of DEVICE memory, 256-byte aligned; two calls on one workspace must not
+ * run concurrently.  GBNF_ERR_INVALID before any launch: a null ll / rho_dev / state_dev / workspace, n < 0 (n == 0 is legal: a bad
+ * start), C outside [1, GBNF_WEIGHTS_MAX_COMPONENTS], ll_row_stride < n, max_iters < 0, a NaN tol, a short workspace.
+ *
+ * gbnf_weights_to_rho: one launch.  rho_dev[c] = clamp(w_c * S, rho_min, rho_max) for c < C, with w_c = state_dev[8 + c] and S the
+ * sum of the old rho_dev[0..C) (double, index order; the product is rounded to float32, then clamped): the total is kept, so
+ * entries at and beyond C keep their relative standing.  In place.  Writes nothing when bad_start is set.  ADDS twice the number
+ * of clamped entries into state_dev[7], so that word reads bad_start + 2 * clamped (hence state_dev is not const).  The reference's
+ * range is [0.01, 100].  GBNF_ERR_INVALID: a null pointer, C outside [1, 64], rho_min > rho_max or a NaN bound. */
+#define GBNF_WEIGHTS_MAX_COMPONENTS 64
+#define GBNF_WEIGHTS_STATE_DOUBLES (8 + GBNF_WEIGHTS_MAX_COMPONENTS)
+int gbnf_weights_em_workspace_bytes(int32_t n_components, int64_t n, int64_t* bytes);
+int gbnf_weights_em(const float* ll, int64_t ll_row_stride, int32_t n_components, int64_t n, const float* rho_dev, int32_t max_iters,
+                    double tol, double* state_dev, void* workspace, int64_t workspace_bytes, void* stream);
+int gbnf_weights_to_rho(double* state_dev, int32_t n_components, float rho_min, float rho_max, float* rho_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
