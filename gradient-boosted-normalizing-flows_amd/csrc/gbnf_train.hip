@@ -1276,7 +1276,9 @@ static void wg_shape(int M, int N, WgProblem& P, int cap = 256) {
   P.bm = M <= 64 ? 64 : (M <= 128 || cap <= 128 ? 128 : 256);
   P.bn = N <= 64 ? 64 : (N <= 128 || cap <= 128 ? 128 : 256);
   struct S { int bm, bn, wm, wn; };
-  static const S table[] = {{256, 256, 2, 4}, {256, 128, 4, 2}, {256, 64, 8, 1}, {128, 256, 2, 4}, {64, 256, 1, 8},
+  // (the layers of a coupling net are h x in (in <= 32), h x h, out x h (out <= 64): a 256-edge block is 256 x 256, 256 x 64 or
+  //  64 x 256 -- tests/test_train_large_batch_host.py walks every geometry gbnf_trainer_create accepts)
+  static const S table[] = {{256, 256, 2, 4}, {256, 64, 8, 1}, {64, 256, 1, 8},
                             {128, 128, 2, 4}, {128, 64, 4, 2},  {64, 128, 2, 4}, {64, 64, 2, 4}};
   for (const S& e : table)
     if (e.bm == P.bm && e.bn == P.bn) { P.wm = e.wm; P.wn = e.wn; }
@@ -2655,6 +2657,28 @@ int gbnf_debug_trainer_last_path(const gbnf_trainer* t, int32_t* fwd_ranges, int
   if (!t) return fail(GBNF_ERR_INVALID, "gbnf_debug_trainer_last_path: trainer is null");
   if (fwd_ranges) *fwd_ranges = t->last_fwd_ranges;
   if (bwd_ranges) *bwd_ranges = t->last_bwd_ranges;
+  return GBNF_OK;
+}
+
+// (tests) the weight-gradient launch the chained backward takes at a batch of n rows, as wgrad_plan decides it:
+// out = {list (0 = probs_dev, 1 = probs_small_dev, 2 = probs_safe_dev), dW blocks, samples per block, sample chunks Y}
+int gbnf_debug_trainer_wgrad_plan(const gbnf_trainer* t, int64_t n, int32_t out[4]) {
+  if (!t || !out || n <= 0) return fail(GBNF_ERR_INVALID, "gbnf_debug_trainer_wgrad_plan: bad argument");
+  if (t->rep.f) return fail(GBNF_ERR_UNSUPPORTED, "gbnf_debug_trainer_wgrad_plan: a repairing trainer has two plans (one per half)");
+  if (!live_blob_has_backward(t->live)) return fail(GBNF_ERR_UNSUPPORTED, "gbnf_debug_trainer_wgrad_plan: this trainer has no chained backward");
+  const WgPlan w = wgrad_plan(t, t->lay.at(n));
+  out[0] = w.probs == t->probs_dev ? 0 : (w.probs == t->probs_small_dev ? 1 : 2);
+  out[1] = w.blocks; out[2] = w.chunk; out[3] = w.Y;
+  return GBNF_OK;
+}
+
+// (tests; host only, touches no device) the block wg_shape cuts an M x N weight-gradient problem into at a largest block edge of `cap`:
+// out = {bm, bn, wm, wn}; wm = wn = 0: the block has no row in wg_shape's table (and no wgrad_block instantiation)
+int gbnf_debug_wg_shape(int32_t M, int32_t N, int32_t cap, int32_t out[4]) {
+  if (!out || M < 1 || N < 1) return fail(GBNF_ERR_INVALID, "gbnf_debug_wg_shape: bad argument");
+  WgProblem P{};
+  wg_shape(M, N, P, cap);
+  out[0] = P.bm; out[1] = P.bn; out[2] = P.wm; out[3] = P.wn;
   return GBNF_OK;
 }
 

@@ -54,10 +54,9 @@
   // pieces per thread (a 64-row operand: one, repeated by the upper waves) and the wave's tile of the block, see wg_shape()
 #define WG_CASE(BM, BN, ND, NA, TM, TN) \
   if (P.bm == BM && P.bn == BN) return wgrad_block<ND, NA, TM, TN, (TM * TN < 32), (GBNF_WG_DET != 0)>(P, ws, WG_DST, np, s_begin, s_end, m0, n0, inv_alpha, wg_stage_raw)
+  // (no 256 x 128 / 128 x 256: a trainer's hidden layers are square and its other edges are at most 64 -- wg_shape never cuts one)
   WG_CASE(256, 256, 2, 2, 8, 4);
-  WG_CASE(256, 128, 2, 1, 4, 4);
   WG_CASE(256, 64, 2, 1, 2, 4);
-  WG_CASE(128, 256, 1, 2, 4, 4);
   WG_CASE(64, 256, 1, 2, 4, 2);
   WG_CASE(128, 128, 1, 1, 4, 2);
   WG_CASE(128, 64, 1, 1, 2, 2);

@@ -776,7 +776,9 @@ def test_fast_forward_writes_what_the_backward_needs(kind, d, h, n):
 @pytest.mark.gpu
 @pytest.mark.parametrize("kind,d,h,K", [("glow", 43, 215, 5), ("realnvp", 21, 105, 5)])
 def test_weight_gradients_are_additive_over_the_batch_at_full_size(kind, d, h, K):
-    """Size-independent property at BASELINE's N = 65536 (the oracle cannot run a backward pass of that size in seconds): with
+    """Size-independent property at BASELINE's N = 65536 (at K = 5 the float64 oracle's backward pass of that size takes more than
+    the few seconds a test has; up to 32 k rows at K <= 5 it does not: tests/test_hip_train_large_batch.py compares the launch forms
+    of large batches with the oracle itself): with
     fixed normalisation statistics the parameter gradients of a batch are the SUM of the gradients of its parts.  One call on
     65536 rows (wgrad_kernel: 8-wave blocks, 32 sample chunks per block column, two k-steps of loads in flight, float atomics)
     against eight calls on 8192 rows each (other chunk counts, other block counts per CU), and g_x row for row."""
