@@ -1027,6 +1027,50 @@ class BoostedFlow(nn.Module):
         torch.autograd.graph.increment_version(params + buffers if batch_stats else params)
         return {"G_nll": stats[4], "ess": stats[5], "nll": stats[0], "grad_norm": stats[1], "clip_coef": stats[2]}
 
+    def mixture_training_step(self, x, *, lr, weight_decay=0.0, max_grad_norm=0.0, optimizer="adamw", betas=(0.9, 0.999), eps=1e-8,
+                              n_used=None):
+        """One JOINT step of components 0 .. ``n_used`` - 1 (default as ``log_prob``) on the objective the model is judged by, the
+        mixture likelihood  -mean_i log sum_c w_c p_c(x_i), in one library call (gbnf_mixture_nll_step): every component's forward,
+        the responsibilities r = softmax_c(log w + ll), every component's backward on the seeds (r_c / n) z_c, -r_c / n, ONE clip
+        coefficient over all components' gradients (``clip_grad_norm_(model.parameters())``) and every component's ``optim.AdamW`` /
+        ``optim.SGD`` update, in place.  No reference counterpart (the reference trains one component at a time); what it replaces
+        is the eager composition of C recorded forwards, a logsumexp, backward, clip and C optimiser steps.  The weights are
+        w_c = rho_c / sum_{j < n_used} rho_j (``score``'s closed form), held fixed during the step.  ``lr``: a float, or ``n_used``
+        floats (0: that component's parameters stay bit for bit while its moments move).  The optimiser states are
+        ``self.opt_state(c, optimizer)``, so a boosted model continues on the moments ``training_step`` left.  Runs on the RUNNING
+        statistics in either module mode (the trainers' batch-statistics mode is switched off for the call and put back; a recorded
+        train-mode forward still awaiting its backward raises RuntimeError on that backward, as with ``score``); uninitialised
+        ActNorms raise ValueError.  Returns device tensors, nothing is read back: ``nll``, ``grad_norm`` (over all components),
+        ``clip_coef`` (0-dim), ``mean_responsibilities`` (n_used,) and ``component_grad_norms`` (n_used,).
+        ``mean_responsibilities`` is the EM update of the weights on this batch (``fit_weights`` does the same over a whole table):
+        a caller who wants a stochastic weight update between ``fit_weights`` calls has it here.  No ``p.grad`` is written."""
+        n_used = self._n_used(n_used)
+        comps = list(range(n_used))
+        x = self._score_input(x, comps)
+        lrs = [float(lr)] * n_used if isinstance(lr, (int, float)) else [float(v) for v in lr]
+        if len(lrs) != n_used:
+            raise ValueError(f"lr must be a float or {n_used} floats (one per component in use), got {len(lrs)}")
+        with torch.cuda.device(x.device):
+            trainers = [self.native_trainer(c) for c in comps]
+            states = [self.opt_state(c, optimizer) for c in comps]
+            modes = [t.batch_stats for t in trainers]
+            try:
+                for t in trainers:
+                    t.set_batch_stats(False)
+                    if t.has_batch_stats:
+                        t.forward_serial = getattr(t, "forward_serial", 0) + 1
+                stats, _, _, _ = native.mixture_nll_step(trainers, states, self._log_w(n_used), x, lr=lrs, weight_decay=weight_decay,
+                                                         max_grad_norm=max_grad_norm, betas=betas, eps=eps)
+            finally:
+                for t, on in zip(trainers, modes):
+                    t.set_batch_stats(on)
+        # the kernels wrote the parameters behind autograd's back: move their version counters so that the packed evaluation copies
+        # keyed on them (_component_key) are rebuilt
+        params = [p for c in comps for p in self._component_tensors(c)[0]]
+        torch.autograd.graph.increment_version(params)
+        return {"nll": stats[0], "grad_norm": stats[1], "clip_coef": stats[2], "mean_responsibilities": stats[4:4 + n_used],
+                "component_grad_norms": stats[4 + n_used:4 + 2 * n_used]}
+
     def opt_state(self, c, optimizer="adamw"):
         """The ``native.OptState`` ``training_step`` keeps for component c (created on first use; another ``optimizer`` kind or a
         re-shaped component starts a new one)."""

@@ -261,6 +261,11 @@ def main(argv=None):
     objs.append(tsc_o)
     if args.force or not newer(tsc_o, [tsc_src, opt_hdr, hdr[2], hdr[3]]):
         jobs.append([HIPCC] + FLAGS + ["-c", tsc_src, "-o", tsc_o])
+    # one joint likelihood step of the whole tabular mixture (the responsibility seed, the sums of G and r, the finish; the sweeps and the update are the trainers' and gbnf_opt.hip's): gbnf_mixstep.hip
+    ms_o, ms_src = os.path.join(OBJ, "gbnf_mixstep.o"), os.path.join(HERE, "gbnf_mixstep.hip")
+    objs.append(ms_o)
+    if args.force or not newer(ms_o, [ms_src, opt_hdr, hdr[2], hdr[3]]):
+        jobs.append([HIPCC] + FLAGS + ["-c", ms_src, "-o", ms_o])
     comm_o, comm_src = os.path.join(OBJ, "gbnf_comm.o"), os.path.join(HERE, "gbnf_comm.hip")
     objs.append(comm_o)
     if args.force or not newer(comm_o, [comm_src, hdr[2], hdr[3]]):

@@ -215,5 +215,8 @@ int64_t trainer_backward_x_base_bytes(const gbnf_trainer* t, int64_t n);
 // batch-statistics mode; the deterministic-mode and workspace-size refusals happen here, before any launch.
 int trainer_backward_x(const gbnf_trainer* t, const float* x, int64_t n, const float* trace, const float* g_z, const float* g_ldj, float* g_x,
                        void* workspace, int64_t workspace_bytes, float* discard, float* xpair, hipStream_t s);
+// ll[i] = sum_j log N(z_ij; 0, 1) + ldj[i]  (n,): score_seed_kernel with only ll wanted -- the per-row double sum in feature order,
+// rounded once, the constant that of gbnf_mixture_component_log_prob.  One launch, n >= 1.  gbnf_score.hip; used by gbnf_mixstep.hip
+void score_launch_ll(const float* z, const float* ldj, int64_t n, int d, float* ll, hipStream_t s);
 
 }  // namespace gbnf

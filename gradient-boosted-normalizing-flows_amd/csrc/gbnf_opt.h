@@ -48,6 +48,16 @@ struct OptUpdateView {
 int opt_launch_update(const char* fn, const OptUpdateView& view, const float* grads, float* m, float* v, const gbnf_opt_hyper* h,
                       float* stats, double* partials, const double* nll_partial, int n_nll_partial, double nll_scale, double nll_const,
                       void* stream);
+// The two launches of opt_launch_update one by one, for a caller whose clip coefficient spans more than one gradient buffer (the
+// mixture step, gbnf_mixstep.hip).  opt_launch_grad_sqsum: grad_sqsum_kernel into `partials`; returns how many it wrote (at most
+// OPT_MAX_PARTIALS, a function of grad_floats alone).  opt_launch_update_from: opt_update_kernel on squared-norm sums that are in
+// memory already -- it re-adds grad_partial[0 .. n_grad_partial) in a fixed order, whoever wrote them (one double: a finished sum).
+int opt_launch_grad_sqsum(const float* grads, int64_t grad_floats, double* partials, void* stream);
+int opt_launch_update_from(const char* fn, const OptUpdateView& view, const float* grads, float* m, float* v, const gbnf_opt_hyper* h,
+                           float* stats, const double* grad_partial, int n_grad_partial, const double* nll_partial, int n_nll_partial,
+                           double nll_scale, double nll_const, void* stream);
+// Workgroups of a reduction's producer over `work` entries: one per 1024, at least 1, at most OPT_MAX_PARTIALS.  gbnf_opt.hip
+unsigned opt_partial_blocks(int64_t work);
 // What every call that ends in an update refuses before it launches anything (GBNF_ERR_INVALID: null hyper, unknown kind, AdamW with
 // step <= 0 or without state); `fn` names the entry point in the message.  gbnf_opt.hip
 int check_hyper(const char* fn, const gbnf_opt_hyper* h, const float* m, const float* v);

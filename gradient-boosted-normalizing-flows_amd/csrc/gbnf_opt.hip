@@ -45,7 +45,7 @@ __device__ __forceinline__ double opt_block_sum(double v, double* lds) {
 }
 
 // workgroups of a producer over `work` entries: one per 1024 entries, at most OPT_MAX_PARTIALS (a function of the size alone)
-static unsigned partial_blocks(int64_t work) {
+unsigned opt_partial_blocks(int64_t work) {
   const int64_t b = (work + 4 * OPT_THREADS - 1) / (4 * OPT_THREADS);
   return (unsigned)(b < 1 ? 1 : (b > OPT_MAX_PARTIALS ? OPT_MAX_PARTIALS : b));
 }
@@ -207,16 +207,22 @@ int check_hyper(const char* fn, const gbnf_opt_hyper* h, const float* m, const f
   return GBNF_OK;
 }
 
-// norm partials -> clip coefficient + update (+ the loss of nll_step) -- two launches
-int opt_launch_update(const char* fn, const OptUpdateView& tv, const float* grads, float* m, float* v, const gbnf_opt_hyper* h, float* stats,
-                      double* partials, const double* nll_partial, int n_nll_partial, double nll_scale, double nll_const, void* stream) {
+// the squared-norm partials of a flat gradient buffer: one launch; returns how many partials it leaves (a function of the size alone)
+int opt_launch_grad_sqsum(const float* grads, int64_t grad_floats, double* partials, void* stream) {
+  const unsigned gb = opt_partial_blocks(grad_floats);
+  hipLaunchKernelGGL(grad_sqsum_kernel, dim3(gb), dim3(OPT_THREADS), 0, (hipStream_t)stream, grads, grad_floats, partials);
+  return (int)gb;
+}
+
+// clip coefficient + update (+ the loss of nll_step) from squared-norm sums that are in memory already -- one launch
+int opt_launch_update_from(const char* fn, const OptUpdateView& tv, const float* grads, float* m, float* v, const gbnf_opt_hyper* h,
+                           float* stats, const double* grad_partial, int n_grad_partial, const double* nll_partial, int n_nll_partial,
+                           double nll_scale, double nll_const, void* stream) {
   hipStream_t s = (hipStream_t)stream;
-  const unsigned gb = partial_blocks(tv.grad_floats);
-  hipLaunchKernelGGL(grad_sqsum_kernel, dim3(gb), dim3(OPT_THREADS), 0, s, grads, tv.grad_floats, partials);
   OptLaunch p{};
   p.regions = tv.regions_dev; p.n_regions = tv.n_regions; p.kind = h->kind; p.ng = tv.grad_floats;
   p.grads = grads; p.m = m; p.v = v;
-  p.grad_partial = partials; p.n_grad_partial = (int)gb;
+  p.grad_partial = grad_partial; p.n_grad_partial = n_grad_partial;
   p.nll_partial = nll_partial; p.n_nll_partial = n_nll_partial;
   if (nll_partial != nullptr) {
     p.nll_scale = nll_scale;
@@ -238,6 +244,13 @@ int opt_launch_update(const char* fn, const OptUpdateView& tv, const float* grad
   const hipError_t e = hipGetLastError();
   if (e != hipSuccess) return fail(GBNF_ERR_HIP, "%s launch: %s", fn, hipGetErrorString(e));
   return GBNF_OK;
+}
+
+// norm partials -> clip coefficient + update (+ the loss of nll_step) -- the two launches above
+int opt_launch_update(const char* fn, const OptUpdateView& tv, const float* grads, float* m, float* v, const gbnf_opt_hyper* h, float* stats,
+                      double* partials, const double* nll_partial, int n_nll_partial, double nll_scale, double nll_const, void* stream) {
+  const int gb = opt_launch_grad_sqsum(grads, tv.grad_floats, partials, stream);
+  return opt_launch_update_from(fn, tv, grads, m, v, h, stats, partials, gb, nll_partial, n_nll_partial, nll_scale, nll_const, stream);
 }
 
 // ... for a gbnf_trainer: the tabular loss is nll = sum / n + 0.5 d log 2 pi
@@ -326,13 +339,13 @@ int gbnf_trainer_nll_step(const gbnf_trainer* t, const float* x, int64_t n_x, co
   const int64_t nd = n * tv.d;
   if (rows != nullptr) {
     float* xg = (float*)(ws + L.xg);
-    hipLaunchKernelGGL(gather_rows_kernel, dim3(partial_blocks(nd)), dim3(OPT_THREADS), 0, s, x, rows, n_x, n, tv.d, xg);
+    hipLaunchKernelGGL(gather_rows_kernel, dim3(opt_partial_blocks(nd)), dim3(OPT_THREADS), 0, s, x, rows, n_x, n, tv.d, xg);
     x = xg;
   }
   int rc = gbnf_trainer_forward(t, x, n, z, ldj, trace, stream);
   if (rc) return rc;
   if (running_update) hipLaunchKernelGGL(bn_running_kernel, dim3((unsigned)tv.bn.n), dim3(64), 0, s, tv.bn, tv.d, h->bn_momentum);
-  const unsigned nb = partial_blocks(nd);
+  const unsigned nb = opt_partial_blocks(nd);
   hipLaunchKernelGGL(nll_seed_kernel, dim3(nb), dim3(OPT_THREADS), 0, s, (const float*)z, (const float*)ldj, n, tv.d, 1.0f / (float)n, g_z, g_ldj,
                      nll_partial);
   hipError_t e = hipMemsetAsync(grads, 0, (size_t)tv.grad_floats * 4, s);

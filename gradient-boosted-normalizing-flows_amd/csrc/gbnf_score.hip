@@ -215,6 +215,11 @@ int check_mix_trainers(const char* fn, gbnf_trainer* const* trainers, int C) {
 
 }  // namespace
 
+// ll[i] = log N(z_i; 0, I) + ldj[i]: the seed launch with nothing but ll wanted (the mixture step's table, gbnf_mixstep.hip)
+void score_launch_ll(const float* z, const float* ldj, int64_t n, int d, float* ll, hipStream_t s) {
+  launch_seed(z, nullptr, nullptr, nullptr, ldj, n, d, nullptr, nullptr, ll, s);
+}
+
 }  // namespace gbnf
 
 using namespace gbnf;

@@ -67,6 +67,7 @@ ABI_SYMBOLS = (
     "gbnf_eval_workspace_bytes", "gbnf_eval_accumulate", "gbnf_eval_accumulate_class_loss", "gbnf_mixture_evaluate",
     "gbnf_image_mixture_evaluate_workspace_bytes", "gbnf_image_mixture_evaluate", "gbnf_image_mixture_evaluate_y",
     "gbnf_weights_em_workspace_bytes", "gbnf_weights_em", "gbnf_weights_to_rho",
+    "gbnf_mixture_step_workspace_bytes", "gbnf_mixture_nll_step",
 )
 # all mixture weights at once (include/gbnf.h: EM over a cached table of component log-likelihoods)
 WEIGHTS_SYMBOLS = ("gbnf_weights_em_workspace_bytes", "gbnf_weights_em", "gbnf_weights_to_rho")
@@ -317,6 +318,9 @@ def lib():
     L.gbnf_weights_em_workspace_bytes.argtypes = [i32, i64, C.POINTER(i64)]
     L.gbnf_weights_em.argtypes = [vp, i64, i32, i64, vp, i32, C.c_double, vp, vp, i64, vp]
     L.gbnf_weights_to_rho.argtypes = [vp, i32, C.c_float, C.c_float, vp, vp]
+    L.gbnf_mixture_step_workspace_bytes.argtypes = [C.POINTER(vp), i32, i64, C.POINTER(i64)]
+    L.gbnf_mixture_nll_step.argtypes = [C.POINTER(vp), i32, vp, vp, i64, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp), C.POINTER(_OptHyper),
+                                        vp, vp, vp, vp, i64, vp]
     for name in ABI_SYMBOLS:
         if name not in ("gbnf_version", "gbnf_last_error"):
             getattr(L, name).restype = C.c_int
@@ -2700,6 +2704,67 @@ def mixture_score(trainers, log_w, x, ll=None, base=None, want_r=False, workspac
         _check(lib().gbnf_mixture_score(arr, nc, ptr(log_w), ptr(mean), ptr(std), ptr(ll), ptr(x), n, ptr(g_x), ptr(G), ptr(r),
                                         ptr(workspace), workspace.numel() * workspace.element_size(), _stream_ptr()))
     return g_x, G, r
+
+
+def mixture_step_workspace_bytes(trainers, n):
+    trainers = _open_trainers(trainers)
+    arr = (C.c_void_p * len(trainers))(*[t.handle for t in trainers])
+    nb = C.c_int64()
+    _check(lib().gbnf_mixture_step_workspace_bytes(arr, len(trainers), int(n), C.byref(nb)))
+    return int(nb.value)
+
+
+def mixture_nll_step(trainers, states, log_w, x, *, lr, weight_decay=0.0, max_grad_norm=0.0, betas=(0.9, 0.999), eps=1e-8, want_G=False,
+                     want_r=False, workspace=None):
+    """gbnf_mixture_nll_step: ONE joint step of every component on the mixture NLL  -mean_i LSE_c(log_w_c + ll_c(x_i))  in one library
+    call: C traced forwards -> responsibilities -> per component the seed (r_c / n) z_c, -r_c / n, its backward and gradient norm ->
+    one clip coefficient over all components -> C optimiser updates on the live tensors, no host read in between.  ``trainers``:
+    ``NativeTrainer``s of components 0 .. C-1 on running statistics; ``states``: their ``OptState``s (one kind), each advanced by one
+    step; ``log_w`` (C,) device, held fixed; ``lr``: a float or a sequence of C floats (0: that component's parameters stay bit for
+    bit, its moments move).  -> (stats (4 + 2 C,) device tensor: nll, total gradient norm, clip coefficient, 0, the C mean
+    responsibilities, the C component gradient norms; the C flat unclipped gradients; G (n,) | None; r (C, n) | None).
+    ``workspace``: a contiguous device tensor to use (None: allocated here; its size is checked by the library).  The parameters
+    change behind autograd's back: no version counter moves (``BoostedFlow.mixture_training_step`` takes care of that)."""
+    import torch
+    trainers = _open_trainers(trainers)
+    nc = len(trainers)
+    states = list(states)
+    if len(states) != nc or any(not isinstance(s, OptState) for s in states):
+        raise GbnfError(f"states must be {nc} OptStates, one per trainer")
+    lrs = [float(lr)] * nc if isinstance(lr, (int, float)) else [float(v) for v in lr]
+    if len(lrs) != nc:
+        raise GbnfError(f"lr must be a float or {nc} floats, got {len(lrs)}")
+    _require_device_f32(x, "x")
+    if x.dim() != 2 or x.shape[0] < 1 or any(x.shape[1] != t.d for t in trainers):
+        raise GbnfError(f"x must be (n,{trainers[0].d}) with n >= 1 for every trainer, got {tuple(x.shape)}")
+    n = x.shape[0]
+    _require_device_f32(log_w, "log_w")
+    if tuple(log_w.shape) != (nc,):
+        raise GbnfError(f"log_w must be ({nc},), got {tuple(log_w.shape)}")
+    if len({s.kind for s in states}) != 1:
+        raise GbnfError("states must be of one optimiser kind")
+    hypers = (_OptHyper * nc)()
+    for c, (t, s) in enumerate(zip(trainers, states)):
+        s.check(t)
+        hypers[c] = t._hyper(s, lr=lrs[c], weight_decay=weight_decay, max_grad_norm=max_grad_norm, betas=betas, eps=eps)
+    if workspace is None:
+        nb = mixture_step_workspace_bytes(trainers, n)
+        workspace = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
+        raise GbnfError("workspace must be a contiguous device tensor")
+    flats = [torch.empty(t.grad_floats, dtype=torch.float32, device=x.device) for t in trainers]
+    stats = torch.zeros(4 + 2 * nc, dtype=torch.float32, device=x.device)
+    G = torch.empty(n, dtype=torch.float32, device=x.device) if want_G else None
+    r = torch.empty((nc, n), dtype=torch.float32, device=x.device) if want_r else None
+    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+    addr = lambda ts: (C.c_void_p * nc)(*[None if t is None else t.data_ptr() for t in ts])
+    arr = (C.c_void_p * nc)(*[t.handle for t in trainers])
+    _check(lib().gbnf_mixture_nll_step(arr, nc, ptr(log_w), ptr(x), n, addr(flats), addr([s.exp_avg for s in states]),
+                                       addr([s.exp_avg_sq for s in states]), hypers, ptr(stats), ptr(G), ptr(r), ptr(workspace),
+                                       workspace.numel() * workspace.element_size(), _stream_ptr()))
+    for s in states:
+        s.step += 1
+    return stats, flats, G, r
 
 
 def prepared_mixture_lse(ll, rho, out):

@@ -1309,6 +1309,53 @@ int gbnf_weights_em(const float* ll, int64_t ll_row_stride, int32_t n_components
                     double tol, double* state_dev, void* workspace, int64_t workspace_bytes, void* stream);
 int gbnf_weights_to_rho(double* state_dev, int32_t n_components, float rho_min, float rho_max, float* rho_dev, void* stream);
 
+/* ---- One joint likelihood step of the whole tabular mixture: every component moves on the mixture NLL ----
+ * No reference counterpart: the reference trains one component at a time on its own NLL (density_experiment.py:340-374, the second
+ * pass `all_trained` included).  Replaces the eager composition a joint fine-tune needs -- C recorded forwards, a logsumexp, C
+ * backward passes, clip_grad_norm_(model.parameters()), C optimiser steps -- for the trainers of components 0 .. n_components - 1:
+ *   L = -1/n sum_i G_i,   G_i = LSE_c(log_w[c] + ll_c(x_i)),   dL/dtheta_c = -1/n sum_i r_ic d ll_c(x_i) / dtheta_c,
+ * so component c's backward runs unchanged on the seeds g_z = (r_c / n) z_c, g_ldj = -r_c / n.  log_w (C,) DEVICE is held fixed
+ * (gbnf_mixture_score's closed form, or any other weights).  The call launches on `stream` in this order and never reads the
+ * device, synchronises or allocates:
+ *   1. per component, in order: gbnf_trainer_forward on the live parameters into the component's OWN trace, then
+ *      ll_c = log N(z_c; 0, I) + ldj_c (gbnf_score_seed's per-row double sum, 2 pi term included);
+ *   2. gbnf_mixture_responsibilities -> r (C, n), G (n,), copied to r_or_null / G_or_null (DEVICE) when given;
+ *   3. per-workgroup double partial sums of sum_i G_i and of sum_i r_ci for every c (at most 256 workgroups, their number a
+ *      function of n alone), re-added in step 5 in a fixed order; no float atomics;
+ *   4. per component, in order: the seed with inv_n = 1.0f / n (s_i = r_c[i] * inv_n, g_z[i][j] = s_i * z_c[i][j], g_ldj[i] = -s_i),
+ *      grads[c] zeroed, gbnf_trainer_backward with the component's trace (no g_x), the squared-norm partials of grads[c];
+ *   5. one workgroup re-adds everything in component order and partial order, in double: nll = -sum G / n,
+ *      rbar_c = sum_i r_ci / n, norm_c = ||grads[c]||_2, total = sqrt(sum_c norm_c^2);
+ *   6. per component gbnf_trainer_apply_update's update kernel with the ONE clip coefficient min(1, max_grad_norm / (total + 1e-6))
+ *      (1 without clipping), as clip_grad_norm_ over all components' parameters gives.
+ * grads / exp_avg / exp_avg_sq: host arrays of C DEVICE buffers, each of its trainer's gbnf_trainer_grad_floats floats (entries of
+ * exp_avg / exp_avg_sq may be NULL for SGD); grads[c] holds component c's unclipped gradient afterwards.  hypers: a host array of C
+ * structs.  kind and max_grad_norm must agree across it; lr, weight_decay, the betas, eps and step are per component (components
+ * boosted one after the other sit at different AdamW steps); a component with lr = 0 keeps its parameters bit for bit while its
+ * moments move; bn_momentum is ignored (the step runs on the running statistics and leaves them alone).
+ * stats_dev: 4 + 2 C floats of DEVICE memory: [0] nll, [1] total gradient norm, [2] clip coefficient, [3] 0, [4 + c] rbar_c (the EM
+ * update of the weights on this batch), [4 + C + c] norm_c.
+ * A non-finite G row is not masked: it reaches [0] and the gradients exactly as a non-finite z does in gbnf_trainer_nll_step.
+ * With C = 1 and log_w = 0, r is exactly 1 and the parameters, moments and grads[0] are those of gbnf_trainer_nll_step bit for bit
+ * on a deterministic trainer (nll agrees to rounding: f32 G summed here, f64 terms there).
+ * workspace: gbnf_mixture_step_workspace_bytes of DEVICE memory, 256-byte aligned: per component z (n, d) and a trace of
+ * gbnf_trainer_trace_floats -- C traces, not one: a single forward per component is bought with about 20 KB per sample and
+ * component for MINIBOONE K = 5, depth 1 -- then ldj, ll (C, n), r (C, n), G, ONE g_z / g_ldj and ONE backward workspace (the
+ * largest gbnf_trainer_workspace_bytes) reused across components, and the partial sums.  The size depends on the trainers'
+ * deterministic mode as gbnf_trainer_workspace_bytes does.
+ * With every trainer in deterministic mode (gbnf_trainer_set_deterministic) everything the call writes -- the parameters, the
+ * moments, grads, stats_dev, G and r -- is bit-identical from run to run.
+ * Refused with nothing launched -- GBNF_ERR_INVALID: a null array, a null entry of trainers or grads, a null log_w / x / stats_dev /
+ * workspace, n_components outside [1, GBNF_WEIGHTS_MAX_COMPONENTS], n < 1, the same trainer twice, trainers of different d, what
+ * gbnf_trainer_apply_update refuses of any hypers[c], differing kind or max_grad_norm, a short workspace; GBNF_ERR_UNSUPPORTED: a
+ * trainer in batch-statistics mode (gbnf_trainer_set_batch_stats(0) first), and gbnf_trainer_backward's deterministic-mode refusals
+ * for any trainer.  gbnf_mixture_step_workspace_bytes refuses the same handle array, a null bytes and n < 1. */
+int gbnf_mixture_step_workspace_bytes(gbnf_trainer* const* trainers, int32_t n_components, int64_t n, int64_t* bytes);
+int gbnf_mixture_nll_step(gbnf_trainer* const* trainers, int32_t n_components, const float* log_w, const float* x, int64_t n,
+                          float* const* grads, float* const* exp_avg, float* const* exp_avg_sq, const gbnf_opt_hyper* hypers,
+                          float* stats_dev, float* G_or_null, float* r_or_null, void* workspace, int64_t workspace_bytes,
+                          void* stream);
+
 #ifdef __cplusplus
 }
 #endif
