@@ -35,6 +35,8 @@ import torch.nn as nn
 
 from . import native
 from . import spec as gspec
+# (the three flag readers are re-exported: they are defined next to the base only to avoid an import cycle, see boosted_base.py)
+from .boosted_base import BoostedMixtureBase, deterministic_from, image_deterministic_from, image_eval_deterministic_from  # noqa: F401
 
 
 # ----------------------------------------------------------------------------- parameter holders
@@ -349,41 +351,10 @@ class _FlowFunction(torch.autograd.Function):
         return (None, g_x) + tuple(out)
 
 
-def deterministic_from(args, env=None):
-    """The deterministic-mode flag of a module: ``args.deterministic`` (a bool, or None / absent = not given), else the environment
-    variable GBNF_DETERMINISTIC ("1" / "0"; unset or empty = off).  Anything else raises ValueError."""
-    return _flag_from(args, env, "deterministic", "GBNF_DETERMINISTIC")
-
-
-def image_deterministic_from(args, env=None):
-    """The deterministic-mode flag of an IMAGE module's trainers (image_glow.BoostedImageFlow.image_deterministic):
-    ``args.image_deterministic``, else the environment variable GBNF_IMAGE_DETERMINISTIC; the rules of ``deterministic_from``."""
-    return _flag_from(args, env, "image_deterministic", "GBNF_IMAGE_DETERMINISTIC")
-
-
-def image_eval_deterministic_from(args, env=None):
-    """The deterministic-mode flag of an IMAGE module's evaluation handles (image_glow.BoostedImageFlow.image_eval_deterministic):
-    ``args.image_eval_deterministic``, else the environment variable GBNF_IMAGE_EVAL_DETERMINISTIC; the rules of
-    ``deterministic_from``.  A flag of its own: it reads neither of the other two and they do not read it."""
-    return _flag_from(args, env, "image_eval_deterministic", "GBNF_IMAGE_EVAL_DETERMINISTIC")
-
-
-def _flag_from(args, env, attr, var):
-    given = getattr(args, attr, None)
-    if given is not None:
-        if not isinstance(given, (bool, int)) or given not in (0, 1, True, False):
-            raise ValueError(f"{attr} must be a bool, got {given!r}")
-        return bool(given)
-    text = (os.environ if env is None else env).get(var, "")
-    if text in ("", "0"):
-        return False
-    if text == "1":
-        return True
-    raise ValueError(f"{var} must be 0 or 1, got {text!r}")
-
-
-class BoostedFlow(nn.Module):
+class BoostedFlow(BoostedMixtureBase):
     """Drop-in for models/boosted_flow.py:BoostedFlow on the density-evaluation path."""
+
+    _CACHES = ("_tensor_cache", "_perm_cache", "_key_cache", "_prior_cache", "_component_table", "_component_meta")
 
     def __new__(cls, args=None, *a, **k):
         # image components (len(input_size) > 1, BASELINE.json configs[3]) live in image_glow.BoostedImageFlow
@@ -393,36 +364,17 @@ class BoostedFlow(nn.Module):
         return super().__new__(cls)
 
     def __init__(self, args):
-        super().__init__()
-        self.args = args
         # arithmetic of the training path (native.NativeTrainer): args.train_math, else env GBNF_TRAIN_MATH, else the fast
         # saturating "f16x3"; "bf16x6" is the range-safe trainer, "repair" f16x3 with a same-call bf16x6 re-run of a step that met the
         # range.  Checked here, before any device work.
         train_math = getattr(args, "train_math", None) or os.environ.get("GBNF_TRAIN_MATH") or "f16x3"
         if train_math not in native.NativeTrainer.TRAIN_MATH:
             raise ValueError(f"train_math must be one of {sorted(native.NativeTrainer.TRAIN_MATH)}, got {train_math!r}")
+        # (`deterministic` -- gbnf_trainer_set_deterministic -- is applied to every trainer native_trainer() hands out; an unsupported
+        # geometry is refused by the first training call)
+        super().__init__(args)
         self.train_math = train_math
-        # bit-reproducible training steps (gbnf_trainer_set_deterministic): args.deterministic, else env GBNF_DETERMINISTIC, else off.
-        # Applied to every trainer native_trainer() hands out; an unsupported geometry is refused by the first training call.
-        self.deterministic = deterministic_from(args)
-        self.num_flows = args.num_flows
-        self.z_size = args.z_size
-        self.density_evaluation = args.density_evaluation
         self.amortized = not args.density_evaluation
-        self.all_trained = False
-        self.component_type = args.component_type
-        self.num_components = args.num_components
-        self.component = 0
-        # GenerativeFlow buffers (models/generative_flow.py:22-23)
-        self.register_buffer("base_dist_mean", torch.randn(self.z_size).normal_(0, 0.1))
-        self.register_buffer("base_dist_var", 3.0 * torch.ones(self.z_size))
-        # rho (models/boosted_flow.py:32-39)
-        if args.rho_init == "decreasing":
-            rho = torch.clamp(1.0 / torch.pow(2.0, torch.arange(self.num_components * 1.0)), min=0.05)
-        else:
-            rho = torch.full((self.num_components,), 1.0 / self.num_components)
-        self.register_buffer("rho", rho.float())
-        self.flows = nn.ModuleList()
         for c in range(self.num_components):
             if args.component_type == "realnvp":
                 self.flows.append(RealNVPFlow(args, flip_init=c))
@@ -430,9 +382,7 @@ class BoostedFlow(nn.Module):
                 self.flows.append(Glow(args))
             else:
                 raise NotImplementedError("Only glow and realnvp components are currently implemented")
-        self._handles = {}      # c -> (version key, NativeFlow)
         self._handles_exact = {}   # c -> (version key, exact-f32 NativeFlow), inverse direction only
-        self._trainers = {}        # c -> (address key, NativeTrainer), calls recorded by autograd
         self._mixture = None    # (version key, NativeMixture)
         dev = getattr(args, "device", None)
         if dev is not None:
@@ -443,35 +393,6 @@ class BoostedFlow(nn.Module):
     def base_dist(self):
         import torch.distributions as D
         return D.Normal(self.base_dist_mean, self.base_dist_var)
-
-    def increment_component(self):
-        """models/boosted_flow.py:52-59."""
-        if self.component == self.num_components - 1:
-            self.component = 0
-            self.all_trained = True
-        else:
-            self.component = min(self.component + 1, self.num_components - 1)
-
-    def _sample_component(self, sampling_components):
-        """models/boosted_flow.py:61-96: "c" | "1:c" | "1:c-1" | "-c" -> component id (draws
-        torch.multinomial over rho for the ranged forms)."""
-        if sampling_components == "c":
-            return min(self.component, self.num_components - 1)
-        if sampling_components in ("1:c", "1:c-1"):
-            if sampling_components == "1:c-1":
-                n = self.component
-            else:
-                n = self.num_components if self.all_trained else self.component + 1
-            n = min(max(n, 1), self.num_components)
-            simplex = self.rho[0:n] / torch.sum(self.rho[0:n])
-            return int(torch.multinomial(simplex, 1, replacement=True).item())
-        if sampling_components == "-c":
-            simplex = self.rho.clone().detach()
-            simplex[self.component] = 0.0
-            simplex = simplex / simplex.sum()
-            return int(torch.multinomial(simplex, 1, replacement=True).item())
-        raise ValueError("z_k can only be sampled from ['c', '1:c-1', '1:c', '-c'] "
-                         "(corresponding to 'new', 'fixed', or new+fixed components)")
 
     def _prior_views(self, c, n):
         """Glow.prior / RealNVPFlow.prior: prior_h (zeros) repeated over the batch, returned as-is -- as broadcast VIEWS here
@@ -527,7 +448,7 @@ class BoostedFlow(nn.Module):
             z = torch.randn(n, self.z_size, device=dev, dtype=torch.float32, generator=generator) * t
         if uniforms is None:
             uniforms = torch.rand(n, device=dev, dtype=torch.float32, generator=generator)
-        self._check_ready(z)
+        self._require_device(z)
         z = z.contiguous().float()
         uniforms = uniforms.contiguous().float()
         if z.dim() != 2 or z.shape != (n, self.z_size) or uniforms.shape != (n,):
@@ -575,27 +496,16 @@ class BoostedFlow(nn.Module):
     @torch.no_grad()
     def _rho_gradients(self, x):
         """models/boosted_flow.py:119-139 (note: un-normalised rho in this recursion, as in the reference)."""
-        self._check_ready(x)
+        self._require_device(x)
         x = x.contiguous().float()
-        # the reference starts all three at zeros (:120-122): with component == 0 (second boosting pass, all_trained)
-        # new_ll and fixed_ll stay zero, the gradient is 0 and rho[0] is left where it is
-        full_ll = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
-        fixed_ll = torch.zeros_like(full_ll)
-        new_ll = torch.zeros_like(full_ll)
-        for c in range(self.component + 1):
-            self._ensure_actnorm(x, c)
-            with torch.cuda.device(x.device):     # ll_c = log N(z;0,I) + ldj straight from the flow kernel
-                _, _, ll = self.native_flow(c).forward(x, want_z=False, want_ldj=False, want_ll=True)
-            if c == 0:
-                full_ll = ll
-            else:
-                new_ll = ll
-                prev = torch.log(1 - self.rho[c]) + full_ll
-                nxt = torch.log(self.rho[c]) + new_ll
-                full_ll = torch.logsumexp(torch.stack([prev, nxt], dim=1), dim=1)
-            if c == self.component - 1:
-                fixed_ll = full_ll
-        return new_ll, fixed_ll, full_ll
+
+        def columns():
+            for c in range(self.component + 1):
+                self._ensure_actnorm(x, c)
+                with torch.cuda.device(x.device):     # ll_c = log N(z;0,I) + ldj straight from the flow kernel
+                    ll = self.native_flow(c).forward(x, want_z=False, want_ldj=False, want_ll=True)[2]
+                yield ll
+        return self._mixture_recursion(columns())
 
     def update_rho(self, data_loader, fused=False):
         """models/boosted_flow.py:141-207 (approximate branch).  The reference's log line references an
@@ -612,16 +522,12 @@ class BoostedFlow(nn.Module):
         if fused and self.component > 0:
             return self._update_rho_fused(data_loader)
         with torch.no_grad():
-            tolerance, min_iters = 0.001, 10
+            tolerance, min_iters = self.RHO_TOLERANCE, self.RHO_MIN_ITERS
             init_step, max_iters = self.args.rho_lr, self.args.rho_iters
             prev_rho = self.rho[self.component].item()
-            data_iter = iter(data_loader)
+            batches = self._cycle(data_loader)
             for batch_id in range(max_iters):
-                try:
-                    (x, _) = next(data_iter)
-                except StopIteration:
-                    data_iter = iter(data_loader)
-                    (x, _) = next(data_iter)
+                (x, _) = next(batches)
                 x = x.detach().to(self.rho.device)
                 g_ll, G_ll, _ = self._rho_gradients(x)
                 gradient = torch.mean((-g_ll) - (-G_ll)).item()
@@ -637,28 +543,16 @@ class BoostedFlow(nn.Module):
     def _update_rho_fused(self, data_loader):
         """The loop of ``update_rho`` on gbnf_mixture_rho_step, for ``self.component`` >= 1."""
         c = int(self.component)
-        tolerance, min_iters = 0.001, 10
-        init_step, max_iters = self.args.rho_lr, self.args.rho_iters
-        rho = self.rho
-        if rho.dtype != torch.float32 or not rho.is_contiguous():
-            raise ValueError("update_rho(fused=True) writes self.rho in place: it must be contiguous float32")
-        data_iter = iter(data_loader)
-        for batch_id in range(max_iters):
-            try:
-                (x, _) = next(data_iter)
-            except StopIteration:
-                data_iter = iter(data_loader)
-                (x, _) = next(data_iter)
+        rho = self._rho_in_place("update_rho(fused=True) writes")
+
+        def step(x, _, step_size):
             x = x.detach().to(rho.device).contiguous().float()
-            self._check_ready(x)
+            self._require_device(x)
             for k in range(c + 1):
                 self._ensure_actnorm(x, k)
             with torch.cuda.device(x.device):
-                stats = self.native_mixture(c + 1).rho_step(x, c, rho, init_step / (0.05 * batch_id + 1))
-            # the kernel wrote rho behind autograd's back: move its version counter as training_step does for parameters
-            torch.autograd.graph.increment_version([rho])
-            if batch_id > min_iters and (batch_id > max_iters or stats.tolist()[3] < tolerance):
-                break
+                return self.native_mixture(c + 1).rho_step(x, c, rho, step_size)
+        self._rho_loop(data_loader, step)
 
     # ------------------------------------------------------------------ native handles
     def _component_tensors(self, c):
@@ -707,13 +601,8 @@ class BoostedFlow(nn.Module):
         except Exception:                      # (no library / no device: the calls that need them raise on their own)
             return None
 
-    def _apply(self, fn, *a, **k):
-        for name in ("_tensor_cache", "_perm_cache", "_key_cache", "_prior_cache", "_component_table", "_component_meta"):
-            self.__dict__.pop(name, None)
-        return super()._apply(fn, *a, **k)
-
     def load_state_dict(self, *a, **k):
-        for name in ("_tensor_cache", "_perm_cache", "_key_cache", "_prior_cache", "_component_table", "_component_meta"):      # (assign=True swaps tensor objects)
+        for name in self._CACHES:      # (assign=True swaps tensor objects)
             self.__dict__.pop(name, None)
         return super().load_state_dict(*a, **k)
 
@@ -744,10 +633,6 @@ class BoostedFlow(nn.Module):
         """Drop the per-component tensor look-ups of the key (a key mismatch may mean a tensor OBJECT was replaced)."""
         for name in ("_key_cache", "_perm_cache", "_tensor_cache"):
             self.__dict__.get(name, {}).pop(c, None)
-
-    def _check_ready(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise native.GbnfError("x must live on the MI355X (cuda) device: this module has no CPU path")
 
     def _needs_grad(self, x, c):
         """True when the call must be recorded by autograd: TRAIN mode, gradients enabled and the input or a parameter
@@ -849,7 +734,7 @@ class BoostedFlow(nn.Module):
     def verify_numerics(self, x, components=None, rows=256):
         """Largest relative log-likelihood difference between the packing each component runs on and its bf16x6 packing,
         on (the first `rows` rows of) x; components beyond NUMERICS_TOL are re-packed as bf16x6 from now on."""
-        self._check_ready(x)
+        self._require_device(x)
         xs = x[:rows].contiguous().float()
         comps = range(self.num_components) if components is None else components
         worst = 0.0
@@ -926,7 +811,7 @@ class BoostedFlow(nn.Module):
     def component_forward(self, x, c, differentiable=None):
         """x (N,d) -> z (N,d), ldj (N,) of component c  ==  self.flows[c](x)[0], [3] of the reference.
         ``differentiable``: None = recorded by autograd in train mode only (see ``_needs_grad``); True / False force it."""
-        self._check_ready(x)
+        self._require_device(x)
         x_in = x
         x = x.contiguous().float()
         self._ensure_actnorm(x, int(c))
@@ -969,7 +854,7 @@ class BoostedFlow(nn.Module):
         (gbnf_boosted_nll_step: mixture log-density, weights, inverse-CDF resample on these uniforms, the step); the result gains ``ess``,
         the effective sample size of the weights, and all five entries are views of one stats tensor.  The first component has nothing
         to resample from and ignores it."""
-        self._check_ready(x)
+        self._require_device(x)
         c = int(self.component)
         x = x.contiguous().float()
         self._ensure_actnorm(x, c)
@@ -1202,7 +1087,7 @@ class BoostedFlow(nn.Module):
 
     def component_inverse(self, z, c):
         """z (N,d) -> x (N,d), log|det dx/dz| (N,) of component c: inverse of ``component_forward``."""
-        self._check_ready(z)
+        self._require_device(z)
         z = z.contiguous().float()
         if not all(bool(l.actnorm.inited) for l in getattr(getattr(self.flows[int(c)], "flow", None), "layers", [])):
             raise ValueError("ActNorm not initiated: run a forward pass on data first (models/layers.py:473-475)")
@@ -1213,7 +1098,7 @@ class BoostedFlow(nn.Module):
     def component_log_prob(self, x, n_used=None):
         """(N, C_used): ll_c(x) = log N(z_c;0,I) + ldj_c for c < n_used, all in ONE launch
         (density_experiment.py:562-565)."""
-        self._check_ready(x)
+        self._require_device(x)
         n_used = self._n_used(n_used)
         x = x.contiguous().float()
         for c in range(n_used):
@@ -1229,7 +1114,7 @@ class BoostedFlow(nn.Module):
         reference's ``evaluate`` (density_experiment.py:562), and ALL components once ``all_trained`` -- a deliberate
         divergence: the reference keeps ``range(self.component + 1)`` there too, which after the last boosting pass
         (component reset to 0) evaluates only the first component; pass ``n_used`` to reproduce that."""
-        self._check_ready(x)
+        self._require_device(x)
         n_used = self._n_used(n_used)
         x = x.contiguous().float()
         for c in range(n_used):
@@ -1262,7 +1147,7 @@ class BoostedFlow(nn.Module):
         state = None
         for (x, _) in data_loader:
             x = x.detach().to(dev)
-            self._check_ready(x)
+            self._require_device(x)
             x = x.contiguous().float()
             for k in range(n_used):
                 self._ensure_actnorm(x, k)
@@ -1271,14 +1156,11 @@ class BoostedFlow(nn.Module):
                 if state is None:
                     state = native.eval_state(x.device)
                 self.native_mixture(n_used).evaluate(x, c, rho, state, n_used=n_used)
-        s = None if state is None else state.tolist()          # the one host read
-        if s is None or s[0] == 0:
-            raise ValueError("evaluate: the loader yielded no rows")
-        S = native.EVAL_STATE
-        rows, batches = s[S["rows"]], s[S["batches"]]
-        out = {"nll": -s[S["sum_G"]] / rows, "g_nll": -s[S["sum_g"]] / rows, "ratio": s[S["sum_G_minus_g"]] / rows,
-               "expected_component_nll": -s[S["sum_E"]] / rows, "nll_batch_mean": -s[S["batch_mean_G"]] / batches,
-               "rows": int(rows), "batches": int(batches), "non_finite_rows": int(s[S["non_finite_rows"]])}
+        s = self._eval_sums(state)          # the one host read
+        rows, batches = s["rows"], s["batches"]
+        out = {"nll": -s["sum_G"] / rows, "g_nll": -s["sum_g"] / rows, "ratio": s["sum_G_minus_g"] / rows,
+               "expected_component_nll": -s["sum_E"] / rows, "nll_batch_mean": -s["batch_mean_G"] / batches,
+               "rows": int(rows), "batches": int(batches), "non_finite_rows": int(s["non_finite_rows"])}
         if c == 0 and not self.all_trained:
             out["g_nll"], out["ratio"] = out["nll"], 0.0
         return out
@@ -1301,43 +1183,21 @@ class BoostedFlow(nn.Module):
         Default ``n_used`` as ``log_prob``.  An empty loader, or a rho with a negative or non-finite entry, raises ValueError."""
         self.eval()
         n_used = self._n_used(n_used)
-        if n_used > native.WEIGHTS_MAX_COMPONENTS:
-            raise ValueError(f"fit_weights handles up to {native.WEIGHTS_MAX_COMPONENTS} components, got n_used = {n_used}")
-        rho = self.rho
-        if rho.dtype != torch.float32 or not rho.is_contiguous():
-            raise ValueError("fit_weights reads (and with write=True writes) self.rho in place: it must be contiguous float32")
-        dev = rho.device
-        try:
-            capacity = len(data_loader.dataset)
-        except (AttributeError, TypeError):
-            capacity = None
-        table, filled, pieces = None, 0, []
-        for (x, _) in data_loader:
-            x = x.detach().to(dev)
-            self._check_ready(x)
-            x = x.contiguous().float()
-            if x.shape[0] == 0:
-                continue
+
+        def batch_table(x, _, table, filled):
             for k in range(n_used):
                 self._ensure_actnorm(x, k)
             self._guard(x, range(n_used))
-            with torch.cuda.device(dev):
+            with torch.cuda.device(x.device):
                 mix = self.native_mixture(n_used)
-                if capacity is None:
-                    pieces.append(mix.component_log_prob(x, 0, n_used))
-                else:
-                    table = native.weights_table_room(table, n_used, capacity, filled, x.shape[0], dev)
-                    mix.prepared_component_log_prob(x, table, 0, n_used, col_offset=filled)(native._stream_ptr())
-            filled += x.shape[0]
-        if filled == 0:
-            raise ValueError("fit_weights: the loader yielded no rows")
-        if capacity is None:
-            table = pieces[0] if len(pieces) == 1 else torch.cat(pieces, dim=1)
-        return native.fit_weights_on_table(table[:, :filled], rho, n_used, max_iters, tol, write)
+                if table is None:
+                    return mix.component_log_prob(x, 0, n_used)
+                mix.prepared_component_log_prob(x, table, 0, n_used, col_offset=filled)(native._stream_ptr())
+        return self._fit_weights_over(data_loader, n_used, batch_table, max_iters, tol, write)
 
     # ---- the score: grad_x log p(x) of a component and of the mixture (gbnf_mixture_score), eval or train mode alike
     def _score_input(self, x, comps):
-        self._check_ready(x)
+        self._require_device(x)
         x = x.detach().contiguous().float()
         if x.dim() != 2:
             raise ValueError(f"x must be (N, d), got {tuple(x.shape)}")
@@ -1345,10 +1205,6 @@ class BoostedFlow(nn.Module):
             if not all(bool(l.actnorm.inited) for l in getattr(getattr(self.flows[c], "flow", None), "layers", [])):
                 raise ValueError("ActNorm not initiated: run a forward pass on data first (models/layers.py:473-475)")
         return x
-
-    def _log_w(self, n_used):
-        rho = self.rho[:n_used].detach().float()
-        return torch.log(rho / rho.sum()).contiguous()
 
     def _mixture_score(self, x, comps, log_w, ll, want_r):
         """One gbnf_mixture_score call on the trainers of ``comps``, on RUNNING statistics whatever the module's mode: the trainers'
@@ -1374,9 +1230,7 @@ class BoostedFlow(nn.Module):
         """-> (g_x (N,d), ll (N,)): the score grad_x ll_c(x) of component c and its log-density ll_c = log N(z_c;0,I) + ldj_c, from the
         training-path kernels on the live parameters with no weight gradient computed.  Running statistics in either module mode;
         nothing is recorded for autograd.  Uninitialised ActNorms raise ValueError as ``component_inverse``."""
-        c = int(c)
-        if not 0 <= c < self.num_components:
-            raise ValueError(f"c={c} is no component of this model (0 .. {self.num_components - 1})")
+        c = self._check_component(c)
         x = self._score_input(x, [c])
         with torch.cuda.device(x.device):
             g_x, ll, _ = self._mixture_score(x, [c], torch.zeros(1, dtype=torch.float32, device=x.device), None, False)
@@ -1397,8 +1251,7 @@ class BoostedFlow(nn.Module):
         with torch.cuda.device(x.device):
             ll = self.native_mixture(n_used).component_log_prob(x, 0, n_used)
             g_x, G, r = self._mixture_score(x, list(range(n_used)), self._log_w(n_used), ll, bool(return_responsibilities))
-        out = (g_x,) + ((G,) if return_log_prob else ()) + ((r.t(),) if return_responsibilities else ())
-        return out[0] if len(out) == 1 else out
+        return self._score_result(g_x, G, r, return_log_prob, return_responsibilities)
 
     @torch.no_grad()
     def responsibilities(self, x, n_used=None):
@@ -1437,14 +1290,6 @@ class BoostedFlow(nn.Module):
             raise FloatingPointError(f"{n} wave(s) met a split-f16 operand beyond +-65504: {n - n_train} of evaluation launches (repaired on "
                                      f"the device), {n_train} of training launches (saturated: gradients of those samples are wrong) -- "
                                      "normalise the inputs")
-
-    def _n_used(self, n_used):
-        if n_used is None:
-            n_used = self.num_components if self.all_trained else self.component + 1
-        n_used = int(n_used)
-        if not 1 <= n_used <= self.num_components:
-            raise ValueError(f"n_used={n_used} outside [1, {self.num_components}]")
-        return n_used
 
     # ------------------------------------------------------------------ checkpoint side-car (fixes S5)
     def permutation_state(self):

@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from . import native
+from .boosted_base import BoostedMixtureBase, image_deterministic_from, image_eval_deterministic_from
 
 
 def _no_eager(*a, **k):
@@ -401,15 +402,16 @@ class _ImageFlowInputGradFunction(torch.autograd.Function):
         return (None, g_x, None, None) + tuple(views[p].view_as(t) for p, t in zip(ctx.paths, tensors))
 
 
-class BoostedImageFlow(nn.Module):
+class BoostedImageFlow(BoostedMixtureBase):
     """models/boosted_flow.py:BoostedFlow for image components: density evaluation, z -> x, and (train mode, gradients enabled) the
     differentiable forward of one component."""
 
+    _CACHES = ("_tensor_cache",)
+
     def __init__(self, args):
-        super().__init__()
         if args.component_type != "glow":
             raise NotImplementedError("image components are Glow (models/boosted_flow.py:44-50 builds nothing else for images)")
-        self.args = args
+        super().__init__(args)
         # Two flags.  `deterministic` (BoostedFlow: args.deterministic / env GBNF_DETERMINISTIC) was defined when only the tabular
         # trainer had ordered sums: an image module that carries it builds and evaluates as ever and its first TRAINING call is
         # refused (native_trainer) -- behaviour the suite pins.  `image_deterministic` (args.image_deterministic / env
@@ -420,50 +422,12 @@ class BoostedImageFlow(nn.Module):
         # EVALUATION handles' ordered log-det sums (gbnf_image_flow_set_deterministic) and is applied to every handle native_flow()
         # hands out: component_forward (eval), component_log_prob, log_prob, forward(y_onehot=...), update_rho, _rho_gradients and
         # the fixed-mixture term of training_step(fixed=...) then repeat bit for bit.  It reads neither of the other two.
-        from .boosted_flow import deterministic_from, image_deterministic_from, image_eval_deterministic_from
-        self.deterministic = deterministic_from(args)
         self.image_deterministic = image_deterministic_from(args)
         self.image_eval_deterministic = image_eval_deterministic_from(args)
-        self.num_flows, self.z_size = args.num_flows, args.z_size
-        self.density_evaluation = args.density_evaluation
-        self.all_trained, self.component_type = False, args.component_type
-        self.num_components, self.component = args.num_components, 0
-        self.register_buffer("base_dist_mean", torch.randn(self.z_size).normal_(0, 0.1))
-        self.register_buffer("base_dist_var", 3.0 * torch.ones(self.z_size))
-        if args.rho_init == "decreasing":
-            rho = torch.clamp(1.0 / torch.pow(2.0, torch.arange(self.num_components * 1.0)), min=0.05)
-        else:
-            rho = torch.full((self.num_components,), 1.0 / self.num_components)
-        self.register_buffer("rho", rho.float())
-        self.flows = nn.ModuleList([ImageGlow(args) for _ in range(self.num_components)])
-        self._handles = {}
-        self._trainers = {}
+        self.flows.extend(ImageGlow(args) for _ in range(self.num_components))
         dev = getattr(args, "device", None)
         if dev is not None:
             self.to(dev)
-
-    # ---- reference API
-    def increment_component(self):
-        if self.component == self.num_components - 1:
-            self.component, self.all_trained = 0, True
-        else:
-            self.component = min(self.component + 1, self.num_components - 1)
-
-    def _sample_component(self, sampling_components):
-        """models/boosted_flow.py:61-96."""
-        if sampling_components == "c":
-            return min(self.component, self.num_components - 1)
-        if sampling_components in ("1:c", "1:c-1"):
-            n = self.component if sampling_components == "1:c-1" else (
-                self.num_components if self.all_trained else self.component + 1)
-            n = min(max(n, 1), self.num_components)
-            simplex = self.rho[0:n] / torch.sum(self.rho[0:n])
-            return int(torch.multinomial(simplex, 1, replacement=True).item())
-        if sampling_components == "-c":
-            simplex = self.rho.clone().detach()
-            simplex[self.component] = 0.0
-            return int(torch.multinomial(simplex / simplex.sum(), 1, replacement=True).item())
-        raise ValueError("z_k can only be sampled from ['c', '1:c-1', '1:c', '-c']")
 
     def _component_tensors(self, c):
         """(parameters, buffers, Permute2d modules, ActNorm modules) of component c, collected once: walking the module
@@ -474,10 +438,6 @@ class BoostedImageFlow(nn.Module):
             cache[c] = (list(flow.parameters()), list(flow.buffers()),
                         [m for m in flow.modules() if isinstance(m, Permute2d)], list(flow._actnorms()))
         return cache[c]
-
-    def _apply(self, fn, *a, **k):
-        self.__dict__.pop("_tensor_cache", None)
-        return super()._apply(fn, *a, **k)
 
     def native_flow(self, c):
         flow = self.flows[c]
@@ -496,10 +456,6 @@ class BoostedImageFlow(nn.Module):
             handle._eval_deterministic = want
         return handle
 
-    def _check(self, x):
-        if not isinstance(x, torch.Tensor) or not x.is_cuda:
-            raise native.GbnfError("x must live on the MI355X (cuda) device: this module has no CPU path")
-
     def _y(self, c, y_onehot, n=None):
         """``y_onehot`` as component c's kernels take it: (n, y_classes) contiguous float32 on the device; None for an unconditional
         component (which ignores the argument, as the reference does).  A class-conditional one refuses None (the reference asserts)."""
@@ -508,7 +464,7 @@ class BoostedImageFlow(nn.Module):
             return None
         if y_onehot is None:
             raise ValueError("this model is class-conditional (y_condition): y_onehot is required")
-        self._check(y_onehot)
+        self._require_device(y_onehot)
         if y_onehot.dim() != 2 or y_onehot.shape[1] != int(flow.y_classes) or (n is not None and y_onehot.shape[0] != n):
             raise ValueError(f"y_onehot must be ({'n' if n is None else n}, {int(flow.y_classes)}), got {tuple(y_onehot.shape)}")
         return y_onehot.contiguous().float()
@@ -699,7 +655,7 @@ class BoostedImageFlow(nn.Module):
         the prior is per image, and the six tensors of ``project_ycond`` / ``project_class`` are updated too
         (gbnf_image_trainer_nll_step_y).  The result gains ``loss_classes`` (the mean cross-entropy, unweighted) and ``class_correct``
         (rows whose largest logit is at argmax y).  A ``fixed`` component is evaluated with the same ``y_onehot``."""
-        self._check(x)
+        self._require_device(x)
         if x.requires_grad:
             raise NotImplementedError("the image training path has no gradient with respect to x")
         c = int(self.component)
@@ -801,7 +757,7 @@ class BoostedImageFlow(nn.Module):
         (z, z_mu, z_var, ldj, y_logits) with the (n,Cz,1,1) priors expanded as views -- its ll under that prior is
         ``component_log_prob``'s.  ``input_grad`` (a recorded call only): an ``x`` that requires grad gets its gradient from
         ``backward()`` as well (the noise held fixed); without the keyword such an x is refused as ever."""
-        self._check(x)
+        self._require_device(x)
         y = self._y(int(c), y_onehot, x.shape[0])
         if self._recording(int(c)):
             xx = x if x.requires_grad else x.contiguous().float()
@@ -826,7 +782,7 @@ class BoostedImageFlow(nn.Module):
         the largest over the components; math_mode and demoted belong to the handles (a failed check of either direction sends a
         handle to exact f32): "f32" as soon as one component runs there."""
         inverse = native.check_direction(direction) == "inverse"
-        n_used = self.num_components if n_used is None else int(n_used)
+        n_used = self._n_used(n_used, "all")
         checks, worst, demoted, mode, tol = 0, 0.0, False, None, 0.0
         for c in range(n_used):
             h = self.native_flow(c)
@@ -881,11 +837,11 @@ class BoostedImageFlow(nn.Module):
     # ---- the component as the bijection it is: x -> (z, eps) -> x (gbnf_image_flow_encode / gbnf_image_flow_inverse) on the evaluation
     # handles, no gradients.  ``noise`` None: no dequantisation noise is added (u = 255 x / 256), so the calls are deterministic.
     def _latent_args(self, x, components, noise):
-        self._check(x)
+        self._require_device(x)
         c = self._sample_component(components) if isinstance(components, str) else int(components)
         x = x.contiguous().float()
         if noise is not None:
-            self._check(noise)
+            self._require_device(noise)
             noise = noise.contiguous().float()
         return c, x, noise
 
@@ -912,7 +868,7 @@ class BoostedImageFlow(nn.Module):
         """Latent interpolation between two batches of images: (len(weights), n, C, H, W), entry k the decode at temperature 1 of
         (1 - w_k) (z, eps)(x_a) + w_k (z, eps)(x_b) -- linear in the full latent; weights 0 and 1 return the two reconstructions."""
         c, x_a, noise = self._latent_args(x_a, components, noise)
-        self._check(x_b)
+        self._require_device(x_b)
         x_b = x_b.contiguous().float()
         if x_b.shape != x_a.shape:
             raise ValueError(f"x_a and x_b must have one shape, got {tuple(x_a.shape)} and {tuple(x_b.shape)}")
@@ -953,11 +909,7 @@ class BoostedImageFlow(nn.Module):
         ``native_flow(c).inverse`` call, gathered and written back by torch indexing.  Defaults: n = ``sample_size``, e / eps / uniforms
         from ``generator``, n_used = the trained components.  Returns x (n,C,H,W), and ``comp`` (n,) int32 with ``return_components``.
         A class-conditional model needs ``y_onehot`` (n, y_classes): row i is drawn from its component's prior of ``y_onehot[i]``."""
-        if n_used is None:
-            n_used = self.num_components if self.all_trained else self.component + 1
-        n_used = int(n_used)
-        if not 1 <= n_used <= self.num_components:
-            raise ValueError(f"n_used={n_used} outside [1, {self.num_components}]")
+        n_used = self._n_used(n_used)
         temperature = 1.0 if temperature is None else float(temperature)
         dev = self.rho.device
         handles = [self.native_flow(c) for c in range(n_used)]
@@ -972,7 +924,7 @@ class BoostedImageFlow(nn.Module):
             eps = [torch.randn((n,) + sh, device=dev, dtype=torch.float32, generator=generator) for sh in handles[0].split_shapes()]
         if uniforms is None:
             uniforms = torch.rand(n, device=dev, dtype=torch.float32, generator=generator)
-        self._check(e)
+        self._require_device(e)
         if y is not None and y.shape[0] != n:
             raise ValueError(f"y_onehot must have {n} rows, got {y.shape[0]}")
         if e.shape != (n,) + tuple(handles[0].z_shape) or uniforms.shape != (n,) or any(t.shape[0] != n for t in eps):
@@ -999,7 +951,7 @@ class BoostedImageFlow(nn.Module):
         if reverse:
             return self.decode(z, y_onehot, temperature, components)
         c = self._sample_component(components) if isinstance(components, str) else int(components)
-        self._check(x)
+        self._require_device(x)
         if self._recording(c) or self.flows[c].y_condition:
             return self.component_forward(x, c, y_onehot=y_onehot)
         zz, ldj, _ = self.component_forward(x, c)
@@ -1049,7 +1001,7 @@ class BoostedImageFlow(nn.Module):
         ``fused=True``: the whole component in ONE library call on its trainer's live tensors (gbnf_image_trainer_actnorm_init: one
         walk of the forward, statistics in f64 in a fixed order, bias / logs written on the device, no host round trip per layer);
         the trainer stays cached for the ``training_step`` that follows.  Every ActNorm2d of the component must have one ``scale``."""
-        self._check(x)
+        self._require_device(x)
         x = x.contiguous().float()
         noise = torch.rand_like(x) if noise is None else noise.contiguous().float()
         comps = range(self.num_components) if components is None else ([int(components)] if isinstance(components, int) else list(components))
@@ -1084,12 +1036,12 @@ class BoostedImageFlow(nn.Module):
         """(N, C_used): ll_c = log_normal_diag(z, z_mu, z_var) + logdet (image_experiment.py:227); the SAME noise for every
         component unless the caller passes one per call.  A class-conditional model needs ``y_onehot`` (N, y_classes): ll_c is
         taken under component c's prior of each row's y."""
-        n_used = self.num_components if n_used is None else int(n_used)
+        n_used = self._n_used(n_used, "all")
         if noise is None:
             noise = torch.rand_like(x.float())
         y = self._y(0, y_onehot, x.shape[0])
         if y is not None:                                # (one chain after the other on the current stream)
-            self._check(x)
+            self._require_device(x)
             x, noise = x.contiguous().float(), noise.contiguous().float()
             with torch.cuda.device(x.device):
                 return torch.stack([self.native_flow(c).forward(x, noise, want_z=False, y=y, want_logits=False)[2] for c in range(n_used)],
@@ -1098,7 +1050,7 @@ class BoostedImageFlow(nn.Module):
             return self.component_forward(x, 0, noise, want_z=False)[2].unsqueeze(1)
         # the components are independent until the recursion and a component is a chain of ~50 latency-bound launches:
         # one HIP stream per component lets the chains overlap (measured: +26 % at batch 64, +13 % at 256)
-        self._check(x)
+        self._require_device(x)
         x = x.contiguous().float()
         noise = noise.contiguous().float()
         streams = self.__dict__.setdefault("_streams", {})
@@ -1138,7 +1090,7 @@ class BoostedImageFlow(nn.Module):
         elif self.flows[0].y_condition:
             raise NotImplementedError("graphed_log_prob of a class-conditional model needs the rows' labels as a graph input: pass "
                                       "labels=True for f(x, noise, y_onehot) (or use log_prob(x, y_onehot=...))")
-        n_used = self.num_components if n_used is None else int(n_used)
+        n_used = self._n_used(n_used, "all")
         dev = self.rho.device
         state = {}
 
@@ -1195,14 +1147,14 @@ class BoostedImageFlow(nn.Module):
 
     # ---- the score: grad_x log p(x) of a component and of the mixture (gbnf_image_mixture_score), eval or train mode
     def _score_call(self, x, comps, log_w, noise, y_onehot, want_r):
-        self._check(x)
+        self._require_device(x)
         x = x.detach().contiguous().float()
         if x.dim() != 4 or tuple(x.shape[1:]) != tuple(self.flows[0].input_size):
             raise ValueError(f"x must be (n, {tuple(self.flows[0].input_size)}), got {tuple(x.shape)}")
         if noise is None:
             noise = torch.rand_like(x)
         else:
-            self._check(noise)
+            self._require_device(noise)
             if noise.shape != x.shape:
                 raise ValueError(f"noise must have the shape of x, got {tuple(noise.shape)}")
             noise = noise.detach().contiguous().float()
@@ -1211,19 +1163,11 @@ class BoostedImageFlow(nn.Module):
             trainers = [self._step_trainer(c)[0] for c in comps]
             return native.image_mixture_score(trainers, log_w, x, noise, y=y, want_r=want_r)
 
-    def _score_n_used(self, n_used):
-        n_used = self.num_components if n_used is None else int(n_used)
-        if not 1 <= n_used <= self.num_components:
-            raise ValueError(f"n_used={n_used} is outside 1 .. {self.num_components}")
-        return n_used
-
     def component_score(self, x, c, noise=None, y_onehot=None):
         """-> (g_x like x, ll (N,)): the score grad_x ll_c(x) of component c and its log-density, from the exact-f32 training-path
         kernels on the live parameters with no weight gradient computed.  ``noise`` (drawn once when None) is held fixed: the
         gradient is that of the dequantised density at that noise.  Uninitialised ActNorms raise ValueError as ``training_step``."""
-        c = int(c)
-        if not 0 <= c < self.num_components:
-            raise ValueError(f"c={c} is no component of this model (0 .. {self.num_components - 1})")
+        c = self._check_component(c)
         g_x, ll, _ = self._score_call(x, [c], torch.zeros(1, dtype=torch.float32, device=x.device), noise, y_onehot, False)
         return g_x, ll
 
@@ -1231,12 +1175,9 @@ class BoostedImageFlow(nn.Module):
         """grad_x log p(x) of the mixture of the first ``n_used`` components, p = sum_c w_c p_c with w_c = rho_c / sum_{j < n_used} rho_j,
         in ONE library call: sum_c r_c grad_x ll_c with the responsibilities r_c = softmax_c(log w + ll).  ``noise`` (drawn once when
         None) is shared by the components and held fixed.  -> g_x, or (g_x[, log_prob (N,)][, responsibilities (N, C_used)])."""
-        n_used = self._score_n_used(n_used)
-        rho = self.rho[:n_used].detach().float()
-        g_x, G, r = self._score_call(x, list(range(n_used)), torch.log(rho / rho.sum()).contiguous(), noise, y_onehot,
-                                     bool(return_responsibilities))
-        out = (g_x,) + ((G,) if return_log_prob else ()) + ((r.t(),) if return_responsibilities else ())
-        return out[0] if len(out) == 1 else out
+        n_used = self._n_used(n_used, "all")
+        g_x, G, r = self._score_call(x, list(range(n_used)), self._log_w(n_used), noise, y_onehot, bool(return_responsibilities))
+        return self._score_result(g_x, G, r, return_log_prob, return_responsibilities)
 
     def responsibilities(self, x, n_used=None, noise=None, y_onehot=None):
         """(N, C_used): p(component c | x) under the mixture ``score`` differentiates."""
@@ -1250,8 +1191,8 @@ class BoostedImageFlow(nn.Module):
 
     def _class_tables(self, x, n_used, noise):
         """(C_used, N, Y) contiguous: component c's log p_c(x | y = k), one ``forward_classes`` per component on the current stream."""
-        n_used = self.num_components if n_used is None else int(n_used)
-        self._check(x)
+        n_used = self._n_used(n_used, "all")
+        self._require_device(x)
         if noise is None:
             noise = torch.rand_like(x.float())
         x, noise = x.contiguous().float(), noise.contiguous().float()
@@ -1304,22 +1245,8 @@ class BoostedImageFlow(nn.Module):
         """models/boosted_flow.py:119-139 -> (new_ll, fixed_ll, full_ll) device tensors, with the image path's own log-likelihood
         (``component_log_prob``: log_normal_diag(z, z_mu, z_var) + logdet; the reference's log_normal_standard(z, dim=-1) raises on a
         4-D z) and the reference's recursion: un-normalised rho, all three zeros where component 0 leaves them."""
-        self._check(x)
-        ll = self.component_log_prob(x, self.component + 1, noise)
-        full_ll = torch.zeros(x.shape[0], dtype=torch.float32, device=x.device)
-        fixed_ll = torch.zeros_like(full_ll)
-        new_ll = torch.zeros_like(full_ll)
-        for c in range(self.component + 1):
-            if c == 0:
-                full_ll = ll[:, 0]
-            else:
-                new_ll = ll[:, c]
-                prev = torch.log(1 - self.rho[c]) + full_ll
-                nxt = torch.log(self.rho[c]) + new_ll
-                full_ll = torch.logsumexp(torch.stack([prev, nxt], dim=1), dim=1)
-            if c == self.component - 1:
-                fixed_ll = full_ll
-        return new_ll, fixed_ll, full_ll
+        self._require_device(x)
+        return self._mixture_recursion(self.component_log_prob(x, self.component + 1, noise).unbind(1))
 
     @torch.no_grad()
     def update_rho(self, data_loader, noise_generator=None, labels=False):
@@ -1344,32 +1271,16 @@ class BoostedImageFlow(nn.Module):
                                       "no y (pass labels=True and a loader of (x, y_onehot))")
         self.eval()
         c = int(self.component)
-        rho = self.rho
-        if rho.dtype != torch.float32 or not rho.is_contiguous():
-            raise ValueError("update_rho writes self.rho in place: it must be contiguous float32")
+        rho = self._rho_in_place("update_rho writes")
         if c == 0:
             rho[0:1].clamp_(0.01, 100.0)
             return
-        tolerance, min_iters = 0.001, 10
-        init_step, max_iters = self.args.rho_lr, self.args.rho_iters
-        data_iter = iter(data_loader)
-        for batch_id in range(max_iters):
-            try:
-                (x, y) = next(data_iter)
-            except StopIteration:
-                data_iter = iter(data_loader)
-                (x, y) = next(data_iter)
-            x = x.detach().to(rho.device).contiguous().float()
-            self._check(x)
-            y = self._y(0, None if y is None else y.detach().to(rho.device), x.shape[0]) if labels else None
-            noise = torch.rand(x.shape, generator=noise_generator, device=x.device)
+
+        def step(x, y, step_size):
+            x, y, noise = self._loader_batch(x, y, labels, noise_generator)
             with torch.cuda.device(x.device):
-                stats = native.NativeImageFlow.rho_step([self.native_flow(k) for k in range(c + 1)], x, noise, c, rho,
-                                                        init_step / (0.05 * batch_id + 1), y=y)
-            # the kernel wrote rho behind autograd's back: move its version counter as training_step does for parameters
-            torch.autograd.graph.increment_version([rho])
-            if batch_id > min_iters and (batch_id > max_iters or stats.tolist()[3] < tolerance):
-                break
+                return native.NativeImageFlow.rho_step([self.native_flow(k) for k in range(c + 1)], x, noise, c, rho, step_size, y=y)
+        self._rho_loop(data_loader, step)
 
     # ---- the validation pass (image_experiment.py:296-337)
     @torch.no_grad()
@@ -1400,11 +1311,7 @@ class BoostedImageFlow(nn.Module):
             raise NotImplementedError("evaluate of a class-conditional model needs the rows' labels: gbnf_image_mixture_evaluate takes "
                                       "no y (pass labels=True and a loader of (x, y_onehot))")
         self.eval()
-        if n_used is None:
-            n_used = self.num_components if self.all_trained else self.component + 1
-        n_used, c = int(n_used), int(self.component)
-        if not 1 <= n_used <= self.num_components:
-            raise ValueError(f"n_used={n_used} outside [1, {self.num_components}]")
+        n_used, c = self._n_used(n_used), int(self.component)
         if c >= n_used:
             raise ValueError(f"component {c} is not among the first n_used = {n_used} components")
         if y_weight is None:
@@ -1415,10 +1322,7 @@ class BoostedImageFlow(nn.Module):
             rho = rho.contiguous().float()
         state, pixels = None, 0
         for (x, y) in data_loader:
-            x = x.detach().to(rho.device).contiguous().float()
-            self._check(x)
-            y = self._y(0, None if y is None else y.detach().to(rho.device), x.shape[0]) if labels else None
-            noise = torch.rand(x.shape, generator=noise_generator, device=x.device)
+            x, y, noise = self._loader_batch(x, y, labels, noise_generator)
             with torch.cuda.device(x.device):
                 if state is None:
                     state, pixels = native.eval_state(x.device), int(x[0].numel())
@@ -1429,19 +1333,16 @@ class BoostedImageFlow(nn.Module):
                     native.eval_accumulate(self.component_log_prob(x, n_used, noise).t().contiguous(), rho, c, state)
                 else:
                     native.NativeImageFlow.evaluate([self.native_flow(k) for k in range(n_used)], x, noise, c, rho, state, y=y)
-        s = None if state is None else state.tolist()          # the one host read
-        if s is None or s[0] == 0:
-            raise ValueError("evaluate: the loader yielded no rows")
-        S = native.EVAL_STATE
-        rows, batches = s[S["rows"]], s[S["batches"]]
+        s = self._eval_sums(state)          # the one host read
+        rows, batches = s["rows"], s["batches"]
         per_dim = 1.0 / (math.log(2.0) * pixels)
-        out = {"bpd": -s[S["sum_G"]] / rows * per_dim, "g_bpd": -s[S["sum_g"]] / rows * per_dim,
-               "expected_component_bpd": -s[S["sum_E"]] / rows * per_dim, "loss": -s[S["batch_mean_E"]] / batches * per_dim,
-               "rows": int(rows), "batches": int(batches), "non_finite_rows": int(s[S["non_finite_rows"]])}
+        out = {"bpd": -s["sum_G"] / rows * per_dim, "g_bpd": -s["sum_g"] / rows * per_dim,
+               "expected_component_bpd": -s["sum_E"] / rows * per_dim, "loss": -s["batch_mean_E"] / batches * per_dim,
+               "rows": int(rows), "batches": int(batches), "non_finite_rows": int(s["non_finite_rows"])}
         if labels:
-            out["loss"] += y_weight * s[S["batch_mean_ce"]] / batches
-            out["loss_classes"] = s[S["sum_ce"]] / rows
-            out["accuracy"] = s[S["sum_correct"]] / rows
+            out["loss"] += y_weight * s["batch_mean_ce"] / batches
+            out["loss_classes"] = s["sum_ce"] / rows
+            out["accuracy"] = s["sum_correct"] / rows
             out["total_loss"] = out["bpd"] + y_weight * out["loss_classes"]
         return out
 
@@ -1460,38 +1361,24 @@ class BoostedImageFlow(nn.Module):
             raise NotImplementedError("fit_weights of a class-conditional model needs the rows' labels (pass labels=True and a loader "
                                       "of (x, y_onehot))")
         self.eval()
-        if n_used is None:
-            n_used = self.num_components if self.all_trained else self.component + 1
-        n_used = int(n_used)
-        if not 1 <= n_used <= min(self.num_components, native.WEIGHTS_MAX_COMPONENTS):
-            raise ValueError(f"n_used={n_used} outside [1, {min(self.num_components, native.WEIGHTS_MAX_COMPONENTS)}]")
-        rho = self.rho
-        if rho.dtype != torch.float32 or not rho.is_contiguous():
-            raise ValueError("fit_weights reads (and with write=True writes) self.rho in place: it must be contiguous float32")
-        try:
-            capacity = len(data_loader.dataset)
-        except (AttributeError, TypeError):
-            capacity = None
-        table, filled, pieces = None, 0, []
-        for (x, y) in data_loader:
-            x = x.detach().to(rho.device).contiguous().float()
-            self._check(x)
-            if x.shape[0] == 0:
-                continue
-            y = self._y(0, None if y is None else y.detach().to(rho.device), x.shape[0]) if labels else None
-            noise = torch.rand(x.shape, generator=noise_generator, device=x.device)
+        n_used = self._n_used(n_used)
+
+        def batch_table(x, y, table, filled):
+            x, y, noise = self._loader_batch(x, y, labels, noise_generator)
             ll = self.component_log_prob(x, n_used, noise, y_onehot=y).t()
-            if capacity is None:
-                pieces.append(ll)
-            else:
-                table = native.weights_table_room(table, n_used, capacity, filled, x.shape[0], rho.device)
-                table[:, filled:filled + x.shape[0]].copy_(ll)
-            filled += x.shape[0]
-        if filled == 0:
-            raise ValueError("fit_weights: the loader yielded no rows")
-        if capacity is None:
-            table = torch.cat(pieces, dim=1)
-        return native.fit_weights_on_table(table[:, :filled], rho, n_used, max_iters, tol, write)
+            if table is None:
+                return ll
+            table[:, filled:filled + x.shape[0]].copy_(ll)
+        return self._fit_weights_over(data_loader, n_used, batch_table, max_iters, tol, write)
+
+    def _loader_batch(self, x, y, labels, noise_generator):
+        """A loader's ``(x, y)`` as the library calls take it: x contiguous float32 on rho's device, the labels checked with ``labels``
+        (None without), and the batch's ONE draw of dequantisation noise -> (x, y, noise)."""
+        dev = self.rho.device
+        x = x.detach().to(dev).contiguous().float()
+        self._require_device(x)
+        y = self._y(0, None if y is None else y.detach().to(dev), x.shape[0]) if labels else None
+        return x, y, torch.rand(x.shape, generator=noise_generator, device=x.device)
 
     # ---- checkpoint side-car (SURVEY.md S5 for image components)
     def _side_car_modules(self, c):

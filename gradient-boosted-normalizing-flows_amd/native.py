@@ -417,6 +417,90 @@ def _stream_ptr():
     return C.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
+# ---- the calling idiom: every entry point below hands tensors, handle lists, size queries and workspaces over with these
+def _ptr(t):
+    """A tensor's address as a void* (None: null; an empty tensor's address is null already)."""
+    return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+
+
+def _handle_array(objs):
+    """The ``handle``s of a list of library objects as a void*[]."""
+    return (C.c_void_p * len(objs))(*[o.handle for o in objs])
+
+
+def _addr_array(tensors):
+    """The addresses of a list of tensors (None: null) as a void*[]."""
+    return (C.c_void_p * len(tensors))(*[None if t is None else t.data_ptr() for t in tensors])
+
+
+def _query_i64(fn, *args):
+    """``fn(*args, &out)`` of a library call that reports one int64 (a size, a count): asked anew on every call."""
+    out = C.c_int64()
+    _check(fn(*args, C.byref(out)))
+    return int(out.value)
+
+
+def _workspace_arg(workspace, nbytes, device):
+    """The ``workspace`` argument of a call: None -> a new float32 buffer of ``nbytes()`` bytes (the size query runs only then);
+    anything else must be a contiguous device tensor (its size is checked by the library)."""
+    if workspace is None:
+        import torch
+        return torch.empty((nbytes() + 3) // 4, dtype=torch.float32, device=device)
+    return _check_workspace(workspace)
+
+
+def _check_workspace(workspace):
+    """A caller's workspace must be a contiguous device tensor (its size is checked by the library)."""
+    import torch
+    if not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
+        raise GbnfError("workspace must be a contiguous device tensor")
+    return workspace
+
+
+def _grown(buf, nbytes, device, dtype=None):
+    """A cached workspace for a call that needs ``nbytes``: ``buf`` itself while it is large enough and on ``device``, else a new one
+    (float32 unless ``dtype`` says otherwise).  The caller asks the library for ``nbytes`` on every call and keeps what it gets back.
+    (The three tabular training steps make the same test in line: their host time is counted in microseconds.)"""
+    if buf is None or buf.numel() * buf.element_size() < nbytes or buf.device != device:
+        import torch
+        dtype = torch.float32 if dtype is None else dtype
+        item = torch.finfo(dtype).bits // 8
+        buf = torch.empty((nbytes + item - 1) // item, dtype=dtype, device=device)
+    return buf
+
+
+def _check_noise(noise, x):
+    """The dequantisation noise of an image call: None, or a device tensor of x's shape."""
+    if noise is None:
+        return
+    _require_device_f32(noise, "noise")
+    if noise.shape != x.shape:
+        raise GbnfError("noise must have the shape of x")
+
+
+def _check_log_w(log_w, n_components):
+    _require_device_f32(log_w, "log_w")
+    if tuple(log_w.shape) != (n_components,):
+        raise GbnfError(f"log_w must be ({n_components},), got {tuple(log_w.shape)}")
+
+
+class _Handle:
+    """Owner of one library object: ``handle`` (a void*, None once closed) and ``_destroy``, the symbol that frees it."""
+
+    _destroy = None
+
+    def close(self):
+        if getattr(self, "handle", None):
+            getattr(lib(), self._destroy)(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
 def check_direction(direction):
     """``"forward"`` or ``"inverse"`` (which direction's on-data checks a numerics status reports); anything else: ValueError."""
     if direction not in ("forward", "inverse"):
@@ -424,8 +508,10 @@ def check_direction(direction):
     return direction
 
 
-class NativeFlow:
+class NativeFlow(_Handle):
     """One packed component on the device (gbnf_flow)."""
+
+    _destroy = "gbnf_flow_destroy"
 
     def __init__(self, spec, math="default", per_step_activation=False):
         """``per_step_activation``: pack for the kernel variants that read the activation per step although this
@@ -462,8 +548,7 @@ class NativeFlow:
         z = torch.empty_like(x) if want_z else None
         ldj = torch.empty(n, dtype=torch.float32, device=x.device) if want_ldj else None
         ll = torch.empty(n, dtype=torch.float32, device=x.device) if want_ll else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-        _check(lib().gbnf_flow_forward(self.handle, ptr(x), n, ptr(z), ptr(ldj), ptr(ll), _stream_ptr()))
+        _check(lib().gbnf_flow_forward(self.handle, _ptr(x), n, _ptr(z), _ptr(ldj), _ptr(ll), _stream_ptr()))
         return z, ldj, ll
 
     def inverse(self, z, want_ldj=True):
@@ -476,20 +561,8 @@ class NativeFlow:
         n = z.shape[0]
         x = torch.empty_like(z)
         ldj = torch.empty(n, dtype=torch.float32, device=z.device) if want_ldj else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
-        _check(lib().gbnf_flow_inverse(self.handle, ptr(z), n, ptr(x), ptr(ldj), _stream_ptr()))
+        _check(lib().gbnf_flow_inverse(self.handle, _ptr(z), n, _ptr(x), _ptr(ldj), _stream_ptr()))
         return x, ldj
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().gbnf_flow_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 def image_flow_desc_from_spec(spec):
@@ -541,11 +614,12 @@ def image_flow_desc_from_spec(spec):
     return desc, keep
 
 
-class NativeImageFlow:
+class NativeImageFlow(_Handle):
     """One packed image Glow component (gbnf_image_flow).  ``spec``: the image flow spec of ``synth.synth_image_glow_spec``
     / ``spec.image_spec_from_glow_module`` (numpy arrays)."""
 
-    y_classes = 0               # (class defaults: a plain handle, also for an object wrapped around a raw handle without __init__)
+    _destroy = "gbnf_image_flow_destroy"
+    y_classes = 0              # (class defaults: a plain handle, also for an object wrapped around a raw handle without __init__)
     has_class_head = False
 
     def __init__(self, spec, math="default"):
@@ -586,9 +660,7 @@ class NativeImageFlow:
 
     def workspace_bytes(self, n):
         """Bytes of a call's workspace at a batch of n images in the handle's current mode (gbnf_image_flow_workspace_bytes)."""
-        nb = C.c_int64()
-        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, int(n), C.byref(nb)))
-        return nb.value
+        return _query_i64(lib().gbnf_image_flow_workspace_bytes, self.handle, int(n))
 
     def set_ycond(self, yc):
         """gbnf_image_flow_set_ycond: make the handle class-conditional.  ``yc``: the spec's ``"ycond"`` entry -- ``cond_w`` (2Cz, Y),
@@ -639,8 +711,7 @@ class NativeImageFlow:
                 raise GbnfError(f"e must be {(n,) + self.z_shape}, got {tuple(e.shape)}")
             e = e.contiguous()
             z = torch.empty_like(e)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_image_flow_prior_y(self.handle, ptr(y), n, ptr(e), float(temperature), ptr(ml), ptr(z), _stream_ptr()))
+        _check(lib().gbnf_image_flow_prior_y(self.handle, _ptr(y), n, _ptr(e), float(temperature), _ptr(ml), _ptr(z), _stream_ptr()))
         if ml is None:
             return None, None, z
         return ml[:, :cz], ml[:, cz:], z
@@ -679,16 +750,12 @@ class NativeImageFlow:
         if noise is not None:
             _require_device_f32(noise, "noise")
         n = x.shape[0]
-        nb = C.c_int64()
-        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
-        if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
-            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        self._ws = _grown(self._ws, self.workspace_bytes(n), x.device)
         mean = torch.empty(512, dtype=torch.float32, device=x.device)
         var = torch.empty(512, dtype=torch.float32, device=x.device)
         ch = C.c_int32()
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_image_flow_actnorm_stats(self.handle, ptr(x), ptr(noise), n, int(index), ptr(mean), ptr(var), C.byref(ch),
-                                                   ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+        _check(lib().gbnf_image_flow_actnorm_stats(self.handle, _ptr(x), _ptr(noise), n, int(index), _ptr(mean), _ptr(var), C.byref(ch),
+                                                   _ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         return mean[: ch.value], var[: ch.value]
 
     def prior(self):
@@ -708,22 +775,15 @@ class NativeImageFlow:
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         n = x.shape[0]
         z = torch.empty((n,) + self.z_shape, dtype=torch.float32, device=x.device) if want_z else None
         ldj = torch.empty(n, dtype=torch.float32, device=x.device)
         ll = torch.empty(n, dtype=torch.float32, device=x.device)
         if n:
-            nb = C.c_int64()
-            _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
-            if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
-                self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-            _check(lib().gbnf_image_flow_forward(self.handle, ptr(x), ptr(noise), n, ptr(z), ptr(ldj), ptr(ll),
-                                                 ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+            self._ws = _grown(self._ws, self.workspace_bytes(n), x.device)
+            _check(lib().gbnf_image_flow_forward(self.handle, _ptr(x), _ptr(noise), n, _ptr(z), _ptr(ldj), _ptr(ll),
+                                                 _ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         return z, ldj, ll
 
     def _forward_y(self, x, noise, want_z, y, want_logits):
@@ -731,10 +791,7 @@ class NativeImageFlow:
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         n = x.shape[0]
         if y is not None and self.y_classes > 0:
             y = self._check_y(y, n)
@@ -744,14 +801,10 @@ class NativeImageFlow:
         ldj = torch.empty(n, dtype=torch.float32, device=x.device)
         ll = torch.empty(n, dtype=torch.float32, device=x.device)
         logits = torch.empty((n, self.y_classes), dtype=torch.float32, device=x.device) if want_logits else None
-        nb = C.c_int64()
-        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
-        if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
-            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        self._ws = _grown(self._ws, self.workspace_bytes(n), x.device)
         # (a null y, a handle without conditioning: the library refuses, nothing launched)
-        _check(lib().gbnf_image_flow_forward_y(self.handle, ptr(x), ptr(noise), ptr(y), n, ptr(z), ptr(ldj), ptr(ll), ptr(logits),
-                                               ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+        _check(lib().gbnf_image_flow_forward_y(self.handle, _ptr(x), _ptr(noise), _ptr(y), n, _ptr(z), _ptr(ldj), _ptr(ll), _ptr(logits),
+                                               _ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         return z, ldj, ll, logits
 
     def forward_classes(self, x, noise=None, want_z=False, want_logits=False):
@@ -762,23 +815,16 @@ class NativeImageFlow:
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         n = x.shape[0]
         z = torch.empty((n,) + self.z_shape, dtype=torch.float32, device=x.device) if want_z else None
         ldj = torch.empty(n, dtype=torch.float32, device=x.device)
         table = torch.empty((n, self.y_classes), dtype=torch.float32, device=x.device)
         logits = torch.empty((n, self.y_classes), dtype=torch.float32, device=x.device) if want_logits else None
-        nb = C.c_int64()
-        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
-        if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
-            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
+        self._ws = _grown(self._ws, self.workspace_bytes(n), x.device)
         # (a handle without conditioning, logits without a class head: the library refuses, nothing launched)
-        _check(lib().gbnf_image_flow_forward_classes(self.handle, ptr(x), ptr(noise), n, ptr(z), ptr(ldj), ptr(table), ptr(logits),
-                                                     ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+        _check(lib().gbnf_image_flow_forward_classes(self.handle, _ptr(x), _ptr(noise), n, _ptr(z), _ptr(ldj), _ptr(table), _ptr(logits),
+                                                     _ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         return z, ldj, table, logits
 
     def split_shapes(self):
@@ -802,25 +848,17 @@ class NativeImageFlow:
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         n = x.shape[0]
-        per = C.c_int64()
-        _check(lib().gbnf_image_flow_eps_floats(self.handle, C.byref(per)))
+        per = _query_i64(lib().gbnf_image_flow_eps_floats, self.handle)
         z = torch.empty((n,) + self.z_shape, dtype=torch.float32, device=x.device)
-        flat = torch.empty(per.value * n, dtype=torch.float32, device=x.device)
+        flat = torch.empty(per * n, dtype=torch.float32, device=x.device)
         ldj = torch.empty(n, dtype=torch.float32, device=x.device)
         ll = torch.empty(n, dtype=torch.float32, device=x.device) if want_ll else None
-        nb = C.c_int64()
-        _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
-        if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
-            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
+        self._ws = _grown(self._ws, self.workspace_bytes(n), x.device)
         # (ll asked of a class-conditional handle: the library refuses, nothing launched)
-        _check(lib().gbnf_image_flow_encode(self.handle, ptr(x.contiguous()), ptr(noise.contiguous() if noise is not None else None), n,
-                                            ptr(z), ptr(flat), ptr(ldj), ptr(ll), ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+        _check(lib().gbnf_image_flow_encode(self.handle, _ptr(x.contiguous()), _ptr(noise.contiguous() if noise is not None else None), n,
+                                            _ptr(z), _ptr(flat), _ptr(ldj), _ptr(ll), _ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         eps, off = [], 0
         for sh in self.split_shapes():
             k = n * sh[0] * sh[1] * sh[2]
@@ -846,20 +884,15 @@ class NativeImageFlow:
             _require_device_f32(e, "eps")
             if tuple(e.shape) != (n,) + sh:
                 raise GbnfError(f"eps tensor must be {(n,) + sh}, got {tuple(e.shape)}")
-        per = C.c_int64()
-        _check(lib().gbnf_image_flow_eps_floats(self.handle, C.byref(per)))
+        per = _query_i64(lib().gbnf_image_flow_eps_floats, self.handle)
         flat = torch.cat([e.reshape(-1) for e in eps]) if eps else None
-        if flat is not None and flat.numel() != per.value * n:
+        if flat is not None and flat.numel() != per * n:
             raise GbnfError("eps size disagrees with gbnf_image_flow_eps_floats")
         x = torch.empty((n,) + self.input_size, dtype=torch.float32, device=z.device)
         if n:
-            nb = C.c_int64()
-            _check(lib().gbnf_image_flow_workspace_bytes(self.handle, n, C.byref(nb)))
-            if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != z.device:
-                self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=z.device)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-            _check(lib().gbnf_image_flow_inverse(self.handle, ptr(z.contiguous()), ptr(flat), float(temperature), n, ptr(x),
-                                                 ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+            self._ws = _grown(self._ws, self.workspace_bytes(n), z.device)
+            _check(lib().gbnf_image_flow_inverse(self.handle, _ptr(z.contiguous()), _ptr(flat), float(temperature), n, _ptr(x),
+                                                 _ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         return x
 
     _rho_ws = {}       # device -> workspace of rho_step (grown to the largest call so far)
@@ -883,10 +916,7 @@ class NativeImageFlow:
         _require_device_f32(rho, "rho")
         if x.dim() != 4 or x.shape[0] < 1 or any(tuple(x.shape[1:]) != f.input_size for f in flows):
             raise GbnfError(f"x must be (n,{flows[0].input_size}) with n >= 1 for every handle, got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         if rho.dim() != 1 or rho.numel() <= component:
             raise GbnfError("rho has no entry for this component")
         n = x.shape[0]
@@ -894,21 +924,17 @@ class NativeImageFlow:
             _require_device_f32(y, "y")
             if y.dim() != 2 or y.shape[0] != n or y.shape[1] != max(int(f.y_classes) for f in flows):
                 raise GbnfError(f"y must be ({n}, y_classes), got {tuple(y.shape)}")
-        handles = (C.c_void_p * len(flows))(*[f.handle.value for f in flows])
-        nb = C.c_int64()
-        _check(lib().gbnf_image_rho_step_workspace_bytes(handles, len(flows), n, C.byref(nb)))
-        ws = NativeImageFlow._rho_ws.get(x.device)
-        if ws is None or ws.numel() * 4 < nb.value:
-            ws = NativeImageFlow._rho_ws[x.device] = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        handles = _handle_array(flows)
+        nb = _query_i64(lib().gbnf_image_rho_step_workspace_bytes, handles, len(flows), n)
+        ws = NativeImageFlow._rho_ws[x.device] = _grown(NativeImageFlow._rho_ws.get(x.device), nb, x.device)
         table = flows[component].rho_ll = torch.empty((component + 1, n), dtype=torch.float32, device=x.device)
         stats = torch.zeros(4, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
         if y is not None:
-            _check(lib().gbnf_image_mixture_rho_step_y(handles, component, ptr(x), ptr(noise), ptr(y), n, ptr(rho), float(step_size),
-                                                       ptr(table), ptr(stats), ptr(ws), ws.numel() * 4, _stream_ptr()))
+            _check(lib().gbnf_image_mixture_rho_step_y(handles, component, _ptr(x), _ptr(noise), _ptr(y), n, _ptr(rho), float(step_size),
+                                                       _ptr(table), _ptr(stats), _ptr(ws), ws.numel() * 4, _stream_ptr()))
             return stats
-        _check(lib().gbnf_image_mixture_rho_step(handles, component, ptr(x), ptr(noise), n, ptr(rho), float(step_size), ptr(table),
-                                                 ptr(stats), ptr(ws), ws.numel() * 4, _stream_ptr()))
+        _check(lib().gbnf_image_mixture_rho_step(handles, component, _ptr(x), _ptr(noise), n, _ptr(rho), float(step_size), _ptr(table),
+                                                 _ptr(stats), _ptr(ws), ws.numel() * 4, _stream_ptr()))
         return stats
 
     _eval_ws = {}      # device -> workspace of evaluate (grown to the largest call so far)
@@ -932,10 +958,7 @@ class NativeImageFlow:
         _require_eval_state(state)
         if x.dim() != 4 or x.shape[0] < 1 or any(tuple(x.shape[1:]) != f.input_size for f in flows):
             raise GbnfError(f"x must be (n,{flows[0].input_size}) with n >= 1 for every handle, got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         if rho.dim() != 1 or rho.numel() < len(flows):
             raise GbnfError("rho is shorter than the handle list")
         n = x.shape[0]
@@ -943,37 +966,69 @@ class NativeImageFlow:
             _require_device_f32(y, "y")
             if y.dim() != 2 or y.shape[0] != n or y.shape[1] != max(int(f.y_classes) for f in flows):
                 raise GbnfError(f"y must be ({n}, y_classes), got {tuple(y.shape)}")
-        handles = (C.c_void_p * len(flows))(*[f.handle.value for f in flows])
-        nb = C.c_int64()
-        _check(lib().gbnf_image_mixture_evaluate_workspace_bytes(handles, len(flows), n, C.byref(nb)))
-        ws = NativeImageFlow._eval_ws.get(x.device)
-        if ws is None or ws.numel() * 4 < nb.value:
-            ws = NativeImageFlow._eval_ws[x.device] = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        handles = _handle_array(flows)
+        nb = _query_i64(lib().gbnf_image_mixture_evaluate_workspace_bytes, handles, len(flows), n)
+        ws = NativeImageFlow._eval_ws[x.device] = _grown(NativeImageFlow._eval_ws.get(x.device), nb, x.device)
         table = NativeImageFlow._eval_ll.get(x.device)
         if table is None or tuple(table.shape) != (len(flows), n):
             table = NativeImageFlow._eval_ll[x.device] = torch.empty((len(flows), n), dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
         if y is not None:
-            _check(lib().gbnf_image_mixture_evaluate_y(handles, len(flows), component, ptr(x), ptr(noise), ptr(y), n, ptr(rho), ptr(table),
-                                                       None, ptr(state), ptr(ws), ws.numel() * 4, _stream_ptr()))
+            _check(lib().gbnf_image_mixture_evaluate_y(handles, len(flows), component, _ptr(x), _ptr(noise), _ptr(y), n, _ptr(rho), _ptr(table),
+                                                       None, _ptr(state), _ptr(ws), ws.numel() * 4, _stream_ptr()))
             return table
-        _check(lib().gbnf_image_mixture_evaluate(handles, len(flows), component, ptr(x), ptr(noise), n, ptr(rho), ptr(table), None,
-                                                 ptr(state), ptr(ws), ws.numel() * 4, _stream_ptr()))
+        _check(lib().gbnf_image_mixture_evaluate(handles, len(flows), component, _ptr(x), _ptr(noise), n, _ptr(rho), _ptr(table), None,
+                                                 _ptr(state), _ptr(ws), ws.numel() * 4, _stream_ptr()))
         return table
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().gbnf_image_flow_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
+class _TrainerBase(_Handle):
+    """What ``NativeTrainer`` and ``NativeImageTrainer`` share: the identity key, the deterministic switch, gbnf_opt_hyper and the
+    update call.  A subclass names its library symbols and the attribute that holds the floats of the buffer ``apply_update`` walks."""
+
+    _get_deterministic = _set_deterministic = _apply_update = None
+    _update_floats = "grad_floats"
+
+    def key(self):
+        return tuple(t.data_ptr() for t in self._tensors)
+
+    @property
+    def deterministic(self):
+        """Deterministic mode of the trainer (the class's gbnf_*_get_deterministic / gbnf_*_set_deterministic)."""
+        on = C.c_int32(0)
+        _check(getattr(lib(), self._get_deterministic)(self.handle, C.byref(on)))
+        return bool(on.value)
+
+    @deterministic.setter
+    def deterministic(self, on):
+        _check(getattr(lib(), self._set_deterministic)(self.handle, 1 if on else 0))
+        self._deterministic = bool(on)
+
+    def _hyper(self, state, lr, weight_decay=0.0, max_grad_norm=0.0, betas=(0.9, 0.999), eps=1e-8, bn_momentum=-1.0):
+        """The gbnf_opt_hyper of the NEXT update of ``state`` (its ``step`` + 1)."""
+        return _OptHyper(kind=OPT_KIND[state.kind], step=state.step + 1, lr=lr, beta1=betas[0], beta2=betas[1], eps=eps,
+                         weight_decay=weight_decay, max_grad_norm=max_grad_norm, bn_momentum=bn_momentum)
+
+    def apply_update(self, flat_grads, state, **hyper):
+        """clip_grad_norm_ + one optimiser step on the bound tensors, in place, from a flat gradient buffer (gbnf_trainer_apply_update:
+        the layout of ``backward``; gbnf_image_trainer_apply_update: the STEP layout).  ``state``: an ``OptState`` of this trainer,
+        advanced by one step.  ``hyper``: lr, weight_decay, max_grad_norm, betas, eps.  -> stats (4,) device tensor: [1] gradient norm,
+        [2] clip coefficient.  The parameters change behind autograd's back: no version counter moves (the modules' ``training_step``
+        takes care of that)."""
+        import torch
+        _require_device_f32(flat_grads, "flat_grads")
+        floats = getattr(self, self._update_floats)
+        if flat_grads.numel() != floats:
+            raise GbnfError(f"flat_grads has {flat_grads.numel()} elements, expected {floats}")
+        state.check(self)
+        h = self._hyper(state, **hyper)
+        stats = torch.zeros(4, dtype=torch.float32, device=flat_grads.device)
+        _check(getattr(lib(), self._apply_update)(self.handle, _ptr(flat_grads), _ptr(state.exp_avg), _ptr(state.exp_avg_sq), C.byref(h),
+                                                  _ptr(stats), _stream_ptr()))
+        state.step += 1
+        return stats
 
 
-class NativeImageTrainer:
+class NativeImageTrainer(_TrainerBase):
     """Training path of one image Glow component (gbnf_image_trainer): forward on the LIVE device parameters and the backward pass,
     exact f32.
 
@@ -988,6 +1043,9 @@ class NativeImageTrainer:
     ``boosted_nll_step`` are bit-reproducible for fixed inputs, parameters and batch size.  The workspaces grow; their sizes are
     asked of the library on every call."""
 
+    _destroy = "gbnf_image_trainer_destroy"
+    _get_deterministic, _set_deterministic = "gbnf_image_trainer_get_deterministic", "gbnf_image_trainer_set_deterministic"
+    _apply_update, _update_floats = "gbnf_image_trainer_apply_update", "step_grad_floats"
     CONV_KEYS = ("w", "b", "an_bias", "an_logs", "logs")          # order of a convolution's arrays in the flat gradient buffer
 
     def __init__(self, dev_spec, deterministic=False):
@@ -1072,9 +1130,7 @@ class NativeImageTrainer:
         _check(lib().gbnf_image_trainer_create(C.byref(desc), C.byref(h)))
         del keep
         self.handle = h
-        nf = C.c_int64()
-        _check(lib().gbnf_image_trainer_grad_floats(h, C.byref(nf)))
-        self.grad_floats = int(nf.value)
+        self.grad_floats = _query_i64(lib().gbnf_image_trainer_grad_floats, h)
         if self.grad_floats != self._off:
             raise GbnfError("gradient-buffer layout mismatch between the library and the binding")
         self.device = self._tensors[0].device
@@ -1086,32 +1142,13 @@ class NativeImageTrainer:
         if deterministic:
             self.deterministic = True
 
-    def key(self):
-        return tuple(t.data_ptr() for t in self._tensors)
-
-    @property
-    def deterministic(self):
-        """Deterministic mode of the trainer (gbnf_image_trainer_get_deterministic / gbnf_image_trainer_set_deterministic)."""
-        on = C.c_int32()
-        _check(lib().gbnf_image_trainer_get_deterministic(self.handle, C.byref(on)))
-        return bool(on.value)
-
-    @deterministic.setter
-    def deterministic(self, on):
-        _check(lib().gbnf_image_trainer_set_deterministic(self.handle, 1 if on else 0))
-        self._deterministic = bool(on)
-
     def workspace_bytes(self, n):
         """Bytes of the forward / backward workspace at a batch of n images (gbnf_image_trainer_workspace_bytes)."""
-        nb = C.c_int64()
-        _check(lib().gbnf_image_trainer_workspace_bytes(self.handle, int(n), C.byref(nb)))
-        return int(nb.value)
+        return _query_i64(lib().gbnf_image_trainer_workspace_bytes, self.handle, int(n))
 
     def step_workspace_bytes(self, n):
         """Bytes of the workspace of ``nll_step`` at a batch of n images (gbnf_image_trainer_step_workspace_bytes)."""
-        nb = C.c_int64()
-        _check(lib().gbnf_image_trainer_step_workspace_bytes(self.handle, int(n), C.byref(nb)))
-        return int(nb.value)
+        return _query_i64(lib().gbnf_image_trainer_step_workspace_bytes, self.handle, int(n))
 
     # ---- data-dependent ActNorm2d initialisation in one pass (gbnf_image_trainer_actnorm_init)
     def actnorm_count(self):
@@ -1121,9 +1158,7 @@ class NativeImageTrainer:
         return int(k.value)
 
     def actnorm_init_workspace_bytes(self, n):
-        nb = C.c_int64()
-        _check(lib().gbnf_image_trainer_actnorm_init_workspace_bytes(self.handle, int(n), C.byref(nb)))
-        return int(nb.value)
+        return _query_i64(lib().gbnf_image_trainer_actnorm_init_workspace_bytes, self.handle, int(n))
 
     def actnorm_init(self, x, noise, scale=1.0, skip=None, workspace=None):
         """The reference's first training-mode forward for every ActNorm2d at once: bias = -mean, logs = log(scale / (sqrt(var) + 1e-6))
@@ -1135,24 +1170,16 @@ class NativeImageTrainer:
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         n = x.shape[0]
         flags = None
         if skip is not None:
             flags = np.ascontiguousarray([1 if s else 0 for s in skip], dtype=np.uint8)
             if flags.size != self.actnorm_count():
                 raise GbnfError(f"skip has {flags.size} entries, the component has {self.actnorm_count()} ActNorm2d layers")
-        nb = self.actnorm_init_workspace_bytes(max(n, 1))
-        if workspace is None:
-            workspace = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
-        elif not workspace.is_cuda or not workspace.is_contiguous():
-            raise GbnfError("workspace must be a contiguous device tensor")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_image_trainer_actnorm_init(self.handle, ptr(x), ptr(noise), n, float(scale),
-                                                     C.c_void_p(flags.ctypes.data) if flags is not None else C.c_void_p(0), ptr(workspace),
+        workspace = _workspace_arg(workspace, lambda: self.actnorm_init_workspace_bytes(max(n, 1)), x.device)
+        _check(lib().gbnf_image_trainer_actnorm_init(self.handle, _ptr(x), _ptr(noise), n, float(scale),
+                                                     C.c_void_p(flags.ctypes.data) if flags is not None else C.c_void_p(0), _ptr(workspace),
                                                      workspace.numel() * workspace.element_size(), _stream_ptr()))
 
     # ---- the one-call training step (gbnf_image_trainer_nll_step / _apply_update)
@@ -1182,11 +1209,9 @@ class NativeImageTrainer:
                 regions.append((("ycond", name), off, tuple(t.shape)))
                 tensors.append(t)
                 off += t.numel()
-        nf = C.c_int64()
-        _check(lib().gbnf_image_trainer_step_grad_floats(self.handle, C.byref(nf)))
-        if nf.value != off:
+        self.step_grad_floats = _query_i64(lib().gbnf_image_trainer_step_grad_floats, self.handle)
+        if self.step_grad_floats != off:
             raise GbnfError("step gradient-buffer layout mismatch between the library and the binding")
-        self.step_grad_floats = int(nf.value)
         self._step_regions = regions
         self.params = tensors
         self._sizes = [int(np.prod(shape)) for _, _, shape in regions]
@@ -1199,8 +1224,7 @@ class NativeImageTrainer:
             _require_device_f32(t, name)
             if c is not None and tuple(t.shape) != shape:
                 raise GbnfError(f"bind_lu: {name} has shape {tuple(t.shape)}, expected {shape}")
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _check(lib().gbnf_image_trainer_bind_lu(self.handle, int(level), int(step), ptr(p), ptr(sign_s), ptr(lower), ptr(upper), ptr(log_s)))
+        _check(lib().gbnf_image_trainer_bind_lu(self.handle, int(level), int(step), _ptr(p), _ptr(sign_s), _ptr(lower), _ptr(upper), _ptr(log_s)))
         self._tensors += [p, sign_s, lower, upper, log_s]
         self._lu[(int(level), int(step))] = (lower, upper, log_s)
         self._layout_step()
@@ -1217,8 +1241,7 @@ class NativeImageTrainer:
             _require_device_f32(t, name)
             if t.numel() != numel:
                 raise GbnfError(f"bind_top: {name} has {t.numel()} elements, expected {numel}")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_image_trainer_bind_top(self.handle, ptr(weight), ptr(bias), ptr(logs)))
+        _check(lib().gbnf_image_trainer_bind_top(self.handle, _ptr(weight), _ptr(bias), _ptr(logs)))
         self._tensors += [t for t in (weight, bias, logs) if t is not None]
         self._top = (weight, bias, logs)
         self._layout_step()
@@ -1239,8 +1262,7 @@ class NativeImageTrainer:
             _require_device_f32(t, name)
             if t.numel() != numel:
                 raise GbnfError(f"bind_ycond: {name} has {t.numel()} elements, expected {numel}")
-        ptr = lambda t: C.c_void_p(t.data_ptr())
-        _check(lib().gbnf_image_trainer_bind_ycond(self.handle, y, *[ptr(t) for t in ts]))
+        _check(lib().gbnf_image_trainer_bind_ycond(self.handle, y, *[_ptr(t) for t in ts]))
         self._tensors += list(ts)
         self._ycond = ts
         self.y_classes = y
@@ -1261,25 +1283,6 @@ class NativeImageTrainer:
             raise GbnfError(f"flat has {flat.numel()} elements, expected {self.step_grad_floats}")
         return {path: flat[off: off + int(np.prod(shape))].view(shape) for path, off, shape in self._step_regions}
 
-    _hyper = None      # (set below the class: NativeTrainer._hyper, the same gbnf_opt_hyper)
-
-    def apply_update(self, flat_grads, state, **hyper):
-        """clip_grad_norm_ + one optimiser step on the bound tensors, in place, from a flat gradient buffer in the STEP layout
-        (gbnf_image_trainer_apply_update).  ``state``: an ``OptState`` of this trainer, advanced by one step.  ``hyper``: lr,
-        weight_decay, max_grad_norm, betas, eps.  -> stats (4,) device tensor: [1] gradient norm, [2] clip coefficient."""
-        import torch
-        _require_device_f32(flat_grads, "flat_grads")
-        if flat_grads.numel() != self.step_grad_floats:
-            raise GbnfError(f"flat_grads has {flat_grads.numel()} elements, expected {self.step_grad_floats}")
-        state.check(self)
-        h = self._hyper(state, **hyper)
-        stats = torch.zeros(4, dtype=torch.float32, device=flat_grads.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_image_trainer_apply_update(self.handle, ptr(flat_grads), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h),
-                                                     ptr(stats), _stream_ptr()))
-        state.step += 1
-        return stats
-
     def nll_step(self, x, noise, state, loss_scale=1.0, y=None, y_weight=0.01, **hyper):
         """One whole training step of this component on the device (gbnf_image_trainer_nll_step): 1x1 log-dets (LU matrices composed) ->
         forward on the live parameters -> loss_scale * mean nll and its seed -> backward -> log-det / LU / top-prior gradients -> clip ->
@@ -1292,31 +1295,24 @@ class NativeImageTrainer:
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         n = x.shape[0]
         if y is not None:
             y = self._check_y(y, n)
         state.check(self)
         h = self._hyper(state, **hyper)
-        nb = C.c_int64()
-        _check(lib().gbnf_image_trainer_step_workspace_bytes(self.handle, n, C.byref(nb)))
-        if self._step_ws is None or self._step_ws.numel() * 4 < nb.value or self._step_ws.device != x.device:
-            self._step_ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+        self._step_ws = _grown(self._step_ws, self.step_workspace_bytes(n), x.device)
         flat = torch.empty(self.step_grad_floats, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
         if y is not None:
             stats = torch.zeros(8, dtype=torch.float32, device=x.device)
-            _check(lib().gbnf_image_trainer_nll_step_y(self.handle, ptr(x), ptr(noise), ptr(y), n, float(loss_scale), float(y_weight),
-                                                       ptr(flat), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h), ptr(stats),
-                                                       ptr(self._step_ws), self._step_ws.numel() * 4, _stream_ptr()))
+            _check(lib().gbnf_image_trainer_nll_step_y(self.handle, _ptr(x), _ptr(noise), _ptr(y), n, float(loss_scale), float(y_weight),
+                                                       _ptr(flat), _ptr(state.exp_avg), _ptr(state.exp_avg_sq), C.byref(h), _ptr(stats),
+                                                       _ptr(self._step_ws), self._step_ws.numel() * 4, _stream_ptr()))
             state.step += 1
             return stats, flat
         stats = torch.zeros(4, dtype=torch.float32, device=x.device)
-        _check(lib().gbnf_image_trainer_nll_step(self.handle, ptr(x), ptr(noise), n, float(loss_scale), ptr(flat), ptr(state.exp_avg),
-                                                 ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(self._step_ws),
+        _check(lib().gbnf_image_trainer_nll_step(self.handle, _ptr(x), _ptr(noise), n, float(loss_scale), _ptr(flat), _ptr(state.exp_avg),
+                                                 _ptr(state.exp_avg_sq), C.byref(h), _ptr(stats), _ptr(self._step_ws),
                                                  self._step_ws.numel() * 4, _stream_ptr()))
         state.step += 1
         return stats, flat
@@ -1334,44 +1330,32 @@ class NativeImageTrainer:
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size or tuple(fixed.input_size) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}) and fixed take the same images, got {tuple(x.shape)} and {fixed.input_size}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         n = x.shape[0]
         state.check(self)
         h = self._hyper(state, **hyper)
         if y is not None:
             y = self._check_y(y, n)
-        nb = C.c_int64()
         query = lib().gbnf_image_boosted_step_workspace_bytes_y if y is not None else lib().gbnf_image_boosted_step_workspace_bytes
-        _check(query(fixed.handle, self.handle, n, C.byref(nb)))
-        if self._boost_ws is None or self._boost_ws.numel() * 4 < nb.value or self._boost_ws.device != x.device:
-            self._boost_ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
-        ws = self._boost_ws
+        ws = self._boost_ws = _grown(self._boost_ws, _query_i64(query, fixed.handle, self.handle, n), x.device)
         flat = torch.empty(self.step_grad_floats, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
         if y is not None:
             stats = torch.zeros(12, dtype=torch.float32, device=x.device)
-            _check(lib().gbnf_image_boosted_nll_step_y(fixed.handle, float(g_floor), self.handle, ptr(x), ptr(noise), ptr(y), n,
-                                                       float(loss_scale), float(y_weight), ptr(flat), ptr(state.exp_avg),
-                                                       ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(ws), ws.numel() * 4,
+            _check(lib().gbnf_image_boosted_nll_step_y(fixed.handle, float(g_floor), self.handle, _ptr(x), _ptr(noise), _ptr(y), n,
+                                                       float(loss_scale), float(y_weight), _ptr(flat), _ptr(state.exp_avg),
+                                                       _ptr(state.exp_avg_sq), C.byref(h), _ptr(stats), _ptr(ws), ws.numel() * 4,
                                                        _stream_ptr()))
             state.step += 1
             return stats, flat
         stats = torch.zeros(8, dtype=torch.float32, device=x.device)
-        _check(lib().gbnf_image_boosted_nll_step(fixed.handle, float(g_floor), self.handle, ptr(x), ptr(noise), n, float(loss_scale),
-                                                 ptr(flat), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(ws),
+        _check(lib().gbnf_image_boosted_nll_step(fixed.handle, float(g_floor), self.handle, _ptr(x), _ptr(noise), n, float(loss_scale),
+                                                 _ptr(flat), _ptr(state.exp_avg), _ptr(state.exp_avg_sq), C.byref(h), _ptr(stats), _ptr(ws),
                                                  ws.numel() * 4, _stream_ptr()))
         state.step += 1
         return stats, flat
 
     def _workspace(self, n):
-        import torch
-        nb = C.c_int64()
-        _check(lib().gbnf_image_trainer_workspace_bytes(self.handle, n, C.byref(nb)))
-        if self._ws is None or self._ws.numel() * 4 < nb.value:
-            self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=self.device)
+        self._ws = _grown(self._ws, self.workspace_bytes(n), self.device)
         return self._ws
 
     def forward(self, x, noise=None, want_trace=True):
@@ -1380,20 +1364,15 @@ class NativeImageTrainer:
         _require_device_f32(x, "x")
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        _check_noise(noise, x)
         n = x.shape[0]
         z = torch.empty((n,) + self.z_shape, dtype=torch.float32, device=x.device)
         ldj = torch.empty(n, dtype=torch.float32, device=x.device)
-        nt = C.c_int64()
-        _check(lib().gbnf_image_trainer_trace_floats(self.handle, n, C.byref(nt)))
-        trace = torch.empty(nt.value, dtype=torch.float32, device=x.device)      # (the state storage of the pass: always needed)
+        nt = _query_i64(lib().gbnf_image_trainer_trace_floats, self.handle, n)
+        trace = torch.empty(nt, dtype=torch.float32, device=x.device)      # (the state storage of the pass: always needed)
         if n:
             ws = self._workspace(n)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-            _check(lib().gbnf_image_trainer_forward(self.handle, ptr(x), ptr(noise), n, ptr(z), ptr(ldj), ptr(trace), ptr(ws),
+            _check(lib().gbnf_image_trainer_forward(self.handle, _ptr(x), _ptr(noise), n, _ptr(z), _ptr(ldj), _ptr(trace), _ptr(ws),
                                                     ws.numel() * 4, _stream_ptr()))
         return z, ldj, (trace if want_trace else None)
 
@@ -1403,11 +1382,10 @@ class NativeImageTrainer:
         ACCUMULATE into (None: a zeroed one)."""
         import torch
         _require_device_f32(trace, "trace")
-        nt = C.c_int64()
-        _check(lib().gbnf_image_trainer_trace_floats(self.handle, 1, C.byref(nt)))
-        if nt.value == 0 or trace.numel() % nt.value:
+        nt = _query_i64(lib().gbnf_image_trainer_trace_floats, self.handle, 1)
+        if nt == 0 or trace.numel() % nt:
             raise GbnfError("trace is not one of this trainer's")
-        n = trace.numel() // nt.value
+        n = trace.numel() // nt
         if g_z is not None:
             _require_device_f32(g_z, "g_z")
             if tuple(g_z.shape) != (n,) + self.z_shape:
@@ -1424,8 +1402,7 @@ class NativeImageTrainer:
                 raise GbnfError(f"out has {out.numel()} elements, expected {self.grad_floats}")
         if n:
             ws = self._workspace(n)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-            _check(lib().gbnf_image_trainer_backward(self.handle, ptr(trace), n, ptr(g_z), ptr(g_ldj), ptr(out), ptr(ws),
+            _check(lib().gbnf_image_trainer_backward(self.handle, _ptr(trace), n, _ptr(g_z), _ptr(g_ldj), _ptr(out), _ptr(ws),
                                                      ws.numel() * 4, _stream_ptr()))
         return out, {path: out[off: off + int(np.prod(shape))].view(shape) for path, off, shape in self._regions}
 
@@ -1441,14 +1418,10 @@ class NativeImageTrainer:
         if x.dim() != 4 or tuple(x.shape[1:]) != self.input_size:
             raise GbnfError(f"x must be (n,{self.input_size}), got {tuple(x.shape)}")
         n = x.shape[0]
-        nt = C.c_int64()
-        _check(lib().gbnf_image_trainer_trace_floats(self.handle, n, C.byref(nt)))
-        if trace.numel() != nt.value:
-            raise GbnfError(f"trace has {trace.numel()} floats: not this trainer's at n = {n} ({nt.value})")
-        if noise is not None:
-            _require_device_f32(noise, "noise")
-            if noise.shape != x.shape:
-                raise GbnfError("noise must have the shape of x")
+        nt = _query_i64(lib().gbnf_image_trainer_trace_floats, self.handle, n)
+        if trace.numel() != nt:
+            raise GbnfError(f"trace has {trace.numel()} floats: not this trainer's at n = {n} ({nt})")
+        _check_noise(noise, x)
         if g_z is not None:
             _require_device_f32(g_z, "g_z")
             if tuple(g_z.shape) != (n,) + self.z_shape:
@@ -1471,30 +1444,16 @@ class NativeImageTrainer:
         else:
             g_x = torch.empty_like(x)
         if n:
-            ws = self._workspace(n) if workspace is None else workspace
-            if not ws.is_cuda or not ws.is_contiguous():
-                raise GbnfError("workspace must be a contiguous device tensor")
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-            _check(lib().gbnf_image_trainer_backward_x(self.handle, ptr(trace), ptr(x), ptr(noise), n, ptr(g_z), ptr(g_ldj), ptr(out),
-                                                       ptr(g_x), 1 if accumulate else 0, ptr(ws), ws.numel() * ws.element_size(),
+            ws = _check_workspace(self._workspace(n) if workspace is None else workspace)
+            _check(lib().gbnf_image_trainer_backward_x(self.handle, _ptr(trace), _ptr(x), _ptr(noise), n, _ptr(g_z), _ptr(g_ldj), _ptr(out),
+                                                       _ptr(g_x), 1 if accumulate else 0, _ptr(ws), ws.numel() * ws.element_size(),
                                                        _stream_ptr()))
         if out is None:
             return g_x
         return g_x, out, {path: out[off: off + int(np.prod(shape))].view(shape) for path, off, shape in self._regions}
 
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().gbnf_image_trainer_destroy(self.handle)
-            self.handle = None
 
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-class NativeTrainer:
+class NativeTrainer(_TrainerBase):
     """Training path of one component (gbnf_trainer): forward on the LIVE device parameters and the backward pass.
 
     ``dev_spec`` has the shape of a flow spec (spec.py) but every float array is a contiguous float32 CUDA tensor --
@@ -1511,6 +1470,9 @@ class NativeTrainer:
     parameters and batch size.  A call that would run the per-step kernels (unordered float atomics) raises GbnfError with the
     library's reason.  The workspaces grow: every helper asks the library for the size at every call."""
 
+    _destroy = "gbnf_trainer_destroy"
+    _get_deterministic, _set_deterministic = "gbnf_trainer_get_deterministic", "gbnf_trainer_set_deterministic"
+    _apply_update, _update_floats = "gbnf_trainer_apply_update", "grad_floats"
     TRAIN_MATH = {"f16x3": MATH["f16x3"], "bf16x6": MATH["bf16x6"], "repair": MATH["default"]}
 
     def __init__(self, dev_spec, math="f16x3", deterministic=False):
@@ -1601,9 +1563,7 @@ class NativeTrainer:
             n_bn = sum(1 for st in dev_spec["steps"] if st["bn"] is not None)
             self.has_batch_stats = bound == n_bn and n_bn > 0
         self.batch_stats = False
-        nf = C.c_int64()
-        _check(lib().gbnf_trainer_grad_floats(h, C.byref(nf)))
-        self.grad_floats = int(nf.value)
+        self.grad_floats = _query_i64(lib().gbnf_trainer_grad_floats, h)
         if self.grad_floats != sum(self._sizes):
             raise GbnfError("gradient-buffer layout mismatch between the library and the binding")
         self._ws = None
@@ -1613,44 +1573,6 @@ class NativeTrainer:
         self._deterministic = False
         if deterministic:
             self.deterministic = True
-
-    def key(self):
-        return tuple(t.data_ptr() for t in self._tensors)
-
-    @property
-    def deterministic(self):
-        """Deterministic mode of the trainer (gbnf_trainer_get_deterministic / gbnf_trainer_set_deterministic)."""
-        on = C.c_int32(0)
-        _check(lib().gbnf_trainer_get_deterministic(self.handle, C.byref(on)))
-        return bool(on.value)
-
-    @deterministic.setter
-    def deterministic(self, on):
-        _check(lib().gbnf_trainer_set_deterministic(self.handle, 1 if on else 0))
-        self._deterministic = bool(on)
-
-    def _hyper(self, state, lr, weight_decay=0.0, max_grad_norm=0.0, betas=(0.9, 0.999), eps=1e-8, bn_momentum=-1.0):
-        """The gbnf_opt_hyper of the NEXT update of ``state`` (its ``step`` + 1)."""
-        return _OptHyper(kind=OPT_KIND[state.kind], step=state.step + 1, lr=lr, beta1=betas[0], beta2=betas[1], eps=eps,
-                         weight_decay=weight_decay, max_grad_norm=max_grad_norm, bn_momentum=bn_momentum)
-
-    def apply_update(self, flat_grads, state, **hyper):
-        """clip_grad_norm_ + one optimiser step on the bound parameter tensors, in place, from a flat gradient buffer in the layout of
-        ``backward`` (gbnf_trainer_apply_update).  ``state``: an ``OptState`` of this trainer, advanced by one step.  ``hyper``: lr,
-        weight_decay, max_grad_norm, betas, eps.  -> stats (4,) device tensor: [1] gradient norm, [2] clip coefficient.  The parameters
-        change behind autograd's back: no version counter moves (BoostedFlow.training_step takes care of that)."""
-        import torch
-        _require_device_f32(flat_grads, "flat_grads")
-        if flat_grads.numel() != self.grad_floats:
-            raise GbnfError(f"flat_grads has {flat_grads.numel()} elements, expected {self.grad_floats}")
-        state.check(self)
-        h = self._hyper(state, **hyper)
-        stats = torch.zeros(4, dtype=torch.float32, device=flat_grads.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_trainer_apply_update(self.handle, ptr(flat_grads), ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h),
-                                               ptr(stats), _stream_ptr()))
-        state.step += 1
-        return stats
 
     def nll_step(self, x, state, rows=None, **hyper):
         """One whole training step of this component on the device (gbnf_trainer_nll_step): [x[rows]] -> forward on the live parameters ->
@@ -1668,15 +1590,14 @@ class NativeTrainer:
             n = rows.shape[0]
         state.check(self)
         h = self._hyper(state, **hyper)
-        nb = C.c_int64()
+        nb = C.c_int64()         # (the size query and the cached-buffer test in line: this is the per-step path, see _grown)
         _check(lib().gbnf_trainer_step_workspace_bytes(self.handle, n, C.byref(nb)))
         if self._step_ws is None or self._step_ws.numel() * 4 < nb.value or self._step_ws.device != x.device:
-            self._step_ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
+            self._step_ws = _grown(None, nb.value, x.device)
         flat = torch.empty(self.grad_floats, dtype=torch.float32, device=x.device)
         stats = torch.zeros(4, dtype=torch.float32, device=x.device)
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_trainer_nll_step(self.handle, ptr(x), n_x, ptr(rows), n, ptr(flat), ptr(state.exp_avg), ptr(state.exp_avg_sq),
-                                           C.byref(h), ptr(stats), ptr(self._step_ws), self._step_ws.numel() * 4, _stream_ptr()))
+        _check(lib().gbnf_trainer_nll_step(self.handle, _ptr(x), n_x, _ptr(rows), n, _ptr(flat), _ptr(state.exp_avg), _ptr(state.exp_avg_sq),
+                                           C.byref(h), _ptr(stats), _ptr(self._step_ws), self._step_ws.numel() * 4, _stream_ptr()))
         state.step += 1
         return stats, flat
 
@@ -1700,17 +1621,16 @@ class NativeTrainer:
             raise GbnfError("rho shorter than n_fixed")
         state.check(self)
         h = self._hyper(state, **hyper)
-        nb = C.c_int64()
+        nb = C.c_int64()         # (in line as in nll_step)
         _check(lib().gbnf_boosted_step_workspace_bytes(mixture.handle, n_fixed, self.handle, n, C.byref(nb)))
         if self._boost_ws is None or self._boost_ws.numel() * 8 < nb.value or self._boost_ws.device != x.device:
-            self._boost_ws = torch.empty((nb.value + 7) // 8, dtype=torch.float64, device=x.device)
+            self._boost_ws = _grown(None, nb.value, x.device, torch.float64)
         flat = torch.empty(self.grad_floats, dtype=torch.float32, device=x.device)
         stats = torch.zeros(8, dtype=torch.float32, device=x.device)
         rows = torch.empty(n, dtype=torch.int64, device=x.device) if want_rows else None
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_boosted_nll_step(mixture.handle, n_fixed, ptr(rho), float(beta), self.handle, ptr(x), n, ptr(u), ptr(flat),
-                                           ptr(state.exp_avg), ptr(state.exp_avg_sq), C.byref(h), ptr(stats), ptr(rows),
-                                           ptr(self._boost_ws), self._boost_ws.numel() * 8, _stream_ptr()))
+        _check(lib().gbnf_boosted_nll_step(mixture.handle, n_fixed, _ptr(rho), float(beta), self.handle, _ptr(x), n, _ptr(u), _ptr(flat),
+                                           _ptr(state.exp_avg), _ptr(state.exp_avg_sq), C.byref(h), _ptr(stats), _ptr(rows),
+                                           _ptr(self._boost_ws), self._boost_ws.numel() * 8, _stream_ptr()))
         state.step += 1
         return stats, flat, rows
 
@@ -1733,13 +1653,9 @@ class NativeTrainer:
         ldj = torch.empty(n, dtype=torch.float32, device=x.device)
         trace = None
         if want_trace:
-            nf = C.c_int64()
-            _check(lib().gbnf_trainer_trace_floats(self.handle, n, C.byref(nf)))
-            trace = torch.empty(nf.value, dtype=torch.float32, device=x.device)
+            trace = torch.empty(_query_i64(lib().gbnf_trainer_trace_floats, self.handle, n), dtype=torch.float32, device=x.device)
         if n:
-            _check(lib().gbnf_trainer_forward(self.handle, C.c_void_p(x.data_ptr()), n, C.c_void_p(z.data_ptr()),
-                                              C.c_void_p(ldj.data_ptr()),
-                                              C.c_void_p(trace.data_ptr() if trace is not None else 0), _stream_ptr()))
+            _check(lib().gbnf_trainer_forward(self.handle, _ptr(x), n, _ptr(z), _ptr(ldj), _ptr(trace), _stream_ptr()))
         return (z, ldj, trace) if want_trace else (z, ldj)
 
     def backward(self, x, g_z=None, g_ldj=None, want_gx=False, trace=None):
@@ -1753,13 +1669,12 @@ class NativeTrainer:
         flat = torch.zeros(self.grad_floats, dtype=torch.float32, device=x.device)
         g_x = torch.empty_like(x) if want_gx else None
         if n:
-            nb = C.c_int64()
+            nb = C.c_int64()         # (in line as in nll_step)
             _check(lib().gbnf_trainer_workspace_bytes(self.handle, n, C.byref(nb)))
             if self._ws is None or self._ws.numel() * 4 < nb.value or self._ws.device != x.device:
-                self._ws = torch.empty((nb.value + 3) // 4, dtype=torch.float32, device=x.device)
-            ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-            _check(lib().gbnf_trainer_backward(self.handle, ptr(x), n, ptr(trace), ptr(g_z), ptr(g_ldj), ptr(g_x), ptr(flat),
-                                               ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
+                self._ws = _grown(None, nb.value, x.device)
+            _check(lib().gbnf_trainer_backward(self.handle, _ptr(x), n, _ptr(trace), _ptr(g_z), _ptr(g_ldj), _ptr(g_x), _ptr(flat),
+                                               _ptr(self._ws), self._ws.numel() * 4, _stream_ptr()))
         grads, off = [], 0
         for t, size in zip(self.params, self._sizes):
             grads.append(None if t is None else flat[off:off + size].view(t.shape))
@@ -1767,9 +1682,7 @@ class NativeTrainer:
         return g_x, grads
 
     def backward_x_workspace_bytes(self, n):
-        nb = C.c_int64()
-        _check(lib().gbnf_trainer_backward_x_workspace_bytes(self.handle, int(n), C.byref(nb)))
-        return int(nb.value)
+        return _query_i64(lib().gbnf_trainer_backward_x_workspace_bytes, self.handle, int(n))
 
     def backward_x(self, x, g_z=None, g_ldj=None, trace=None, g_x=None, workspace=None):
         """The gradient with respect to the input alone (gbnf_trainer_backward_x): the sweeps of ``backward`` with no weight-gradient
@@ -1792,10 +1705,9 @@ class NativeTrainer:
                 raise GbnfError(f"g_ldj must be ({n},), got {tuple(g_ldj.shape)}")
         if trace is not None:
             _require_device_f32(trace, "trace")
-            nt = C.c_int64()
-            _check(lib().gbnf_trainer_trace_floats(self.handle, n, C.byref(nt)))
-            if trace.numel() != nt.value:
-                raise GbnfError(f"trace has {trace.numel()} floats: not this trainer's at n = {n} ({nt.value})")
+            nt = _query_i64(lib().gbnf_trainer_trace_floats, self.handle, n)
+            if trace.numel() != nt:
+                raise GbnfError(f"trace has {trace.numel()} floats: not this trainer's at n = {n} ({nt})")
         accumulate = g_x is not None
         if accumulate:
             _require_device_f32(g_x, "g_x")
@@ -1806,17 +1718,11 @@ class NativeTrainer:
         if not n:
             return g_x
         if workspace is None:
-            nb = self.backward_x_workspace_bytes(n)
-            ws = getattr(self, "_bx_ws", None)
-            if ws is None or ws.numel() * 4 < nb or ws.device != x.device:
-                ws = self._bx_ws = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
+            ws = self._bx_ws = _grown(getattr(self, "_bx_ws", None), self.backward_x_workspace_bytes(n), x.device)
         else:
-            ws = workspace
-            if not isinstance(ws, torch.Tensor) or not ws.is_cuda or not ws.is_contiguous():
-                raise GbnfError("workspace must be a contiguous device tensor")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_trainer_backward_x(self.handle, ptr(x), n, ptr(trace), ptr(g_z), ptr(g_ldj), ptr(g_x), 1 if accumulate else 0,
-                                             ptr(ws), ws.numel() * ws.element_size(), _stream_ptr()))
+            ws = _check_workspace(workspace)
+        _check(lib().gbnf_trainer_backward_x(self.handle, _ptr(x), n, _ptr(trace), _ptr(g_z), _ptr(g_ldj), _ptr(g_x), 1 if accumulate else 0,
+                                             _ptr(ws), ws.numel() * ws.element_size(), _stream_ptr()))
         return g_x
 
     def repair_count(self, reset=False):
@@ -1825,20 +1731,6 @@ class NativeTrainer:
         n = C.c_int64(0)
         _check(lib().gbnf_trainer_repair_count(self.handle, C.byref(n), 1 if reset else 0))
         return int(n.value)
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().gbnf_trainer_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
-
-
-NativeImageTrainer._hyper = NativeTrainer._hyper
 
 
 class OptState:
@@ -1969,14 +1861,15 @@ def mixture_from_specs(specs, math="default"):
         return NativeMixture(flows), flows
 
 
-class NativeMixture:
+class NativeMixture(_Handle):
     """C same-architecture components behind one launch (gbnf_mixture)."""
+
+    _destroy = "gbnf_mixture_destroy"
 
     def __init__(self, flows):
         self.flows = list(flows)           # keeps the NativeFlow handles alive
-        arr = (C.c_void_p * len(self.flows))(*[f.handle for f in self.flows])
         h = C.c_void_p()
-        _check(lib().gbnf_mixture_create(arr, len(self.flows), C.byref(h)))
+        _check(lib().gbnf_mixture_create(_handle_array(self.flows), len(self.flows), C.byref(h)))
         self.handle = h
         self.d = self.flows[0].d
 
@@ -2032,9 +1925,8 @@ class NativeMixture:
         ldj = torch.empty((k, n), dtype=torch.float32, device=x.device) if want_ldj else None
         ll = torch.empty((k, n), dtype=torch.float32, device=x.device) if want_ll else None
         if n and k:
-            ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
             _check(lib().gbnf_mixture_component_forward(self.handle, C.c_void_p(x.data_ptr()), n, c_begin, c_end,
-                                                        ptr(z), ptr(ldj), ptr(ll), _stream_ptr()))
+                                                        _ptr(z), _ptr(ldj), _ptr(ll), _stream_ptr()))
         return z, ldj, ll
 
     def prepared_component_log_prob(self, x, out, c_begin=0, c_end=None, col_offset=0):
@@ -2148,21 +2040,9 @@ class NativeMixture:
             raise GbnfError(f"component = {component} outside [0, {n_used})")
         if n == 0:                              # (an empty batch adds nothing, `batches` included: there is nothing to launch)
             return G
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-        _check(lib().gbnf_mixture_evaluate(self.handle, ptr(x), n, n_used, int(component), ptr(rho), ptr(table), ptr(G), ptr(state), ptr(ws),
+        _check(lib().gbnf_mixture_evaluate(self.handle, _ptr(x), n, n_used, int(component), _ptr(rho), _ptr(table), _ptr(G), _ptr(state), _ptr(ws),
                                            ws.numel() * ws.element_size(), _stream_ptr()))
         return G
-
-    def close(self):
-        if getattr(self, "handle", None):
-            lib().gbnf_mixture_destroy(self.handle)
-            self.handle = None
-
-    def __del__(self):
-        try:
-            self.close()
-        except Exception:
-            pass
 
 
 class Comm:
@@ -2259,9 +2139,8 @@ class GroupLaunch:
             raise GbnfError("GroupLaunch: ll_full must be (C, len(xs) * n)")
         self._keep = (mix, comm, list(xs), rho, ll_local, ll_full, G)
         self._arr = (C.c_void_p * len(xs))(*[t.data_ptr() for t in xs])
-        ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
         self._args = (mix.handle, comm.handle if comm is not None else C.c_void_p(0), self._arr, len(xs), n, int(n_components),
-                      ptr(rho), ptr(ll_local), ptr(ll_full), ptr(G))
+                      _ptr(rho), _ptr(ll_local), _ptr(ll_full), _ptr(G))
         self.graph, self.graph_error = None, None
         if graph:
             h = C.c_void_p()
@@ -2329,11 +2208,7 @@ _eval_ws = {}      # device -> the partial-sum scratch of the accumulate calls
 
 def _eval_workspace(device, n):
     import torch
-    nb = C.c_int64()
-    _check(lib().gbnf_eval_workspace_bytes(n, C.byref(nb)))
-    ws = _eval_ws.get(device)
-    if ws is None or ws.numel() * 8 < nb.value:
-        ws = _eval_ws[device] = torch.empty((nb.value + 7) // 8, dtype=torch.float64, device=device)
+    ws = _eval_ws[device] = _grown(_eval_ws.get(device), _query_i64(lib().gbnf_eval_workspace_bytes, n), device, torch.float64)
     return ws
 
 
@@ -2356,8 +2231,7 @@ def eval_accumulate(ll, rho, component, state, want_G=False, workspace=None):
     G = torch.empty(n, dtype=torch.float32, device=ll.device) if want_G else None
     if n == 0 and 0 <= int(component) < n_used:      # (an empty table has no address to hand over; the library adds nothing for it)
         return G
-    ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else 0)
-    _check(lib().gbnf_eval_accumulate(ptr(ll), stride, n_used, n, ptr(rho), int(component), ptr(G), ptr(state), ptr(ws),
+    _check(lib().gbnf_eval_accumulate(_ptr(ll), stride, n_used, n, _ptr(rho), int(component), _ptr(G), _ptr(state), _ptr(ws),
                                       ws.numel() * ws.element_size(), _stream_ptr()))
     return G
 
@@ -2378,8 +2252,7 @@ def eval_accumulate_class_loss(y_logits, y, rho, c, state, n_used=None, workspac
     if rho.dim() != 1 or rho.numel() < n_used:
         raise GbnfError("rho shorter than n_used")
     ws = _eval_workspace(y.device, n) if workspace is None else workspace
-    ptr = lambda t: C.c_void_p(t.data_ptr())
-    _check(lib().gbnf_eval_accumulate_class_loss(ptr(y_logits), ptr(y), n, Y, ptr(rho), n_used, int(c), ptr(state), ptr(ws),
+    _check(lib().gbnf_eval_accumulate_class_loss(_ptr(y_logits), _ptr(y), n, Y, _ptr(rho), n_used, int(c), _ptr(state), _ptr(ws),
                                                  ws.numel() * ws.element_size(), _stream_ptr()))
 
 
@@ -2418,12 +2291,9 @@ def weights_em(ll, rho, max_iters, tol, state=None, workspace=None):
         raise GbnfError("rho shorter than the number of components")
     state = weights_state(ll.device) if state is None else _require_weights_state(state)
     stride = ll.stride(0) if n_comp > 1 else max(n, 1)
-    nb = C.c_int64()
-    _check(lib().gbnf_weights_em_workspace_bytes(n_comp, n, C.byref(nb)))
+    nb = _query_i64(lib().gbnf_weights_em_workspace_bytes, n_comp, n)
     if workspace is None:
-        workspace = _weights_ws.get(ll.device)
-        if workspace is None or workspace.numel() * 8 < nb.value:
-            workspace = _weights_ws[ll.device] = torch.empty((nb.value + 7) // 8, dtype=torch.float64, device=ll.device)
+        workspace = _weights_ws[ll.device] = _grown(_weights_ws.get(ll.device), nb, ll.device, torch.float64)
     # (an empty table has no address to hand over; no row of it is read: rho's stands in)
     llp = C.c_void_p(ll.data_ptr() if ll.numel() else rho.data_ptr())
     _check(lib().gbnf_weights_em(llp, stride, n_comp, n, C.c_void_p(rho.data_ptr()), int(max_iters), float(tol),
@@ -2505,9 +2375,8 @@ def class_posterior(class_ll, log_prior=None, want_post=True, want_pred=False):
     log_px = torch.empty(n, dtype=torch.float32, device=class_ll.device)
     post = torch.empty((n, Y), dtype=torch.float32, device=class_ll.device) if want_post else None
     pred = torch.empty(n, dtype=torch.int32, device=class_ll.device) if want_pred else None
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
     if n:
-        _check(lib().gbnf_class_posterior(ptr(class_ll), ptr(log_prior), n, Y, ptr(log_px), ptr(post), ptr(pred), _stream_ptr()))
+        _check(lib().gbnf_class_posterior(_ptr(class_ll), _ptr(log_prior), n, Y, _ptr(log_px), _ptr(post), _ptr(pred), _stream_ptr()))
     return log_px, post, pred
 
 
@@ -2536,9 +2405,8 @@ def tabular_score_seed(z, r=None, base=None, want_ll=False):
     g_z = torch.empty_like(z)
     g_ldj = torch.empty(n, dtype=torch.float32, device=z.device)
     ll = torch.empty(n, dtype=torch.float32, device=z.device) if want_ll else None
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
     if n:
-        _check(lib().gbnf_score_seed(ptr(z), ptr(mean), ptr(std), ptr(r), n, d, ptr(g_z), ptr(g_ldj), ptr(ll), _stream_ptr()))
+        _check(lib().gbnf_score_seed(_ptr(z), _ptr(mean), _ptr(std), _ptr(r), n, d, _ptr(g_z), _ptr(g_ldj), _ptr(ll), _stream_ptr()))
     return (g_z, g_ldj, ll) if want_ll else (g_z, g_ldj)
 
 
@@ -2575,9 +2443,8 @@ def score_seed(z, prior=None, r=None, base=None, want_ll=False):
             raise GbnfError(f"r must be ({n},), got {tuple(r.shape)}")
     g_z = torch.empty_like(z)
     g_ldj = torch.empty(n, dtype=torch.float32, device=z.device)
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None and t.numel() else C.c_void_p(0)
     if n:
-        _check(lib().gbnf_image_score_seed(ptr(z), ptr(prior), stride, ptr(r), n, cz, int(z.shape[2] * z.shape[3]), ptr(g_z), ptr(g_ldj),
+        _check(lib().gbnf_image_score_seed(_ptr(z), _ptr(prior), stride, _ptr(r), n, cz, int(z.shape[2] * z.shape[3]), _ptr(g_z), _ptr(g_ldj),
                                            _stream_ptr()))
     return g_z, g_ldj
 
@@ -2599,11 +2466,15 @@ def mixture_responsibilities(ll, log_w):
     return r, G
 
 
+def _open_trainers(trainers, cls):
+    trainers = list(trainers)
+    if not trainers or any(not isinstance(t, cls) or not t.handle for t in trainers):
+        raise GbnfError(f"trainers must be a non-empty sequence of open {cls.__name__}s")
+    return trainers
+
+
 def image_mixture_score_workspace_bytes(trainers, n):
-    arr = (C.c_void_p * len(trainers))(*[t.handle for t in trainers])
-    nb = C.c_int64()
-    _check(lib().gbnf_image_mixture_score_workspace_bytes(arr, len(trainers), int(n), C.byref(nb)))
-    return int(nb.value)
+    return _query_i64(lib().gbnf_image_mixture_score_workspace_bytes, _handle_array(trainers), len(trainers), int(n))
 
 
 def image_mixture_score(trainers, log_w, x, noise=None, y=None, want_r=False, workspace=None):
@@ -2612,20 +2483,13 @@ def image_mixture_score(trainers, log_w, x, noise=None, y=None, want_r=False, wo
     log p(x), r (C, n) | None).  ``noise`` is shared by the components and held fixed; ``y`` (n, Y) for conditioned trainers.
     ``workspace``: a contiguous device tensor to use (None: allocated here; its size is checked by the library)."""
     import torch
-    trainers = list(trainers)
-    if not trainers or any(not isinstance(t, NativeImageTrainer) or not t.handle for t in trainers):
-        raise GbnfError("trainers must be a non-empty sequence of open NativeImageTrainers")
+    trainers = _open_trainers(trainers, NativeImageTrainer)
     _require_device_f32(x, "x")
     if x.dim() != 4 or any(tuple(x.shape[1:]) != t.input_size for t in trainers):
         raise GbnfError(f"x must be (n,{trainers[0].input_size}) for every trainer, got {tuple(x.shape)}")
     n = x.shape[0]
-    if noise is not None:
-        _require_device_f32(noise, "noise")
-        if noise.shape != x.shape:
-            raise GbnfError("noise must have the shape of x")
-    _require_device_f32(log_w, "log_w")
-    if tuple(log_w.shape) != (len(trainers),):
-        raise GbnfError(f"log_w must be ({len(trainers)},), got {tuple(log_w.shape)}")
+    _check_noise(noise, x)
+    _check_log_w(log_w, len(trainers))
     conditioned = [t.y_classes > 0 for t in trainers]
     if any(conditioned) and (not all(conditioned) or y is None):
         raise GbnfError("class-conditional trainers need y (n, Y), and every trainer of the call must be conditioned")
@@ -2635,31 +2499,16 @@ def image_mixture_score(trainers, log_w, x, noise=None, y=None, want_r=False, wo
     G = torch.empty(n, dtype=torch.float32, device=x.device)
     r = torch.empty((len(trainers), n), dtype=torch.float32, device=x.device) if want_r else None
     if n:
-        arr = (C.c_void_p * len(trainers))(*[t.handle for t in trainers])
-        if workspace is None:
-            nb = image_mixture_score_workspace_bytes(trainers, n)
-            workspace = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
-        elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
-            raise GbnfError("workspace must be a contiguous device tensor")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_image_mixture_score(arr, len(trainers), ptr(log_w), ptr(x), ptr(noise), ptr(y), n, ptr(g_x), ptr(G), ptr(r),
-                                              ptr(workspace), workspace.numel() * workspace.element_size(), _stream_ptr()))
+        workspace = _workspace_arg(workspace, lambda: image_mixture_score_workspace_bytes(trainers, n), x.device)
+        _check(lib().gbnf_image_mixture_score(_handle_array(trainers), len(trainers), _ptr(log_w), _ptr(x), _ptr(noise), _ptr(y), n,
+                                              _ptr(g_x), _ptr(G), _ptr(r), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                              _stream_ptr()))
     return g_x, G, r
 
 
-def _open_trainers(trainers):
-    trainers = list(trainers)
-    if not trainers or any(not isinstance(t, NativeTrainer) or not t.handle for t in trainers):
-        raise GbnfError("trainers must be a non-empty sequence of open NativeTrainers")
-    return trainers
-
-
 def mixture_score_workspace_bytes(trainers, n):
-    trainers = _open_trainers(trainers)
-    arr = (C.c_void_p * len(trainers))(*[t.handle for t in trainers])
-    nb = C.c_int64()
-    _check(lib().gbnf_mixture_score_workspace_bytes(arr, len(trainers), int(n), C.byref(nb)))
-    return int(nb.value)
+    trainers = _open_trainers(trainers, NativeTrainer)
+    return _query_i64(lib().gbnf_mixture_score_workspace_bytes, _handle_array(trainers), len(trainers), int(n))
 
 
 def mixture_score(trainers, log_w, x, ll=None, base=None, want_r=False, workspace=None):
@@ -2671,14 +2520,12 @@ def mixture_score(trainers, log_w, x, ll=None, base=None, want_r=False, workspac
     forward on the running statistics: a ``forward(want_trace=True)`` made in batch-statistics mode before it must not be followed
     by its ``backward`` after it (the BatchNorm entries that backward reads were re-derived; ``BoostedFlow`` raises in that case)."""
     import torch
-    trainers = _open_trainers(trainers)
+    trainers = _open_trainers(trainers, NativeTrainer)
     _require_device_f32(x, "x")
     if x.dim() != 2 or any(x.shape[1] != t.d for t in trainers):
         raise GbnfError(f"x must be (n,{trainers[0].d}) for every trainer, got {tuple(x.shape)}")
     n, nc = x.shape[0], len(trainers)
-    _require_device_f32(log_w, "log_w")
-    if tuple(log_w.shape) != (nc,):
-        raise GbnfError(f"log_w must be ({nc},), got {tuple(log_w.shape)}")
+    _check_log_w(log_w, nc)
     if ll is not None:
         _require_device_f32(ll, "ll")
         if tuple(ll.shape) != (nc, n):
@@ -2694,24 +2541,15 @@ def mixture_score(trainers, log_w, x, ll=None, base=None, want_r=False, workspac
     G = torch.empty(n, dtype=torch.float32, device=x.device)
     r = torch.empty((nc, n), dtype=torch.float32, device=x.device) if want_r else None
     if n:
-        arr = (C.c_void_p * nc)(*[t.handle for t in trainers])
-        if workspace is None:
-            nb = mixture_score_workspace_bytes(trainers, n)
-            workspace = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
-        elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
-            raise GbnfError("workspace must be a contiguous device tensor")
-        ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-        _check(lib().gbnf_mixture_score(arr, nc, ptr(log_w), ptr(mean), ptr(std), ptr(ll), ptr(x), n, ptr(g_x), ptr(G), ptr(r),
-                                        ptr(workspace), workspace.numel() * workspace.element_size(), _stream_ptr()))
+        workspace = _workspace_arg(workspace, lambda: mixture_score_workspace_bytes(trainers, n), x.device)
+        _check(lib().gbnf_mixture_score(_handle_array(trainers), nc, _ptr(log_w), _ptr(mean), _ptr(std), _ptr(ll), _ptr(x), n, _ptr(g_x),
+                                        _ptr(G), _ptr(r), _ptr(workspace), workspace.numel() * workspace.element_size(), _stream_ptr()))
     return g_x, G, r
 
 
 def mixture_step_workspace_bytes(trainers, n):
-    trainers = _open_trainers(trainers)
-    arr = (C.c_void_p * len(trainers))(*[t.handle for t in trainers])
-    nb = C.c_int64()
-    _check(lib().gbnf_mixture_step_workspace_bytes(arr, len(trainers), int(n), C.byref(nb)))
-    return int(nb.value)
+    trainers = _open_trainers(trainers, NativeTrainer)
+    return _query_i64(lib().gbnf_mixture_step_workspace_bytes, _handle_array(trainers), len(trainers), int(n))
 
 
 def mixture_nll_step(trainers, states, log_w, x, *, lr, weight_decay=0.0, max_grad_norm=0.0, betas=(0.9, 0.999), eps=1e-8, want_G=False,
@@ -2726,7 +2564,7 @@ def mixture_nll_step(trainers, states, log_w, x, *, lr, weight_decay=0.0, max_gr
     ``workspace``: a contiguous device tensor to use (None: allocated here; its size is checked by the library).  The parameters
     change behind autograd's back: no version counter moves (``BoostedFlow.mixture_training_step`` takes care of that)."""
     import torch
-    trainers = _open_trainers(trainers)
+    trainers = _open_trainers(trainers, NativeTrainer)
     nc = len(trainers)
     states = list(states)
     if len(states) != nc or any(not isinstance(s, OptState) for s in states):
@@ -2738,30 +2576,25 @@ def mixture_nll_step(trainers, states, log_w, x, *, lr, weight_decay=0.0, max_gr
     if x.dim() != 2 or x.shape[0] < 1 or any(x.shape[1] != t.d for t in trainers):
         raise GbnfError(f"x must be (n,{trainers[0].d}) with n >= 1 for every trainer, got {tuple(x.shape)}")
     n = x.shape[0]
-    _require_device_f32(log_w, "log_w")
-    if tuple(log_w.shape) != (nc,):
-        raise GbnfError(f"log_w must be ({nc},), got {tuple(log_w.shape)}")
+    _check_log_w(log_w, nc)
     if len({s.kind for s in states}) != 1:
         raise GbnfError("states must be of one optimiser kind")
     hypers = (_OptHyper * nc)()
     for c, (t, s) in enumerate(zip(trainers, states)):
         s.check(t)
         hypers[c] = t._hyper(s, lr=lrs[c], weight_decay=weight_decay, max_grad_norm=max_grad_norm, betas=betas, eps=eps)
-    if workspace is None:
-        nb = mixture_step_workspace_bytes(trainers, n)
-        workspace = torch.empty((nb + 3) // 4, dtype=torch.float32, device=x.device)
-    elif not isinstance(workspace, torch.Tensor) or not workspace.is_cuda or not workspace.is_contiguous():
-        raise GbnfError("workspace must be a contiguous device tensor")
+    if workspace is None:        # (in line, without _workspace_arg's closure: this is the per-step path)
+        workspace = torch.empty((mixture_step_workspace_bytes(trainers, n) + 3) // 4, dtype=torch.float32, device=x.device)
+    else:
+        _check_workspace(workspace)
     flats = [torch.empty(t.grad_floats, dtype=torch.float32, device=x.device) for t in trainers]
     stats = torch.zeros(4 + 2 * nc, dtype=torch.float32, device=x.device)
     G = torch.empty(n, dtype=torch.float32, device=x.device) if want_G else None
     r = torch.empty((nc, n), dtype=torch.float32, device=x.device) if want_r else None
-    ptr = lambda t: C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
-    addr = lambda ts: (C.c_void_p * nc)(*[None if t is None else t.data_ptr() for t in ts])
-    arr = (C.c_void_p * nc)(*[t.handle for t in trainers])
-    _check(lib().gbnf_mixture_nll_step(arr, nc, ptr(log_w), ptr(x), n, addr(flats), addr([s.exp_avg for s in states]),
-                                       addr([s.exp_avg_sq for s in states]), hypers, ptr(stats), ptr(G), ptr(r), ptr(workspace),
-                                       workspace.numel() * workspace.element_size(), _stream_ptr()))
+    _check(lib().gbnf_mixture_nll_step(_handle_array(trainers), nc, _ptr(log_w), _ptr(x), n, _addr_array(flats),
+                                       _addr_array([s.exp_avg for s in states]), _addr_array([s.exp_avg_sq for s in states]), hypers,
+                                       _ptr(stats), _ptr(G), _ptr(r), _ptr(workspace), workspace.numel() * workspace.element_size(),
+                                       _stream_ptr()))
     for s in states:
         s.step += 1
     return stats, flats, G, r
@@ -2820,12 +2653,10 @@ def resample_rows(w, u):
     _require_device_f32(u, "u")
     if w.dim() != 1 or w.numel() < 1 or u.dim() != 1 or u.numel() < 1:
         raise GbnfError("w must be (n,) and u (m,) with n, m >= 1")
-    nb = C.c_int64()
-    _check(lib().gbnf_resample_workspace_bytes(w.numel(), C.byref(nb)))
-    cdf = torch.empty(nb.value // 8, dtype=torch.float64, device=w.device)
+    nb = _query_i64(lib().gbnf_resample_workspace_bytes, w.numel())
+    cdf = torch.empty(nb // 8, dtype=torch.float64, device=w.device)
     rows = torch.empty(u.numel(), dtype=torch.int64, device=w.device)
-    _check(lib().gbnf_resample_rows(C.c_void_p(w.data_ptr()), w.numel(), C.c_void_p(u.data_ptr()), u.numel(),
-                                    C.c_void_p(rows.data_ptr()), C.c_void_p(cdf.data_ptr()), nb.value, _stream_ptr()))
+    _check(lib().gbnf_resample_rows(_ptr(w), w.numel(), _ptr(u), u.numel(), _ptr(rows), _ptr(cdf), nb, _stream_ptr()))
     return rows
 
 
@@ -2834,12 +2665,11 @@ _sample_ws = {}        # device -> workspace of mixture_partition / mixture_samp
 
 def _sample_workspace(n_flows, n, d, device):
     import torch
-    nb = C.c_int64()
-    _check(lib().gbnf_mixture_sample_workspace_bytes(int(n_flows), int(n), int(d), C.byref(nb)))
+    nb = _query_i64(lib().gbnf_mixture_sample_workspace_bytes, int(n_flows), int(n), int(d))
     ws = _sample_ws.get(str(device))
-    if ws is None or ws.numel() * 4 < nb.value:
-        ws = _sample_ws[str(device)] = torch.empty(nb.value // 4, dtype=torch.float32, device=device)
-    return ws, nb.value
+    if ws is None or ws.numel() * 4 < nb:
+        ws = _sample_ws[str(device)] = torch.empty(nb // 4, dtype=torch.float32, device=device)
+    return ws, nb
 
 
 def mixture_partition(rho, u, n_used=None, z=None):
@@ -2892,7 +2722,7 @@ def mixture_sample(flows, rho, u, z, n_used=None, want_ldj=True, out=None):
     if tuple(x.shape) != (n, d):
         raise GbnfError(f"out must be ({n},{d}), got {tuple(x.shape)}")
     ldj = torch.empty(n, dtype=torch.float32, device=z.device) if want_ldj else None
-    handles = (C.c_void_p * n_used)(*[f.handle for f in flows[:n_used]])
+    handles = _handle_array(flows[:n_used])
     host = (C.c_int64 * n_used)(*counts.cpu().tolist())
     _check(lib().gbnf_mixture_sample_finish(handles, n_used, host, C.c_void_p(order.data_ptr()), n, C.c_void_p(x.data_ptr()),
                                             C.c_void_p(ldj.data_ptr() if ldj is not None else 0), C.c_void_p(ws.data_ptr()),
